@@ -18,6 +18,9 @@ from rank 0 once (RCCL) and the per-step move records are gathered to rank 0 ove
 (weak scaling).  Launch: `python bench.py --gpus N` from a bare shell starts the N ranks itself (fresh interpreters,
 the launcher never touches a GPU; fewer than N visible devices is an error); under torch.distributed.run (RANK /
 WORLD_SIZE in the environment) the process is one rank.  N = 1 runs the same code with a one-rank process group.
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds the legs that take runs of their own
+(config3_avg8, steady_state, roofline_saturated, cpu_baseline).  --dump-outputs DIR writes what the last timed step handed
+to its caller (the step's move tuples as gathered to rank 0) as DIR/<field>.npy, for output-by-output comparison of builds.
 """
 import argparse
 import json
@@ -57,8 +60,9 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N>1 path on fewer GPUs than ranks (ranks share devices, CPU tensors in the collectives)")
     ap.add_argument("--plain-net", type=int, default=0, help="1: plain PyTorch module instead of the fused inference net")
-    ap.add_argument("--saturated", type=int, default=1, help="also time board_advance on a chip-filling dense batch")
-    ap.add_argument("--steady-state", type=int, default=1, help="also measure run_selfplay-style operation with slot turnover")
+    ap.add_argument("--saturated", type=int, default=None, help="also time board_advance on a chip-filling dense batch (default: on with --full)")
+    ap.add_argument("--steady-state", type=int, default=None, help="also measure run_selfplay-style operation with slot turnover "
+                    "(default: on with --full)")
     ap.add_argument("--steady-moves", type=int, default=5, help="num_moves cap of the steady-state games (short, so slots turn over)")
     ap.add_argument("--steady-generations", type=int, default=2, help="games per slot in the steady-state leg")
     ap.add_argument("--writer-processes", type=int, default=0, help="steady-state leg: conf['WRITER_PROCESSES'] (0 = writer threads)")
@@ -72,13 +76,50 @@ def parse():
     ap.add_argument("--gather-collective", default="gather", choices=["gather", "all_gather"])
     ap.add_argument("--gather-flush", type=int, default=0, help="1: complete every step's gather before the next step (blocking form, A/B)")
     ap.add_argument("--gather", type=int, default=1, help="0: skip the per-step tuple gather (A/B of its cost on small configurations)")
-    ap.add_argument("--avg8-leg", type=int, default=1, help="headline configuration only: one warm-up + one step with 8-fold symmetry "
-                    "averaging (BASELINE config 3 as written), reported as config3_avg8")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--avg8-leg", type=int, default=None, help="headline configuration only: one warm-up + one step with 8-fold symmetry "
+                    "averaging (BASELINE config 3 as written), reported as config3_avg8 (default: on with --full)")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="the oracle + torch CPU comparator (default: on with --full)")
     ap.add_argument("--cpu-games", type=int, default=32, help="concurrent games of the CPU baseline (the reference's N_GAME_PROCESS, conf.py:30)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="wall-clock budget of the CPU baseline sample")
     ap.add_argument("--cpu-moves", type=int, default=1)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: config3_avg8, steady_state, "
+                    "roofline_saturated, cpu_baseline (each can still be switched off by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's move tuples "
+                    "(as gathered to rank 0) as DIR/<field>.npy in float32 / float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for leg in ("avg8_leg", "cpu_baseline", "saturated", "steady_state"):
+        if getattr(args, leg) is None:
+            setattr(args, leg, int(args.full))
+    return args
+
+
+DUMP_LIMIT = 64 << 20     # bytes of .npy data --dump-outputs may write; a larger step is sampled by rows (fixed seed)
+
+
+def dump_outputs(out_dir, tuples):
+    """The last timed step's move tuples (what a caller of the step receives: one row per move played, in slot order),
+    one file per field: integer fields as float64 (exact), value / pi as float32.  `z` is left out: it is only known when
+    the game ends and is NaN in every tuple of a step.  Above DUMP_LIMIT a fixed, seeded sample of rows is written and
+    its row numbers go to row.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {}
+    for name in tuples.dtype.names:
+        if name == "z":
+            continue
+        a = tuples[name]
+        cols[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    row_bytes = sum(a[:1].nbytes for a in cols.values()) + 8
+    n = len(tuples)
+    if n * row_bytes > DUMP_LIMIT:
+        keep = np.sort(np.random.RandomState(0).choice(n, DUMP_LIMIT // row_bytes, replace=False))
+        cols = {k: a[keep] for k, a in cols.items()}
+        cols["row"] = keep.astype(np.float64)
+    for k, a in cols.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(cols)
 
 
 def cpu_baseline(args, size, sims, energy, n_blocks, channels, symmetry):
@@ -366,6 +407,7 @@ def run_rank(args):
     tdt = tuple_dtype(S)
     exchange = TupleGather(tdt, side_stream=(args.gather_stream == "side"), collective=args.gather_collective)          # three-stage pipeline, recycled pinned staging
     gathered = [0]
+    last = {"local": None, "gathered": None}      # the newest step's tuples: this rank's, and the newest batch gathered on rank 0
     rccl = device_identities()           # which physical device every rank computes on (N ranks must show N distinct devices)
 
     restarts = [0]
@@ -401,10 +443,12 @@ def run_rank(args):
                 r["game_seq"] = mv["game_seq"]
                 k += 1
             eng.records[s] = []
+        last["local"] = recs[:k]
         h2 = time.perf_counter()
         if args.gather:
             for got in exchange.submit(recs[:k]) + (exchange.flush() if args.gather_flush else []):
                 gathered[0] += 0 if got is None else len(got)
+                last["gathered"] = got
         h3 = time.perf_counter()
         host_s["drain"] += h1 - h0; host_s["tuples"] += h2 - h1; host_s["gather_submit"] += h3 - h2
 
@@ -430,6 +474,7 @@ def run_rank(args):
         one_step()
     for got in exchange.flush():             # the last two steps' tuples: the timed region ends with every tuple on rank 0
         gathered[0] += 0 if got is None else len(got)
+        last["gathered"] = got
     sync()
     dt = time.perf_counter() - t0
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
@@ -537,6 +582,10 @@ def run_rank(args):
             except Exception:
                 pass
         eng.close()
+        if args.dump_outputs:
+            # batches arrive on rank 0 in submission order, so the newest one is the last timed step's; without the gather
+            # (--gather 0) the step hands rank 0 its own tuples
+            dump_outputs(args.dump_outputs, last["gathered"] if args.gather else last["local"])
         if (args.avg8_leg and world == 1 and args.symmetry == "random1" and args.net == "resnet" and not args.plain_net
                 and (S, sims, G, args.blocks, args.channels) == (19, 400, 1024, 20, 256)):
             try:

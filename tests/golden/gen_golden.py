@@ -935,8 +935,29 @@ SYNC_CASES = [
 ]
 
 
-def run_child(args, cwd):
-    env = dict(os.environ)
+# extra random playouts under other seeds (tests/test_oracle_vs_reference_live.py): (size, SGO_GOLDEN_SEED)
+SEEDED_RULES_CASES = [(5, 101), (9, 202), (13, 303)]
+
+
+def entry_imports(out):
+    """The names the reference's main_selfplay.py imports, as [module, name] pairs (tests/test_entry_path.py checks that the
+    package's mirrors provide every one of them under the reference's module names)."""
+    import ast
+    import json
+    tree = ast.parse(open(os.path.join(REF, "main_selfplay.py")).read())
+    pairs = []
+    for node in tree.body:
+        if isinstance(node, ast.ImportFrom):
+            pairs += [[node.module, a.name] for a in node.names]
+        elif isinstance(node, ast.Import):
+            pairs += [[a.name, None] for a in node.names]
+    with open(out, "w") as f:
+        json.dump({"file": "main_selfplay.py", "imports": pairs}, f, indent=1)
+        f.write("\n")
+
+
+def run_child(args, cwd, **extra_env):
+    env = dict(os.environ, **extra_env)
     env["PYTHONDONTWRITEBYTECODE"] = "1"
     cmd = [sys.executable, os.path.abspath(__file__), "--child"] + [str(a) for a in args]
     print("+", " ".join(cmd[2:]), flush=True)
@@ -974,6 +995,11 @@ def main():
     if only in (None, "rules"):
         for s in (5, 7, 9, 13, 19):
             run_child(["rules", s, os.path.join(HERE, "rules_S%d.npz" % s)], scratch)
+    if only in (None, "rules", "seeded_rules"):
+        for s, seed in SEEDED_RULES_CASES:
+            run_child(["rules", s, os.path.join(HERE, "rules_S%d_seed%d.npz" % (s, seed))], scratch, SGO_GOLDEN_SEED=str(seed))
+    if only in (None, "entry"):
+        entry_imports(os.path.join(HERE, "main_selfplay_imports.json"))
     if only in (None, "sgf"):
         run_child(["sgf", os.path.join(HERE, "sgf_S19.npz")], scratch)
     if only in (None, "sym"):

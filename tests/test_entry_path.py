@@ -1,8 +1,9 @@
 """The self-play ENTRY path: main_selfplay.main() -> init_predicting_workers / put_name_request in a GPU-free
 parent -> NoModelSelfPlayWorker processes (main_selfplay.py:9-29, selfplay_worker.py:61-130).
 
-CPU part: the parent never touches the GPU runtime; the reference's own main_selfplay.py runs unchanged on this
-package's modules (INTEGRATION.md §A recipe) and starts / joins N_GAME_PROCESS workers; model loader branches.
+CPU part: the parent never touches the GPU runtime; every name the reference's main_selfplay.py imports exists on this
+package's modules under the reference's names (INTEGRATION.md §A recipe), and main() starts / joins N_GAME_PROCESS
+workers there; model loader branches.
 GPU part: the whole flow on the device, by fork (fresh parent) and by spawn (parent that already used the GPU),
 the sync SelfPlayWorker, and that the shipped path runs the hand-written tower convolution."""
 import glob
@@ -15,7 +16,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
 
 CONF_SNIPPET = """
 import os, sys
@@ -53,16 +53,23 @@ def test_parent_side_calls_do_not_touch_the_gpu(tmp_path):
     assert "NAME model_1" in out
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "main_selfplay.py")), reason="reference checkout absent")
-def test_reference_main_selfplay_runs_on_the_mirrors(tmp_path):
-    """the reference's main_selfplay.py, unchanged, with this package's modules under the
-    reference's names.  run_selfplay (the GPU body) is replaced by a marker writer: the test is about imports,
-    the loop, and that N_GAME_PROCESS workers are started (by fork, from a GPU-free parent) and joined."""
+def test_main_selfplay_runs_on_the_mirrors(tmp_path):
+    """the reference's main_selfplay.py runs on this package's modules under the reference's names.  Every
+    name that file imports (recorded from it by tests/golden/gen_golden.py --only entry) must exist on the mirrors installed
+    under those names; then main() runs its loop there, with run_selfplay (the GPU body) replaced by a marker writer: the test
+    is about imports, the loop, and that N_GAME_PROCESS workers are started (by fork, from a GPU-free parent) and joined."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "main_selfplay_imports.json")) as f:
+        imports = json.load(f)["imports"]
+    assert len(imports) >= 7
     out = _run(CONF_SNIPPET.format(root=ROOT, tmp=str(tmp_path)) + textwrap.dedent("""
         import importlib
         for name in ("conf", "play", "symmetry", "tree_util", "self_play", "nomodel_self_play", "predicting_queue_worker",
-                     "simulation_workers", "selfplay_worker", "sgfsave", "utils", "model", "go_game"):
+                     "simulation_workers", "selfplay_worker", "sgfsave", "utils", "model", "go_game", "main_selfplay"):
             sys.modules[name] = importlib.import_module("sejonggo_amd." + name)
+        for mod, attr in %r:
+            m = importlib.import_module(mod)
+            assert attr is None or hasattr(m, attr), "%%s.%%s" %% (mod, attr)
         conf['N_GAME_PROCESS'] = 2
         conf['GPUs'] = [0, 1]
         import selfplay_worker
@@ -73,13 +80,11 @@ def test_reference_main_selfplay_runs_on_the_mirrors(tmp_path):
             open(os.path.join(%r, "worker_gpu%%d_pid%%d_ppid%%d" %% (gpu_id, os.getpid(), os.getppid())), "w").write(indicator)
             return 0
         selfplay_worker.run_selfplay = fake_run_selfplay
-        sys.path.append(%r)
         import main_selfplay
-        assert main_selfplay.__file__.startswith(%r)
         assert main_selfplay.NoModelSelfPlayWorker is selfplay_worker.NoModelSelfPlayWorker
         main_selfplay.main()
         print("PARENT", os.getpid())
-    """ % (str(tmp_path), REFERENCE, REFERENCE)))
+    """ % ([tuple(p) for p in imports], str(tmp_path))))
     assert "SELF-PLAYING BEST MODEL  model_1" in out
     assert "No new best model for self-playing. Stopping.." in out
     parent = int(out.split("PARENT")[1].split()[0])
@@ -492,3 +497,75 @@ def test_bench_stdout_is_one_json_line(tower):
     assert out["n_gpus"] == 1 and out["steps"] == 1 and out["value"] > 0
     # bench.py --tower-kernel 2 runs the step on k_conv4r (net.use_packed_tower) and says so in the roofline object
     assert ("k_conv4r" if tower == 2 else "k_conv4w") in out["roofline"]["kernel"] and 0 < out["roofline"]["frac"] < 1
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_outputs_writes_every_field(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one .npy per tuple field (z, NaN until the game ends, left out), integers as exact float64,
+    value / pi as float32; above the size limit a seeded sample of rows -- the same on every call -- with its row numbers."""
+    from sejonggo_amd.distributed import tuple_dtype
+    bench = _bench_module()
+    t = np.zeros(300, dtype=tuple_dtype(9))
+    t["game"] = np.arange(300)
+    t["action"] = np.arange(300) % 82
+    t["state"] = 0xFFFFFFFF
+    t["pi"] = 1.0 / 82
+    t["value"] = -0.25
+    t["z"] = np.nan
+    names = bench.dump_outputs(str(tmp_path / "all"), t)
+    assert set(names) == set(t.dtype.names) - {"z"}
+    for n in names:
+        a = np.load(str(tmp_path / "all" / (n + ".npy")))
+        assert a.dtype == (np.float32 if n in ("pi", "value") else np.float64) and len(a) == 300, n
+        assert np.array_equal(a, t[n]), n
+    row_bytes = sum(np.load(str(tmp_path / "all" / (n + ".npy")))[:1].nbytes for n in names) + 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100 * row_bytes)
+    kept = []
+    for d in ("s1", "s2"):
+        names = bench.dump_outputs(str(tmp_path / d), t)
+        assert "row" in names
+        arrs = {n: np.load(str(tmp_path / d / (n + ".npy"))) for n in names}
+        assert sum(a.nbytes for a in arrs.values()) <= bench.DUMP_LIMIT and len(arrs["row"]) == 100
+        assert np.array_equal(arrs["game"], arrs["row"]) and np.all(np.diff(arrs["row"]) > 0)
+        kept.append(arrs["row"])
+    assert np.array_equal(kept[0], kept[1])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs_and_full_adds_the_legs(tmp_path):
+    """A plain bench run times exactly --steps steps, carries none of the legs that take runs of their own, and with
+    --dump-outputs writes the last timed step's move tuples; --full adds steady_state, roofline_saturated and cpu_baseline
+    (config3_avg8 belongs to the headline configuration only)."""
+    import json
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "9", "--games", "64", "--sims", "64", "--blocks", "4",
+            "--warmup", "1"]
+    dump = tmp_path / "dump"
+    r = subprocess.run(base + ["--steps", "2", "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = r.stdout.decode().splitlines()
+    assert len(lines) == 1, lines[:5]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["engine"]["positions_in_window"] >= 2 * 64
+    for k in ("config3_avg8", "steady_state", "roofline_saturated", "cpu_baseline"):
+        assert k not in out, k
+    game, action, pi = (np.load(str(dump / (n + ".npy"))) for n in ("game", "action", "pi"))
+    value, state = np.load(str(dump / "value.npy")), np.load(str(dump / "state.npy"))
+    assert game.dtype == np.float64 and pi.dtype == np.float32 and value.dtype == np.float32
+    assert len(game) >= 64 and pi.shape == (len(game), 82) and state.shape[0] == len(game)
+    assert set(game.astype(int)) <= set(range(64)) and np.all((action >= 0) & (action <= 81))
+    assert np.all(state == np.floor(state)) and np.all(pi >= 0) and np.all(np.abs(value) <= 1)
+    r = subprocess.run(base + ["--steps", "1", "--full", "--cpu-seconds", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    out = json.loads(r.stdout.decode().splitlines()[0])
+    for k in ("steady_state", "roofline_saturated", "cpu_baseline"):
+        assert k in out and "error" not in out[k], (k, out.get(k))
+    assert "config3_avg8" not in out
