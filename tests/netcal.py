@@ -1,0 +1,255 @@
+"""Calibrated whole-net parity (test helper, not a fixture module).
+
+The whole-net checks compare the resident fp16 net with a reference forward of the same weights.  Under PyTorch's default
+init the policy of a 256-filter net is almost uniform (every probability within a factor of ~2 of 1/A) and the value sits
+near 0, so a bound on |dp| says little: a dropped residual branch or a wrong symmetry moves the probabilities by less than
+1e-3.  This module builds nets whose outputs are sharp enough for a wrong kernel to show, and measures errors where they
+are visible:
+
+* `build_calibrated_net`: the seeded PolicyValueNet of net.build_fused_net (same BN statistics), with the policy head rescaled
+  so that the centred logits have a standard deviation of ~2 on a fixed batch of played positions, and the last value layer
+  centred and rescaled so that the pre-tanh value has mean ~0 and standard deviation ~0.7 (scaling the weights alone
+  saturates the 19x19 value at +-1);
+* `Weights`: the weights exactly as net.FusedInferenceNet holds them (BN folded in fp32, then rounded to fp16), including
+  the packed stem's colour fold, which is summed from the UNROUNDED fp32 weights of plane 16;
+* `forward`: the net on the 17-plane NHWC tensor, in float64 (the reference), or in fp32 with every conv / linear output
+  rounded to fp16 (`emulate=True`: the kernels' rounding model, fp16 weights and inputs, fp32 accumulation), optionally
+  under one of the `MUTATIONS` -- the faults the parity check must be able to see;
+* `logit_error` / `value_error`: the metrics the tolerances below bound.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+# (board size, residual blocks) -> tolerance of the logit error and of the value error.  Derived from the fp16 rounding model
+# on CPU (tests/test_net_parity_power.py asserts both sides): the emulated forward's worst error against the float64
+# reference on played positions from the opening to a crowded board under all 8 symmetries (512 rows at 9x9, 128 at 19x19),
+# times ~2.5 and rounded, so that the model's noise is <= TOL / 2 with room for the larger number of rows the GPU test
+# takes the maximum over (the maximum grows with the rows: 8 -> 128 rows at 19x19 took the logit noise 4.9e-3 -> 6.8e-3).
+#   logit, 9x9 x 4 blocks:   noise 3.7e-3;  subtlest mutation (one tap x 16 channels of one conv) 8.5e-2   -> 1e-2
+#   logit, 19x19 x 20 blocks: noise 6.8e-3; subtlest mutation 7.1e-2 on the power test's 16 rows, and each
+#     of 18 variants of it (taps 0 / 4 / 8 x channel chunks 0 / 16 / 128 x conv1 / conv2) moved it by 3.7e-2..1.0e-1 -> 1.6e-2
+#   value, 9x9 x 4 blocks:   noise 3.3e-3                                                                   -> 1e-2
+#   value, 19x19 x 20 blocks: noise 8.7e-3 (the calibrated value is ~20x as sensitive as the default init's) -> 2e-2
+# The value metric is the weaker detector (the subtlest mutation moves it by 3.1e-2 at 19x19); the logit metric is the one
+# the power test holds to >= 2 * TOL for every mutation.
+LOGIT_TOL = {(9, 4): 1e-2, (19, 20): 1.6e-2}
+V_TOL = {(9, 4): 1e-2, (19, 20): 2e-2}
+
+P_FLOOR = 1e-6          # moves with a reference probability below this are left out of the logit metric
+LOGIT_STD = 2.0         # target per-row standard deviation of the centred policy logits
+VALUE_STD = 0.7         # target standard deviation of the pre-tanh value
+
+
+def playout_boards(S, plies, per_ply, seed):
+    """[len(plies) * per_ply, S, S, 17] int32 boards (the reference's planes: 16 history planes relative to the side to move,
+    plane 16 the colour) after `ply` seeded random legal moves each, played by the CPU oracle."""
+    from oracle import oracle as ora
+    rng = np.random.RandomState(seed)
+    out = []
+    for ply in plies:
+        for _ in range(per_ply):
+            b, _ = ora.game_init(S)
+            for _ in range(ply):
+                legal = np.flatnonzero(ora.legal_moves(b)[:S * S] == 0)
+                if len(legal) == 0:
+                    break
+                a = int(legal[rng.randint(len(legal))])
+                ora.make_play(a % S, a // S, b)
+            out.append(b[0].copy())
+    return np.stack(out)
+
+
+def build_calibrated_net(S, n_blocks, channels=256, seed=11, calib=None):
+    """The seeded fp32 PolicyValueNet of net.build_fused_net (eval mode, CPU) with its policy and value heads calibrated on
+    `calib` ([n, S, S, 17]; by default 32 played positions from the opening to a crowded board)."""
+    from sejonggo_amd.net import PolicyValueNet
+    torch.manual_seed(seed)
+    net = PolicyValueNet(S, n_blocks, channels, name="calibrated")
+    for mod in net.modules():
+        if isinstance(mod, nn.BatchNorm2d):
+            mod.running_mean.normal_(0, 0.1)
+            mod.running_var.uniform_(0.5, 1.5)
+    net.eval()
+    if calib is None:
+        calib = playout_boards(S, (0, S * S // 8, S * S // 3, S * S * 2 // 3), 8, seed=seed + 1)
+    x = torch.as_tensor(np.asarray(calib), dtype=torch.float32).permute(0, 3, 1, 2)
+    with torch.no_grad():
+        hp, hv = _head_inputs(net, x)
+        logits = net.p_fc(hp)
+        sd = (logits - logits.mean(dim=1, keepdim=True)).std(dim=1).mean()
+        net.p_fc.weight.mul_(LOGIT_STD / sd)
+        net.p_fc.bias.mul_(LOGIT_STD / sd)
+        z = F.relu(net.v_fc1(hv)) @ net.v_fc2.weight.t()          # [n, 1], the pre-tanh value without its bias
+        a = VALUE_STD / z.std()
+        net.v_fc2.weight.mul_(a)
+        net.v_fc2.bias.copy_(-a * z.mean().reshape(1))
+    return net
+
+
+def _head_inputs(net, x):
+    """The flattened (channels-last) inputs of p_fc and v_fc1 of the training-form module on NCHW float input."""
+    y = F.relu(net.stem_bn(net.stem(x)))
+    for b in net.blocks:
+        y = b(y)
+    p = F.relu(net.p_bn(net.p_conv(y))).permute(0, 2, 3, 1).reshape(x.shape[0], -1)
+    v = F.relu(net.v_bn(net.v_conv(y))).permute(0, 2, 3, 1).reshape(x.shape[0], -1)
+    return p, v
+
+
+def fused_net(net, device="cuda"):
+    """net.FusedInferenceNet of the calibrated module (needs the GPU)."""
+    from sejonggo_amd.net import FusedInferenceNet
+    return FusedInferenceNet(net, torch.float16, device)
+
+
+class Weights(object):
+    """The fp16 weights FusedInferenceNet reads (BN folded in fp32, rounded to fp16), held as float64 on `device`, plus the
+    packed stem's colour fold summed in fp32 from the unrounded plane-16 weights."""
+
+    def __init__(self, net, device="cpu"):
+        f = net.fused(torch.float32).float().cpu()
+
+        def r(t):
+            return t.detach().contiguous().half().to(device=device, dtype=torch.float64)
+
+        self.stem_w, self.stem_b = r(f.stem.weight), r(f.stem.bias)
+        self.stem_wcol = f.stem.weight.detach()[:, 16].reshape(-1, 9).sum(dim=1).to(device=device, dtype=torch.float64)
+        self.blocks = [[r(b.conv1.weight), r(b.conv1.bias), r(b.conv2.weight), r(b.conv2.bias)] for b in f.blocks]
+        self.head_w = r(torch.cat([f.p_conv.weight.reshape(2, -1), f.v_conv.weight.reshape(2, -1)], 0))
+        self.head_b = r(torch.cat([f.p_conv.bias, f.v_conv.bias], 0))
+        self.p_fc_w, self.p_fc_b = r(f.p_fc.weight), r(f.p_fc.bias)
+        self.v_fc1_w, self.v_fc1_b = r(f.v_fc1.weight), r(f.v_fc1.bias)
+        self.v_fc2_w, self.v_fc2_b = r(f.v_fc2.weight), r(f.v_fc2.bias)
+
+    def copy(self):
+        import copy
+        w = copy.copy(self)
+        w.blocks = [list(b) for b in self.blocks]
+        return w
+
+
+def roll_taps(w):
+    """A 3x3 filter bank [K, C, 3, 3] with its 9 taps rotated by one (tap t reads tap t-1's weights)."""
+    k, c = w.shape[:2]
+    return torch.roll(w.reshape(k, c, 9), 1, dims=2).reshape(w.shape).contiguous()
+
+
+# The faults the whole-net check must see.  Each is the kind of wrong a kernel or its host wrapper could produce without
+# faulting: a K-chunk / tap / channel group lost, a filter bank read in the wrong order, an epilogue term lost or misplaced,
+# the stem's planes or the symmetry misread, the head's flatten order wrong.
+MUTATIONS = ("tap_x16ch_zeroed_mid_conv", "8_out_ch_zeroed_last_conv", "taps_rolled_one_conv", "bias_dropped_one_conv",
+             "skip_after_relu", "stem_history_reversed", "colour_flipped", "wrong_symmetry", "head_flatten_channels_first")
+
+
+def _mutate(W, x, mutation):
+    """(weights, NHWC input, flags) for `mutation`; the weights are copied where changed."""
+    flags = set()
+    if mutation is None:
+        return W, x, flags
+    W = W.copy()
+    mid = len(W.blocks) // 2
+    if mutation == "tap_x16ch_zeroed_mid_conv":
+        w = W.blocks[mid][0].clone()
+        w[:, 16:32, 1, 1] = 0                  # one tap (the centre) of one 16-channel K-chunk
+        W.blocks[mid][0] = w
+    elif mutation == "8_out_ch_zeroed_last_conv":
+        w, b = W.blocks[-1][2].clone(), W.blocks[-1][3].clone()
+        w[:8], b[:8] = 0, 0                    # the conv's output channels 0..7 are zero: relu(skip) only
+        W.blocks[-1][2], W.blocks[-1][3] = w, b
+    elif mutation == "taps_rolled_one_conv":
+        W.blocks[mid][0] = roll_taps(W.blocks[mid][0])
+    elif mutation == "bias_dropped_one_conv":
+        W.blocks[mid][3] = torch.zeros_like(W.blocks[mid][3])
+    elif mutation == "skip_after_relu":
+        flags.add(mutation)
+    elif mutation == "stem_history_reversed":
+        x = torch.cat([x[..., :16].flip(-1), x[..., 16:]], dim=-1)
+    elif mutation == "colour_flipped":
+        x = torch.cat([x[..., :16], -x[..., 16:]], dim=-1)
+    elif mutation == "wrong_symmetry":
+        x = x.transpose(1, 2)                  # the left-diagonal reflection in place of the identity
+    elif mutation == "head_flatten_channels_first":
+        flags.add(mutation)
+    else:
+        raise ValueError(mutation)
+    return W, x, flags
+
+
+@torch.no_grad()
+def forward(W, X, route="packed", emulate=False, mutation=None):
+    """(log policy [n, A], value [n, 1]) of the net on NHWC input X [n, S, S, 17] (planes as nn_pack writes them).
+
+    emulate=False: float64 throughout (the reference).  emulate=True: fp32 arithmetic with every conv / linear output rounded
+    to fp16 after its bias (+ skip) and ReLU, as the kernels and the fp16 GEMMs of the heads write them.
+    route="packed": the stem of sgo_stem_packed_dev (history planes with fp16 weights, colour plane through the fp32 fold);
+    route="tensor": the stem of the channel-padded tensor route (k_stem: all 17 planes with fp16 weights)."""
+    dt = torch.float32 if emulate else torch.float64
+    W, X, flags = _mutate(W, torch.as_tensor(X).to(device=W.stem_w.device, dtype=torch.float64), mutation)
+
+    def rnd(t):
+        return t.half().to(dt) if emulate else t
+
+    def c(t):
+        return t.to(dt)
+
+    x = X.permute(0, 3, 1, 2).to(dt)
+    n = x.shape[0]
+    if route == "packed":
+        y = F.conv2d(x[:, :16], c(W.stem_w[:, :16]), c(W.stem_b))
+        y = y + x[:, 16:17, 1:-1, 1:-1] * c(W.stem_wcol).reshape(1, -1, 1, 1)
+    else:
+        assert route == "tensor", route
+        y = F.conv2d(x, c(W.stem_w), c(W.stem_b))
+    y = rnd(F.relu(y))
+    for (w1, b1, w2, b2) in W.blocks:
+        z = rnd(F.relu(F.conv2d(y, c(w1), c(b1), padding=1)))
+        if "skip_after_relu" in flags:
+            y = rnd(F.relu(F.conv2d(z, c(w2), c(b2), padding=1)) + y)
+        else:
+            y = rnd(F.relu(F.conv2d(z, c(w2), c(b2), padding=1) + y))
+    t = y.shape[-1]
+    h = rnd(F.relu(torch.einsum("nchw,kc->nkhw", y, c(W.head_w)) + c(W.head_b).reshape(1, 4, 1, 1)))
+    if "head_flatten_channels_first" in flags:
+        p, v = h[:, 0:2].reshape(n, 2 * t * t), h[:, 2:4].reshape(n, 2 * t * t)
+    else:
+        p = h[:, 0:2].permute(0, 2, 3, 1).reshape(n, 2 * t * t)          # Keras Flatten of [t, t, 2]
+        v = h[:, 2:4].permute(0, 2, 3, 1).reshape(n, 2 * t * t)
+    logits = rnd(F.linear(p, c(W.p_fc_w), c(W.p_fc_b)))
+    v = rnd(F.relu(F.linear(v, c(W.v_fc1_w), c(W.v_fc1_b))))
+    v = torch.tanh(rnd(F.linear(v, c(W.v_fc2_w), c(W.v_fc2_b))))
+    return torch.log_softmax(logits.double(), dim=1), v.double()
+
+
+def logit_error(logp, logp_ref):
+    """max over rows and moves of |(log p - log p_ref) - rowmean(.)|, over the moves with p_ref > P_FLOOR."""
+    logp, logp_ref = torch.as_tensor(logp).double(), torch.as_tensor(logp_ref).double().to(torch.as_tensor(logp).device)
+    if bool(torch.isnan(logp).any()):
+        return float("inf")
+    m = logp_ref.exp() > P_FLOOR
+    d = torch.where(m, logp - logp_ref, torch.zeros_like(logp))      # a move left out may even have p == 0 (log p = -inf)
+    d = d - (d.sum(dim=1, keepdim=True) / m.sum(dim=1, keepdim=True))
+    return _worst(torch.where(m, d, torch.zeros_like(d)))
+
+
+def value_error(v, v_ref):
+    v, v_ref = torch.as_tensor(v).double(), torch.as_tensor(v_ref).double()
+    return _worst(v - v_ref.to(v.device))
+
+
+def _worst(d):
+    """max |d|, and inf if any entry is NaN or infinite (torch's max would pass a NaN on, and a NaN compares false with every
+    bound, so a caller folding errors with max() would lose it)."""
+    if not bool(torch.isfinite(d).all()):
+        return float("inf")
+    return float(d.abs().max())
+
+
+def regime(logp, v):
+    """Statistics that say whether a calibrated net is in the intended regime: (max probability per row: min / max over
+    rows, mean per-row std of the centred logits, max |v|)."""
+    logp = torch.as_tensor(logp).double()
+    pmax = logp.exp().max(dim=1).values
+    sd = (logp - logp.mean(dim=1, keepdim=True)).std(dim=1).mean()
+    return float(pmax.min()), float(pmax.max()), float(sd), float(torch.as_tensor(v).abs().max())

@@ -98,6 +98,23 @@ def test_packed_route_equals_the_tensor_route_of_the_same_net(L):
         p0, v0 = fnet.predict_on_batch(x)
         p1, v1 = fnet.predict_packed(recs.data_ptr(), None, 96, k)
         assert float((p1 - p0).abs().max()) <= 5e-4 and float((v1 - v0).abs().max()) <= 2e-3
+    # the same on the calibrated 20-block net (tests/netcal.py), where a policy bound of 5e-4 says little: each route within
+    # the logit / value tolerance of the float64 forward of its own stem's weights, and the two routes within it of each other
+    from tests import netcal
+    net = netcal.build_calibrated_net(S, 20)
+    fnet = netcal.fused_net(net)
+    W = netcal.Weights(net, device="cuda")
+    tol_l, tol_v = netcal.LOGIT_TOL[(S, 20)], netcal.V_TOL[(S, 20)]
+    for k in (0, 3, 6):
+        x = torch.zeros((96, S, S, 17), dtype=torch.float32, device="cuda")
+        L.check(lib.sgo_nn_pack_dev(S, 96, L.ptr(recs), None, k, 0, 1, L.ptr(x), L.stream_ptr()))
+        p0, v0 = fnet.predict_on_batch(x.half())
+        p1, v1 = fnet.predict_packed(recs.data_ptr(), None, 96, k)
+        l0, l1 = torch.log(p0.double()), torch.log(p1.double())
+        for route, lp, v in (("tensor", l0, v0), ("packed", l1, v1)):
+            lr, vr = netcal.forward(W, x.double(), route=route)
+            assert netcal.logit_error(lp, lr) <= tol_l and netcal.value_error(v, vr) <= tol_v, (route, k)
+        assert netcal.logit_error(l1, l0) <= tol_l and netcal.value_error(v1, v0) <= tol_v, k
 
 
 def test_tower_conv_at_the_headline_launch(L):

@@ -709,6 +709,21 @@ def test_fused_inference_net_matches_fp32_reference(L):
         p2, v2 = fnet.predict_on_batch(Xp)
         # same input, padded by the caller: equal up to the library's choice of conv algorithm per call
         assert float((p1 - p2).abs().max()) <= 1e-3 and float((v1 - v2).abs().max()) <= 2e-3
+    # the same routes on calibrated nets (tests/netcal.py: sharp policy, unsaturated value), where the bounds above say
+    # little: logits and value against the float64 forward of the same fp16 weights, 256 channels (k_stem + tower kernels)
+    # and 64 (the framework's convolution + k_bias_act), under the 9x9 x 4-block tolerances
+    from tests import netcal
+    for ch in (256, 64):
+        net = netcal.build_calibrated_net(9, 4, channels=ch)
+        fnet = netcal.fused_net(net)
+        X = torch.zeros((16, 9, 9, 17), device="cuda")
+        X[..., :16] = (torch.rand((16, 9, 9, 16), device="cuda") < 0.2).float()
+        X[..., 16] = 1.0
+        X[8:, :, :, 16] = -1.0
+        lr, vr = netcal.forward(netcal.Weights(net, device="cuda"), X.double(), route="tensor")
+        p1, v1 = fnet.predict_on_batch(X.half())
+        dl, dv = netcal.logit_error(torch.log(p1.double()), lr), netcal.value_error(v1, vr)
+        assert dl <= netcal.LOGIT_TOL[(9, 4)] and dv <= netcal.V_TOL[(9, 4)], (ch, dl, dv)
 
 
 def test_nn_pack_channel_padded_layout(L):
@@ -985,6 +1000,49 @@ def test_worker_survives_a_slot_that_outgrows_its_block_pool(L, tmp_path, monkey
         pq.destroy_predicting_workers([0])
         conf.clear()
         conf.update(keep)
+
+
+@pytest.mark.parametrize("C", [8, 64, 256])
+def test_bias_act_kernel(L, C):
+    """sgo_bias_act_dev (k_bias_act: out = relu(x + bias[c] (+ skip)), the epilogue of every conv on the small-channel route)
+    bit for bit against torch fp16 relu((x + b) + skip): both round after each add (the kernel's half8 adds are correctly
+    rounded fp16 adds, torch adds in fp32 and rounds once, which for two fp16 operands is the same), in place (x == out, as
+    net.FusedInferenceNet calls it) and out of place, with and without skip, up to a launch whose grid-stride loop wraps;
+    exact on small-integer data; sizes that are not multiples of 8 halves are refused, nothing written."""
+    import torch
+    lib = L.load()
+    st = L.stream_ptr()
+    g = torch.Generator(device="cuda").manual_seed(C)
+    for rows in (1, 37, (1 << 24) // C + 37):          # the last: more half8 groups than the kernel's capped grid has lanes
+        x = (torch.randn(rows, C, device="cuda", generator=g) * 4).half()
+        b = (torch.randn(C, device="cuda", generator=g) * 2).half()
+        skip = (torch.randn(rows, C, device="cuda", generator=g) * 4).half()
+        for sk in (None, skip):
+            ref = torch.relu(x + b if sk is None else (x + b) + sk)
+            out = torch.full_like(x, 7.0)
+            L.check(lib.sgo_bias_act_dev(x.numel(), C, x.data_ptr(), b.data_ptr(), None if sk is None else sk.data_ptr(),
+                                         out.data_ptr(), st))
+            assert torch.equal(out, ref), (rows, sk is None, int((out != ref).sum()))
+            y = x.clone()
+            L.check(lib.sgo_bias_act_dev(y.numel(), C, y.data_ptr(), b.data_ptr(), None if sk is None else sk.data_ptr(),
+                                         y.data_ptr(), st))
+            assert torch.equal(y, ref), (rows, sk is None, "in place")
+    # small integers: every sum exact, so the result is the exact relu(x + b + skip)
+    x = torch.randint(-40, 41, (333, C), device="cuda", generator=g).half()
+    b = torch.randint(-20, 21, (C,), device="cuda", generator=g).half()
+    skip = torch.randint(-40, 41, (333, C), device="cuda", generator=g).half()
+    y = x.clone()
+    L.check(lib.sgo_bias_act_dev(y.numel(), C, y.data_ptr(), b.data_ptr(), skip.data_ptr(), y.data_ptr(), st))
+    ref = torch.relu(x.float() + b.float() + skip.float())
+    assert torch.equal(y.float(), ref) and bool((ref > 0).any()) and bool((ref == 0).any())
+    # refused: element count or channel count not a multiple of 8 halves (the kernel works in 16-byte groups)
+    out = torch.full_like(x, 7.0)
+    assert lib.sgo_bias_act_dev(x.numel() - 4, C, x.data_ptr(), b.data_ptr(), None, out.data_ptr(), st) < 0
+    assert b"multiples of 8" in lib.sgo_last_error()
+    assert lib.sgo_bias_act_dev(x.numel(), C - 4, x.data_ptr(), b.data_ptr(), None, out.data_ptr(), st) < 0
+    assert lib.sgo_bias_act_dev(x.numel(), C, x.data_ptr(), None, None, out.data_ptr(), st) < 0
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
 
 
 def test_fused_conv_kernel_matches_torch(L):
