@@ -290,6 +290,14 @@ int sgo_set_halt(sgo_ctx *ctx, int slot, int move_n);
 /* Diagnostic: cycles per phase of k_search, summed over games and calls (zeros unless the library was built with
  * -DSGO_KSEARCH_PROFILE): [0] consuming evaluations, [2] selection, [7] round back-propagation, [3] move step, [4] wave-calls. */
 int sgo_debug_counters(sgo_ctx *ctx, unsigned long long *out, int n);
+/* Test hook: the PUCT selector of the search (play.py:308-323 top_one_with_virtual_loss) on caller-supplied child tables.
+ * DEVICE pointers to flat [n_cases][A] arrays: priors as float32 and, when f64 != 0, as the float64 root priors (P64 may be
+ * NULL otherwise); counts; means; busy (> 0 = virtual loss set); legal (!= 0 = the child exists).  out[n_cases] receives the
+ * chosen slot or -1.  Each case is written into the root block of a game slot and handed to the very function the descent
+ * calls; cases run in chunks of n_games, all queued on `stream`.  Refuses (SGO_ERR_STATE) a context with games in flight;
+ * the root blocks of all slots are overwritten. */
+int sgo_debug_top_one(sgo_ctx *ctx, int n_cases, const float *P32, const double *P64, const int32_t *N, const float *Q,
+                      const int8_t *busy, const uint8_t *legal, int f64, int32_t *out, void *stream);
 
 /* average duration (ms) and launch count of the board_advance kernel inside sgo_step since the last
  * call (HIP events on the step's stream); used by bench.py for the roofline object */

@@ -988,6 +988,46 @@ __global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int h
     }
 }
 
+// ---------------------------------------------------------------------------------------- test hook: the selector alone
+// sgo_debug_top_one: one wave per case writes a flat child table into the root block of game slot blockIdx.x -- every array
+// top_one() reads: counts, busy flags, priors (float32 and the slot's float64 root priors), means, child pointers (-1), the
+// legal words -- and then runs Eng<S>::top_one itself on it, the function every descent step of k_search calls.
+template <int S>
+__global__ void __launch_bounds__(64) k_debug_top_one(Ctx c, int n, const float *P32, const double *P64, const int32_t *N,
+                                                      const float *Q, const int8_t *busy, const uint8_t *legal, int f64,
+                                                      int32_t *out) {
+    using G = Geo<S>;
+    const int g = blockIdx.x, lane = threadIdx.x & 63;
+    if (g >= n || g >= c.G) return;
+    Eng<S> e(c, g);
+    int blk = c.gs[g].root_blk;
+    if (blk < 0 || blk >= c.cap) blk = 0;
+    const size_t pb = e.ph(blk), sb = pb * (size_t)G::APAD, t = (size_t)g * G::A;
+    for (int i = lane; i < G::APAD; i += 64) {                 // slot i by lane i & 63, as everywhere in the engine
+        const bool in = i < G::A;
+        c.cP[sb + i] = in ? P32[t + i] : 0.f;
+        c.cN[sb + i] = in ? N[t + i] : 0;
+        c.cW[sb + i] = 0.f;
+        c.cQ[sb + i] = in ? Q[t + i] : 0.f;
+        c.cB[sb + i] = -1;
+        c.cBusy[sb + i] = (in && busy[t + i] > 0) ? 2 : 0;
+        c.rootP64[(size_t)g * G::APAD + i] = (in && f64) ? P64[t + i] : 0.0;
+    }
+    for (int w = lane; w < G::NW; w += 64) {
+        uint32_t m = 0;
+        for (int b = 0; b < 32; b++) {
+            const int i = 32 * w + b;
+            if (i < G::A && legal[t + i]) m |= 1u << b;
+        }
+        c.legal[pb * G::NW + w] = m;
+    }
+    __threadfence();                                           // the legal words are read by other lanes than their writers
+    __syncthreads();
+    int child = -1;
+    const int a = e.top_one(blk, f64 != 0, child);
+    if (lane == 0) out[g] = a;
+}
+
 template <int S>
 static size_t search_lds(const Ctx &c) {
     return sizeof(int32_t) * ((size_t)c.L + 2 * Geo<S>::APAD + (c.L + 31) / 32 + 4);
@@ -1552,6 +1592,36 @@ int sgo_debug_counters(sgo_ctx *x, unsigned long long *out, int n) {
     Counters h;
     SGO_HIP(hipMemcpy(&h, x->c.counters, sizeof h, hipMemcpyDeviceToHost));
     for (int i = 0; i < n && i < 8; i++) out[i] = h.dbg[i];
+    return SGO_OK;
+}
+
+/* Test hook (tests/test_gpu_selector.py): Eng<S>::top_one on caller-supplied child tables.  Flat [n_cases][A] DEVICE arrays;
+ * the cases run in chunks of the context's game count, case k of a chunk in the root block of slot k, whose contents it
+ * replaces -- so the context must have no game in flight, and trees of finished games are gone afterwards. */
+int sgo_debug_top_one(sgo_ctx *x, int n_cases, const float *P32, const double *P64, const int32_t *N, const float *Q,
+                      const int8_t *busy, const uint8_t *legal, int f64, int32_t *out, void *stream) {
+    if (!x || n_cases < 0 || !P32 || !N || !Q || !busy || !legal || !out || (f64 && !P64)) {
+        set_error("sgo_debug_top_one: bad argument");
+        return SGO_ERR_ARG;
+    }
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    SGO_HIP(hipDeviceSynchronize());
+    std::vector<GameState> all(c.G);
+    SGO_HIP(hipMemcpy(all.data(), c.gs, sizeof(GameState) * c.G, hipMemcpyDeviceToHost));
+    for (int g = 0; g < c.G; g++)
+        if (all[g].phase == PH_WAIT_ROOT || all[g].phase == PH_SEARCH) {
+            set_error("sgo_debug_top_one: the context has games in flight (the hook overwrites the root block of every slot)");
+            return SGO_ERR_STATE;
+        }
+    for (int c0 = 0; c0 < n_cases; c0 += c.G) {
+        const int n = std::min(c.G, n_cases - c0);
+        const size_t o = (size_t)c0 * c.A;
+        SGO_DISPATCH(c.S, k_debug_top_one<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, P32 + o, f64 ? P64 + o : nullptr, N + o, Q + o,
+                                                                            busy + o, legal + o, f64, out + c0));
+        SGO_HIP(hipGetLastError());
+    }
     return SGO_OK;
 }
 

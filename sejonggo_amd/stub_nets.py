@@ -11,6 +11,9 @@ GPU engine, the CPU oracle and the Python reference can be fed *bit-identical* p
 * ``HashNet``      p, v are dyadic rationals computed from an integer hash of the 17 planes, so
                    no floating-point rounding happens anywhere and numpy / torch-CPU /
                    torch-ROCm agree to the bit.
+* ``TableNet``     row ``hash(position) mod K`` of a fixed table of what a trained head emits: full 24-bit
+                   mantissas at several sharpnesses, exact zeros, float32 denormals, v = +-1.0 / +-0.0.
+                   Integer hash plus one gather, so the three back-ends still agree to the bit.
 
 Each class works on numpy arrays and on torch tensors (any device); the arithmetic is integer
 until the final exact scaling.
@@ -119,7 +122,83 @@ class HashNet(_Base):
         return p, v.reshape(-1, 1)
 
 
+def _table(size, K):
+    """(T float32[K, A], V float32[K]) of TableNet.  Every value is assembled from a float32 BIT PATTERN (sign, exponent field,
+    23 random mantissa bits drawn with RandomState.randint): no libm call and no floating-point reduction takes part, so every
+    host builds the same bytes (tests/test_host_logic.py pins their SHA-256)."""
+    A = size * size + 1
+    rng = np.random.RandomState(977 + size)
+    e0 = 127 - int(A).bit_length()                     # exponent field of [2^-ceil(log2 A), 2 * that): a flat row sums to about 1
+    hot = (size * size) // 2                           # the centre point: it is taken within the first plies of most games
+
+    def f32(expo, mant, sign=0):
+        bits = (np.asarray(sign, np.int64) << 31) | (np.asarray(expo, np.int64) << 23) | np.asarray(mant, np.int64)
+        return bits.astype(np.uint32).view(np.float32)
+
+    T = np.zeros((K, A), dtype=np.float32)
+    for k in range(K):
+        mant = rng.randint(0, 1 << 23, size=A)
+        kind = k % 8
+        peak = int(rng.randint(0, A))
+        if kind == 0:                                  # flat: one binade
+            row = f32(np.full(A, e0), mant)
+        elif kind == 1:                                # mild: four binades
+            row = f32(e0 + rng.randint(-3, 1, size=A), mant)
+        elif kind == 2:                                # sharp: twenty binades and a few large entries
+            row = f32(e0 + rng.randint(-20, 1, size=A), mant)
+            big = rng.randint(0, A, size=3)
+            row[big] = f32(rng.randint(122, 126, size=3), rng.randint(0, 1 << 23, size=3))
+        elif kind in (3, 4, 5):
+            # near one-hot (softmax of logit gaps up to and beyond 87): the rest is a mix of exact zeros, denormals (exponent
+            # field 0) and tiny normals; kind 4 puts the peak on the centre point, kind 5 on the pass
+            cls = rng.randint(0, 3, size=A)
+            expo = np.where(cls == 2, rng.randint(1, 60, size=A), 0)
+            row = f32(expo, np.where(cls == 0, 0, mant))
+            peak = {3: peak, 4: hot, 5: A - 1}[kind]
+            row[peak] = f32(126, (1 << 23) - 1 - int(rng.randint(0, 256)))
+        elif kind == 6:                                # two close rivals, full mantissas, over a flat floor
+            row = f32(np.full(A, e0 - 4), mant)
+            a, b = rng.choice(A, size=2, replace=False)
+            m = int(rng.randint(0, (1 << 23) - 1))
+            row[a], row[b] = f32(125, m), f32(125, m + 1)
+        else:                                          # every entry the same value
+            row = np.full(A, np.float32(1.0) / np.float32(A), dtype=np.float32)
+        T[k] = row
+    V = f32(rng.randint(117, 127, size=K), rng.randint(0, 1 << 23, size=K), rng.randint(0, 2, size=K))
+    V[:4] = np.array([1.0, -1.0, 0.0, -0.0], dtype=np.float32)
+    V[4:8] = f32([126, 126, 1, 0], [(1 << 23) - 1, (1 << 23) - 1, 0, 1], [0, 1, 0, 1])   # +-(1 - 2^-24), smallest normal, a denormal
+    return T, V
+
+
+class TableNet(_Base):
+    """Board-dependent net with the value domain of a trained policy / value head: row ``hash mod K`` of _table()."""
+    K = 128
+
+    def __init__(self, size, name="table_stub"):
+        _Base.__init__(self, size, name)
+        self._w = _hash_weights(size)
+        self._T, self._V = _table(size, self.K)
+        self._wt = {}
+
+    def predict_on_batch(self, X):
+        if isinstance(X, np.ndarray):
+            x = X.astype(np.int64).reshape(X.shape[0], -1)
+            h = np.mod(np.mod(x @ self._w.reshape(-1), _HASH_MOD), self.K)
+            return self._T[h], self._V[h].reshape(-1, 1)
+        import torch
+        dev = X.device
+        if dev not in self._wt:
+            self._wt[dev] = (torch.from_numpy(self._w.reshape(-1)).to(dev), torch.from_numpy(self._T).to(dev),
+                             torch.from_numpy(self._V).to(dev))
+        w, T, V = self._wt[dev]
+        x = X.to(torch.int64).reshape(X.shape[0], -1)
+        h = torch.remainder(torch.remainder((x * w.unsqueeze(0)).sum(dim=1), _HASH_MOD), self.K)
+        return T.index_select(0, h), V.index_select(0, h).reshape(-1, 1)
+
+
 def make_stub(kind, size):
+    if kind == "table":
+        return TableNet(size)
     if kind == "hash2":
         return HashNet(size, name="hash_stub_2", variant=1)
     return {"uniform": UniformNet, "dummy": DummyNet, "hash": HashNet}[kind](size)

@@ -286,6 +286,227 @@ def child_puct(out):
     np.savez_compressed(out, P=P, N=N, Q=Q, V=V, EX=EX, F64=F64, out_vl=out_vl, out_one=out_one, out_top=out_top)
 
 
+# ---- near-tie tables for the PUCT selectors (puct_ties.npz) ---------------------------------------------------------------
+# The reference's score under numpy >= 2 is fl32(q + fl32(fl32(p * fl32(tn)) / fl32(1 + n))) on float32 priors and
+# q + (p * tn) / (1 + n) in float64 at a root whose priors were mixed with Dirichlet noise.  Each entry below is a selector
+# that is algebraically the same and differs in rounding: what a reciprocal, a hoisted tn / (1 + n) or a widened product
+# would compute.  tests/test_selector_power.py restates them; a case is worth keeping when one of them picks another child.
+def _ref_scores(P, N, Q, tn, f64):
+    import numpy as np
+    if f64:
+        return Q.astype(np.float64) + P * tn / (1. + N)
+    return Q + (P.astype(np.float32) * np.float32(tn)) / (1. + N).astype(np.float32)
+
+
+def _wrong_scores(P, N, Q, tn, f64):
+    """{name: scores} of the listed wrong formulas for one regime (P float64 [A], N int32, Q float32)."""
+    import numpy as np
+    n1 = 1. + N
+    if f64:
+        q = Q.astype(np.float64)
+        return {"f64_hoisted_ratio": q + P * (tn / n1),
+                "f64_prior_over_count_first": q + (P / n1) * tn,
+                "f64_scored_in_f32": _ref_scores(P.astype(np.float32).astype(np.float64), N, Q, tn, False)}
+    p, n1f, tnf = P.astype(np.float32), n1.astype(np.float32), np.float32(tn)
+    return {"f32_hoisted_ratio": Q + p * (tnf / n1f),
+            "f32_prior_over_count_first": Q + (p / n1f) * tnf,
+            "f32_in_f64_rounded_once": (Q.astype(np.float64) + p.astype(np.float64) * tn / n1).astype(np.float32),
+            "f32_product_with_f64_tn": Q + (p.astype(np.float64) * tn).astype(np.float32) / n1f}
+
+
+def _select(scores, free):
+    """First index of the largest score among the free children (the strict `>` of play.py:320), -1 when none is free."""
+    import numpy as np
+    idx = np.flatnonzero(free)
+    return int(idx[np.argmax(scores[idx])]) if len(idx) else -1
+
+
+TIE_CLASSES = ["same_lane", "neighbour_lanes", "slot0", "last_point", "pass", "random",          # placement of the tied pair
+               "winner_busy", "all_busy", "only_pass_free", "only_pass_busy", "counts_all_zero", "special_values"]
+
+
+def child_puct_ties(out):
+    """Child tables on which two children score equal or one ulp apart, so that the argmax depends on the last bit of the
+    score: for the device geometries A = 26 / 82 / 362, both float regimes, the tied pair placed in one lane of the selecting
+    wave, in neighbouring lanes, at slot 0, at the last board point and at the pass.  Expected outputs are the reference's."""
+    import math
+    import numpy as np
+    _setup_reference(9, 8, 8)
+    import play
+    f32 = np.float32
+    NEED, TIES_PER_PLACE = 24, 2
+    data = {"sizes": np.array([26, 82, 362], dtype=np.int32),
+            "cls_names": np.frombuffer("\n".join(TIE_CLASSES).encode(), dtype=np.uint8)}
+
+    def reference(P, N, Q, V, EX, f64):
+        sub = {}
+        for a in np.flatnonzero(EX):
+            a = int(a)
+            sub[a] = {"index": a, "count": int(N[a]), "value": 0, "mean_value": f32(Q[a]) if N[a] else 0,
+                      "p": np.float64(P[a]) if f64 else f32(P[a]), "subtree": {}, "parent": None, "virtual_loss": int(V[a])}
+        r = play.top_one_with_virtual_loss({"subtree": sub})
+        top = np.full(8, -1, dtype=np.int32)
+        for k, d in enumerate(play.top_n_actions(sub, 8)):
+            top[k] = d["action"]
+        return (r["action"] if r else -1), play.top_one_action(sub)["action"], top
+
+    def place(kind, A, rng):
+        if kind == "same_lane" and A > 64:
+            i = int(rng.randint(0, A - 64))
+            return i, i + 64 * int(rng.randint(1, (A - 1 - i) // 64 + 1))
+        if kind == "neighbour_lanes":
+            i = int(rng.randint(0, A - 1))
+            return i, i + 1
+        if kind == "slot0":
+            return 0, int(rng.randint(1, A))
+        if kind == "last_point":
+            return (A - 2, A - 1) if rng.rand() < 0.3 else (int(rng.randint(0, A - 2)), A - 2)
+        if kind == "pass":
+            return int(rng.randint(0, A - 1)), A - 1
+        i, j = sorted(rng.choice(A, size=2, replace=False))
+        return int(i), int(j)
+
+    def fillers(A, rng, big):
+        """Every child but the pair: values from a small set (the file stays small), scores far below the pair's."""
+        a = np.arange(A)
+        EX = [np.ones(A, bool), a % 3 == 0, np.zeros(A, bool)][int(rng.randint(0, 3))]
+        N = np.where(EX, [2, 2, 2500][int(rng.randint(0, 3))] if big else 2, 0).astype(np.int32)
+        Q = np.where(EX, f32(-0.75), f32(0)).astype(np.float32)
+        P = np.where(EX, 2.0 ** -12, 0.0)
+        V = np.where(EX & (a % 5 == 0) & (rng.rand() < 0.5), 2, 0).astype(np.int8)
+        return P, N, Q, V, EX.astype(np.int8)
+
+    def special(rng, what, f64):
+        """(p, q) of child i for the special_values class: p = 0, a denormal p, q = +-1, q = -0.0."""
+        p = rng.uniform(0.001, 0.5) if f64 else float(f32(rng.uniform(0.001, 0.5)))
+        if what == 0:
+            return 0.0, f32(rng.uniform(-0.5, 0.9))
+        if what == 1:
+            return float(np.array(rng.randint(1, 1 << 23), dtype=np.uint32).view(np.float32)), f32(rng.uniform(-0.5, 0.9))
+        if what == 2:
+            return 0.0, f32(1.0)
+        if what == 3:
+            return p, f32(-1.0)
+        return p, f32(-0.0)
+
+    for A in (26, 82, 362):
+        rows = []
+        for f64 in (0, 1):
+            rng = np.random.RandomState(9000 + 10 * A + f64)
+            names = sorted(_wrong_scores(np.ones(2), np.ones(2, np.int32), np.ones(2, np.float32), 1.0, f64))
+            kills = dict.fromkeys(names, 0)
+            ties = dict.fromkeys(TIE_CLASSES[:6], 0)
+            specials = dict.fromkeys(range(5), 0)
+            kept, tries = [], 0
+            while min(kills.values()) < NEED or min(ties[k] for k in ties if A > 64 or k != 'same_lane') < TIES_PER_PLACE or min(specials.values()) < 2:
+                tries += 1
+                kind = TIE_CLASSES[tries % 6]
+                i, j = place(kind, A, rng)
+                big = rng.rand() < 0.4
+                P, N, Q, V, EX = fillers(A, rng, big)
+                spec = int(rng.randint(0, 5)) if rng.rand() < 0.15 else -1
+                for a in (i, j):
+                    N[a] = rng.randint(2000, 9000) if big else rng.randint(1, 60)
+                    V[a], EX[a] = 0, 1
+                if spec >= 0:
+                    P[i], Q[i] = special(rng, spec, f64)
+                else:
+                    P[i] = rng.uniform(0.001, 0.5) if f64 else f32(rng.uniform(0.001, 0.5))
+                    Q[i] = f32(rng.uniform(-0.5, 0.9))
+                tn = math.sqrt(int(N.sum()))
+                si = _ref_scores(P, N, Q, tn, f64)[i]
+                if f64:
+                    Q[j] = f32(rng.uniform(-0.6, float(si) - 0.01))
+                    pj = (si - np.float64(Q[j])) * (1. + N[j]) / tn
+                    for _ in range(int(rng.randint(0, 3))):
+                        pj = np.nextafter(pj, 1.0 if rng.rand() < 0.5 else 0.0)
+                    P[j] = pj
+                else:
+                    P[j] = f32(rng.uniform(0.001, 0.5))
+                    uj = (f32(P[j]) * f32(tn)) / f32(1. + N[j])
+                    qj = f32(si - uj)
+                    k = int(rng.randint(-1, 2))
+                    Q[j] = qj if k == 0 else np.nextafter(qj, f32(k * 4))
+                if not (abs(float(Q[j])) <= 1 and 0 < P[j] <= 1):
+                    continue
+                free = (EX > 0) & (V == 0)
+                ref = _ref_scores(P, N, Q, tn, f64)
+                rest = free.copy()
+                rest[[i, j]] = False
+                if rest.any() and ref[rest].max() > min(ref[i], ref[j]) - 0.01:
+                    continue                                             # a filler is not far below the pair
+                want = _select(ref, free)
+                assert want in (i, j)
+                hit = [n for n, sc in _wrong_scores(P, N, Q, tn, f64).items() if _select(sc, free) != want]
+                tie = ref[i] == ref[j]
+                keep = any(kills[n] < NEED for n in hit)
+                if not keep and spec >= 0 and specials[spec] < 2:
+                    keep = True
+                if not keep and tie and not hit and spec < 0 and ties[kind] < TIES_PER_PLACE:
+                    keep = True
+                    ties[kind] += 1
+                if not keep:
+                    continue
+                if spec >= 0:
+                    specials[spec] += 1
+                for n in hit:
+                    kills[n] += 1
+                kept.append((TIE_CLASSES.index("special_values" if spec >= 0 else kind), i, j, P, N, Q, V, EX))
+                assert tries < 400000, (A, f64, kills, ties, specials)
+            # busy patterns and the all-zero counts, derived from kept cases
+            base = [c for c in kept if c[0] < 6]
+            extra = []
+            for c in base[:6]:
+                _, i, j, P, N, Q, V, EX = c
+                w = _select(_ref_scores(P, N, Q, math.sqrt(int(N.sum())), f64), (EX > 0) & (V == 0))
+                V2 = V.copy()
+                V2[w] = 2
+                extra.append((TIE_CLASSES.index("winner_busy"), i, j, P, N, Q, V2, EX))
+            for c in base[6:9]:
+                _, i, j, P, N, Q, V, EX = c
+                extra.append((TIE_CLASSES.index("all_busy"), i, j, P, N, Q, np.where(EX > 0, 2, 0).astype(np.int8), EX))
+            for c in base[9:13]:
+                _, i, j, P, N, Q, V, EX = c
+                for busy in (0, 2):
+                    EX2 = np.zeros(A, np.int8)
+                    EX2[A - 1] = 1
+                    P2, N2, Q2, V2 = np.zeros(A), np.zeros(A, np.int32), np.zeros(A, np.float32), np.zeros(A, np.int8)
+                    P2[A - 1], N2[A - 1], Q2[A - 1], V2[A - 1] = P[j], N[j], Q[j], busy
+                    extra.append((TIE_CLASSES.index("only_pass_busy" if busy else "only_pass_free"), A - 1, A - 1, P2, N2, Q2, V2, EX2))
+            for t, c in enumerate(base[13:25]):
+                _, i, j, P, N, Q, V, EX = c
+                P2 = np.where(EX > 0, 2.0 ** -12, 0.0)
+                P2[i] = P[i] if P[i] > 2.0 ** -10 else 0.25
+                P2[j] = P2[i]
+                for _ in range(t % 3):                                   # equal, or j one / two ulp (of the regime) above
+                    P2[j] = np.nextafter(P2[j], 1.0) if f64 else np.nextafter(f32(P2[j]), f32(1))
+                extra.append((TIE_CLASSES.index("counts_all_zero"), i, j, P2, np.zeros(A, np.int32), np.zeros(A, np.float32), V, EX))
+            print("puct_ties A=%d %s: %d tries, %d near-tie + %d derived cases; cases that defeat each wrong formula: %s" % (
+                A, "float64 root" if f64 else "float32", tries, len(kept), len(extra), kills))
+            assert min(kills.values()) >= 20
+            rows += [(f64,) + c for c in kept + extra]
+        n = len(rows)
+        out_vl, out_one, out_top = np.zeros(n, np.int32), np.zeros(n, np.int32), np.full((n, 8), -1, np.int32)
+        for r, (f64, cls, i, j, P, N, Q, V, EX) in enumerate(rows):
+            out_vl[r], out_one[r], out_top[r] = reference(P, N, Q, V, EX, f64)
+            free = (EX > 0) & (V == 0)
+            assert out_vl[r] == _select(_ref_scores(P, N, Q, math.sqrt(int(N.sum())) or 1, f64), free), (A, r)
+        sfx = "_%d" % A
+        data["A" + sfx] = np.full(n, A, dtype=np.int32)
+        data["F64" + sfx] = np.array([r[0] for r in rows], dtype=np.int8)
+        data["cls" + sfx] = np.array([r[1] for r in rows], dtype=np.int8)
+        data["I" + sfx] = np.array([r[2] for r in rows], dtype=np.int32)
+        data["J" + sfx] = np.array([r[3] for r in rows], dtype=np.int32)
+        data["P" + sfx] = np.array([r[4] for r in rows], dtype=np.float64)
+        data["N" + sfx] = np.array([r[5] for r in rows], dtype=np.int32)
+        data["Q" + sfx] = np.array([r[6] for r in rows], dtype=np.float32)
+        data["V" + sfx] = np.array([r[7] for r in rows], dtype=np.int8)
+        data["EX" + sfx] = np.array([r[8] for r in rows], dtype=np.int8)
+        data["out_vl" + sfx], data["out_one" + sfx], data["out_top" + sfx] = out_vl, out_one, out_top
+    np.savez_compressed(out, **data)
+    print("puct_ties: %d bytes" % os.path.getsize(out))
+
+
 def _tree_hash(root):
     """Canonical serialisation: pre-order, ascending action; per child
     <i action, i count, f value, f mean_value, d p, i virtual_loss, i expanded>."""
@@ -924,6 +1145,11 @@ ASYNC_CASES = [
     (13, 40, 8, "hash", 8, 3, 14),
     (7, 36, 4, "hash", None, 5, 15),         # whole 7x7 game, 4-leaf rounds
     (13, 33, 16, "uniform", 5, 5, 16),       # sims not divisible by the energy (32 effective), 16-leaf rounds
+    # full-mantissa priors (stub_nets.TableNet: exact zeros, denormals, v = +-1.0): the nets above are rounding-free by design
+    (9, 64, 8, "table", 14, 5, 17),
+    (5, 48, 8, "table", None, 3, 18),        # whole 5x5 game
+    (19, 400, 8, "table", 2, 30, 19),        # the headline search width
+    (9, 48, 8, "table+hash2", 30, 0, 20),    # two-model game
 ]
 
 
@@ -932,6 +1158,7 @@ SYNC_CASES = [
     (9, 48, 8, "hash", 10, 4, 11),
     (9, 32, 4, "dummy", 8, 2, 12),
     (5, 24, 8, "hash", 12, 3, 13),
+    (9, 48, 8, "table", 10, 4, 14),
 ]
 
 
@@ -979,6 +1206,8 @@ def main():
             child_sym(int(a.child[1]), a.child[2])
         elif what == "puct":
             child_puct(a.child[1])
+        elif what == "puct_ties":
+            child_puct_ties(a.child[1])
         elif what == "units":
             child_units(a.child[1])
         elif what == "gtp":
@@ -1007,6 +1236,8 @@ def main():
             run_child(["sym", s, os.path.join(HERE, "sym_S%d.npz" % s)], scratch)
     if only in (None, "puct"):
         run_child(["puct", os.path.join(HERE, "puct.npz")], scratch)
+    if only in (None, "puct_ties"):
+        run_child(["puct_ties", os.path.join(HERE, "puct_ties.npz")], scratch)
     if only in (None, "units"):
         run_child(["units", os.path.join(HERE, "units_S9.npz")], scratch)
     if only in (None, "gtp"):

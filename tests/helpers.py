@@ -23,8 +23,21 @@ def name_of(z, key):
     return bytes(z[key]).decode()
 
 
-# 08 = BASELINE config 5 (19x19, 1600 sims, 32-leaf rounds); 09..11 are the two-model games; 12..14: 13x13 / 7x7, energies 4 / 16
-ASYNC_FILES = ["async_%02d.npz" % i for i in list(range(9)) + [12, 13, 14]]
+# 08 = BASELINE config 5 (19x19, 1600 sims, 32-leaf rounds); 09..11 and 18 are the two-model games; 12..14: 13x13 / 7x7,
+# energies 4 / 16; 15..17: full-mantissa priors (stub_nets.TableNet) at 9x9, 5x5 and 19x19 / 400 sims
+ASYNC_FILES = ["async_%02d.npz" % i for i in list(range(9)) + [12, 13, 14, 15, 16, 17]]
+TWO_MODEL_FILES = ["async_09.npz", "async_10.npz", "async_11.npz", "async_18.npz"]
+
+
+def selector_tables(name):
+    """[(A, {P, N, Q, V, EX, F64, out_vl, out_one, out_top[, cls, I, J]}, class names)] of a selector fixture: puct.npz is one
+    table set of A = 82; puct_ties.npz holds one set per size, its arrays suffixed _<A>."""
+    z = load(name)
+    keys = ("P", "N", "Q", "V", "EX", "F64", "out_vl", "out_one", "out_top")
+    if "sizes" not in z.files:
+        return [(z["P"].shape[1], {k: z[k] for k in keys}, None)]
+    names = bytes(z["cls_names"]).decode().split("\n")
+    return [(int(A), {k: z["%s_%d" % (k, A)] for k in keys + ("cls", "I", "J")}, names) for A in z["sizes"]]
 
 
 def dict_tree_hash(root):
@@ -46,7 +59,7 @@ def dict_tree_hash(root):
     return h.digest()[:16], n_nodes[0]
 
 
-SYNC_FILES = ["sync_%02d.npz" % i for i in range(3)]
+SYNC_FILES = ["sync_%02d.npz" % i for i in range(4)]
 
 
 # ---- the reference's unit tests recorded as data (tests/golden/units_S9.npz, gen_golden.py child_units) ----------

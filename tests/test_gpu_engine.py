@@ -8,7 +8,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from tests.helpers import load, sha8, ASYNC_FILES
+from tests.helpers import load, sha8, ASYNC_FILES, TWO_MODEL_FILES
 
 pytestmark = pytest.mark.gpu
 
@@ -92,11 +92,21 @@ def test_golden_trees(L, fn):
 
 def test_many_concurrent_games_equal_the_oracle(L):
     """64 games with different draws share one GPU context; each must equal the oracle's game."""
+    _many_concurrent_games(L, "hash")
+
+
+def test_many_concurrent_games_equal_the_oracle_on_full_mantissa_priors(L):
+    """The same with stub_nets.TableNet: 24-bit mantissas, exact zeros, denormals, v = +-1.0 through expand's gather, the float64
+    Dirichlet mix and the back-up (the hash net is rounding-free by construction)."""
+    _many_concurrent_games(L, "table")
+
+
+def _many_concurrent_games(L, net_kind):
     from oracle import oracle as ora
     from sejonggo_amd.engine import SelfPlayEngine
     from sejonggo_amd.stub_nets import make_stub
     S, sims, E, G, nm = 9, 48, 8, 64, 14
-    net = make_stub("hash", S)
+    net = make_stub(net_kind, S)
     rng = np.random.RandomState(11)
     noises = rng.dirichlet([0.03] * (S * S + 1), size=G)
     uni = rng.random_sample((G, nm))
@@ -249,9 +259,6 @@ def test_headline_batch_shape_from_the_shared_pool(L):
     eng.step()
     assert eng.pool_info()["shared_free"] == pool
     eng.close()
-
-
-TWO_MODEL_FILES = ["async_09.npz", "async_10.npz", "async_11.npz"]
 
 
 def _eval_engine(z, halt_at=None, **kw):
@@ -440,7 +447,7 @@ class _PackedProbe(object):
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "captured_rounds"])
-@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz", "async_07.npz", "async_08.npz"])
+@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz", "async_07.npz", "async_08.npz", "async_15.npz"])
 def test_packed_record_route_reproduces_the_golden_games(L, fn, graph):
     """The engine's packed-record route (evaluation list of record indices -> sgo_stem_packed_dev, no input tensor) against the
     reference's goldens: 9x9 and 5x5 games incl. the 'No best leaf' path, 19x19 at 400 sims and at 1 600 sims / 32-leaf rounds."""
@@ -470,6 +477,14 @@ def test_packed_record_route_reproduces_the_golden_games(L, fn, graph):
 
 
 def test_two_half_populations_on_two_streams_equal_the_oracle(L):
+    _two_half_populations(L, "hash")
+
+
+def test_two_half_populations_on_two_streams_equal_the_oracle_on_full_mantissa_priors(L):
+    _two_half_populations(L, "table")
+
+
+def _two_half_populations(L, net_kind):
     """engine.DualEngine: 48 games as two half-populations alternating on two HIP streams, every round a captured launch
     chain (stem from the records -> ... -> k_search -> k_compact -> board_advance), different round counts per game (some
     resign, some pass out), slots restarted mid-run.  Each game must equal the oracle's game for the same draws, move for
@@ -478,7 +493,7 @@ def test_two_half_populations_on_two_streams_equal_the_oracle(L):
     from sejonggo_amd.engine import DualEngine
     from sejonggo_amd.stub_nets import make_stub
     S, sims, E, G, nm = 9, 48, 8, 48, 12
-    net = make_stub("hash", S)
+    net = make_stub(net_kind, S)
     rng = np.random.RandomState(31)
     noises = rng.dirichlet([0.03] * (S * S + 1), size=2 * G)
     uni = rng.random_sample((2 * G, nm))
@@ -541,11 +556,22 @@ def test_two_stream_engine_refuses_large_rounds(L):
 @pytest.mark.parametrize("packed", [False, True])
 @pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, 6, 7, "avg8"])
 def test_symmetry_modes_equal_the_oracle(L, mode, packed):
+    _symmetry_mode(L, mode, packed, "hash")
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("mode", [3, "avg8"])
+def test_symmetry_modes_equal_the_oracle_on_full_mantissa_priors(L, mode, packed):
+    """avg8 is the only place eight float32 policies are summed, and on the hash net every such sum is exact."""
+    _symmetry_mode(L, mode, packed, "table")
+
+
+def _symmetry_mode(L, mode, packed, net_kind):
     from oracle import oracle as ora
     from sejonggo_amd.engine import SelfPlayEngine
     from sejonggo_amd.stub_nets import make_stub
     S, sims, E, nm = 9, 32, 8, 6
-    net = make_stub("hash", S)
+    net = make_stub(net_kind, S)
     rng = np.random.RandomState(21)
     noises = rng.dirichlet([0.03] * (S * S + 1), size=2)
     uni = rng.random_sample((2, nm))
@@ -564,6 +590,58 @@ def test_symmetry_modes_equal_the_oracle(L, mode, packed):
         tb, _, _ = g.tree_serialize()
         assert ta.tobytes() == tb.tobytes()
     eng.close()
+
+
+def test_move_choice_at_a_cdf_boundary_equals_the_oracle(L):
+    """The sampled move (nomodel_self_play.py:125-136, np.random.choice = searchsorted(cdf, u, side='right')) is the other
+    argmax-like choice of the loop.  The root counts of ply 0 are recorded first; then the game is replayed with the first
+    uniform draw placed exactly on a cdf boundary, cdf[i] / cdf[-1], and one ulp below it: the two draws choose neighbouring
+    moves, and the engine must choose what the oracle chooses (whose cdf code the golden games pin) in both."""
+    from oracle import oracle as ora
+    from sejonggo_amd.engine import SelfPlayEngine
+    from sejonggo_amd.stub_nets import make_stub
+    S, sims, E, nm = 9, 48, 8, 3
+    net = make_stub("hash", S)
+    rng = np.random.RandomState(41)
+    noises = rng.dirichlet([0.03] * (S * S + 1), size=1)
+    uni = rng.random_sample((1, nm))
+
+    def engine(u, halt_at=None):
+        eng = SelfPlayEngine(net, size=S, n_games=1, sims=sims, energy=E, stop_exploration=nm, num_moves=nm, komi=5.5,
+                             symmetry="identity")
+        eng.start_games([0], noises=noises, uniforms=u)
+        if halt_at is not None:
+            eng.set_halt(0, halt_at)
+        return eng, eng.run()
+
+    g = ora.Game(S, sims, E, nm, nm, uniforms=uni[0], noises=noises, halt_at=0)
+    while g.phase != ora.PH_DONE:
+        p, v = net.predict_on_batch(g.pending())
+        g.submit(p, v)
+    N = g.root_table()["N"]
+    eng, _ = engine(uni, halt_at=0)
+    assert np.array_equal(eng.root_table(0)["N"], N)
+    eng.close()
+    moves = np.flatnonzero(N)
+    assert len(moves) >= 4
+    cdf = np.cumsum(N[moves] / float(N.sum()))
+    cdf /= cdf[-1]
+    i = len(moves) // 2
+    chosen = []
+    for u0 in (cdf[i], np.nextafter(cdf[i], 0.0)):
+        u = uni.copy()
+        u[0, 0] = u0
+        o = ora.Game(S, sims, E, nm, nm, uniforms=u[0], noises=noises).run(net)
+        eng, games = engine(u)
+        assert o.n_moves == nm == len(games[0]["moves"])
+        for k, mv in enumerate(games[0]["moves"]):
+            m = o.move(k)
+            assert (mv["move"][0] + S * mv["move"][1] if mv["move"][1] != S else S * S) == m["action"], (u0, k)
+            assert np.array_equal(mv["board"], m["board"]) and mv["policy"].tobytes() == m["policy"].tobytes(), (u0, k)
+        assert eng.tree_serialize(0)[0].tobytes() == o.tree_serialize()[0].tobytes()
+        eng.close()
+        chosen.append(o.move(0)["action"])
+    assert chosen == [moves[i + 1], moves[i]]          # side='right': a draw ON the boundary belongs to the next move
 
 
 def test_real_net_selfplay_runs_and_restarts(L):
@@ -588,7 +666,7 @@ def test_real_net_selfplay_runs_and_restarts(L):
     eng.close()
 
 
-@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz", "async_07.npz", "async_13.npz"])
+@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz", "async_07.npz", "async_13.npz", "async_17.npz"])
 def test_golden_games_from_the_shared_block_pool(L, fn):
     """The context-wide block pool: with a private region of the minimum size (energy + 2 blocks) practically every tree block
     of the game is an overflow id backed by the shared pool -- taken one at a time inside k_search, handed back by the re-root's
@@ -921,6 +999,15 @@ def test_other_sizes_and_energies_equal_the_oracle(L, S, sims, E, nm):
 
 @pytest.mark.parametrize("seed", [101, 102, 103, 104, 105, 106, 107, 108])
 def test_fuzzed_configurations_equal_the_oracle(L, seed):
+    _fuzzed_configuration(L, seed, None)
+
+
+@pytest.mark.parametrize("seed", [101, 102, 103, 104, 105, 106, 107, 108])
+def test_fuzzed_configurations_equal_the_oracle_on_full_mantissa_priors(L, seed):
+    _fuzzed_configuration(L, seed, "table")
+
+
+def _fuzzed_configuration(L, seed, net_kind):
     """Randomly drawn configurations (board size, simulations not divisible by the energy, energies 1..32, exploration
     cut-off, komi, self-play with Dirichlet noise or evaluation mode, per-game resign thresholds, stub net): every move,
     board, prior vector, value, result and the final tree must equal the oracle's, byte for byte."""
@@ -935,7 +1022,8 @@ def test_fuzzed_configurations_equal_the_oracle(L, seed):
     stop = int(rng.randint(0, nm + 1))
     komi = float(rng.choice([0.5, 5.5, 7.5]))
     self_play = bool(rng.randint(0, 2))
-    net = make_stub(str(rng.choice(["hash", "uniform"])), S)
+    drawn = str(rng.choice(["hash", "uniform"]))              # drawn in either case: the configurations stay the same
+    net = make_stub(net_kind or drawn, S)
     G = 8
     noises = rng.dirichlet([0.03] * (S * S + 1), size=G)
     uni = rng.random_sample((G, nm))

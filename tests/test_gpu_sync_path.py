@@ -4,7 +4,7 @@ calls go through libsgo_hip.so."""
 import numpy as np
 import pytest
 
-from tests.helpers import load, sha8, dict_tree_hash, SYNC_FILES
+from tests.helpers import load, sha8, dict_tree_hash, SYNC_FILES, TWO_MODEL_FILES
 
 pytestmark = pytest.mark.gpu
 
@@ -79,7 +79,7 @@ def test_sync_play_game_matches_reference(sync_env, fn, monkeypatch):
     assert gd['result'] == bytes(z["result"]).decode()
 
 
-@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz"])
+@pytest.mark.parametrize("fn", ["async_02.npz", "async_05.npz", "async_16.npz"])
 def test_host_async_path_matches_reference(sync_env, fn, monkeypatch):
     """nomodel_self_play.play_game_host (host dict trees, async_simulate2 + back_propagation mirrors) replays the
     reference's golden async games, including the game that hits the 'No best leaf' path 24 times."""
@@ -156,9 +156,6 @@ def test_gtp_front_end(sync_env):
     finally:
         pq.set_model_factory(None)
         pq.destroy_predicting_workers([0])
-
-
-TWO_MODEL_FILES = ["async_09.npz", "async_10.npz", "async_11.npz"]
 
 
 @pytest.mark.parametrize("fn", TWO_MODEL_FILES)

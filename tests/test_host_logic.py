@@ -102,7 +102,7 @@ def test_stub_nets_numpy_equals_torch():
     import torch
     from sejonggo_amd.stub_nets import make_stub
     rng = np.random.RandomState(2)
-    for kind in ("uniform", "dummy", "hash"):
+    for kind in ("uniform", "dummy", "hash", "table"):
         net = make_stub(kind, 9)
         X = rng.randint(0, 2, size=(5, 9, 9, 17)).astype(np.int32)
         X[..., 16] = -1
@@ -110,6 +110,68 @@ def test_stub_nets_numpy_equals_torch():
         p2, v2 = net.predict_on_batch(torch.from_numpy(X).to(torch.float16))
         assert p1.dtype == np.float32 and p1.tobytes() == p2.numpy().tobytes()
         assert v1.tobytes() == v2.numpy().tobytes()
+
+
+TABLE_SHA256 = {5: "4afc77d0508e4a8e41b149d2ed215d052c1bdbf46dc9577bb3f94c8fec68b36a",
+                7: "b33da1ce64e3686dcae32e9933f9930928c5aa86d66753b5e44d5150e6659590",
+                9: "8f8e56011871e3cb2871e28aba4d8548dda008e3a6ac991912b4ff2643d512e1",
+                13: "c391c88e3c6b7511a0d0f1604d8781d7ab8056a8fcfbcca977863cd874eb46e8",
+                19: "3eddc297376dcbed4807aa861e5fc5a627b7f2e0d52a170b43d52344d7cf5a11"}
+
+
+def test_table_net_is_the_same_table_on_every_host():
+    """TableNet's table is assembled from bit patterns (no libm, no reductions); the fixtures async_15..18 / sync_03 were recorded
+    with exactly these bytes.  A host that builds another table fails here, not in every fixture."""
+    import hashlib
+    from sejonggo_amd.stub_nets import make_stub
+    for S, want in TABLE_SHA256.items():
+        net = make_stub("table", S)
+        assert net._T.dtype == np.float32 and net._T.shape == (net.K, S * S + 1) and net._V.dtype == np.float32
+        assert hashlib.sha256(net._T.tobytes() + net._V.tobytes()).hexdigest() == want, S
+
+
+def test_table_net_has_the_value_domain_of_a_trained_head():
+    """What the rounding-free stubs never produce: full 24-bit mantissas, exact zeros, float32 denormals, near one-hot rows, an
+    all-equal row, v = +-1.0 and +-0.0 -- and positions whose strongest prior sits on an illegal point."""
+    import torch
+    from oracle import oracle as ora
+    from sejonggo_amd.stub_nets import make_stub
+    tiny = np.finfo(np.float32).tiny
+    for S in (5, 9, 19):
+        net = make_stub("table", S)
+        T, V = net._T, net._V
+        assert np.isfinite(T).all() and (T >= 0).all() and (T < 1).all() and (np.abs(V) <= 1).all()
+        assert (T == 0).sum() > 100 and ((T > 0) & (T < tiny)).sum() > 100
+        bits = T.view(np.uint32)
+        assert ((bits & 1) == 1).mean() > 0.3 and ((bits & 0xFFF) != 0).mean() > 0.8        # the low mantissa bits are in use
+        assert (T.max(axis=1) > 0.99).sum() >= 3 * (net.K // 8) and any((r == r[0]).all() for r in T)
+        for v, neg in ((1.0, False), (-1.0, True), (0.0, False), (0.0, True)):
+            assert np.any((V == v) & (np.signbit(V) == neg))
+        assert np.any((V != 0) & (np.abs(V) < tiny))
+        rng = np.random.RandomState(S)
+        X = rng.randint(-1, 2, size=(300, S, S, 17)).astype(np.int32)
+        p1, v1 = net.predict_on_batch(X)
+        p2, v2 = net.predict_on_batch(torch.from_numpy(X))
+        assert p1.tobytes() == p2.numpy().tobytes() and v1.tobytes() == v2.numpy().tobytes() and v1.shape == (300, 1)
+        assert len({r.tobytes() for r in p1}) > net.K // 2                                  # the positions reach most rows
+    # the recorded 9x9 game: some evaluated positions have their largest prior on a point that is not legal
+    z = load("async_15.npz")
+    net = make_stub("table", 9)
+    g = ora.Game(9, int(z["sims"]), int(z["energy"]), int(z["stop_exploration"]), int(z["num_moves"]), uniforms=z["uniforms"],
+                 noises=z["noises"])
+    on_illegal = n_zero = n_denormal = 0
+    while g.phase != ora.PH_DONE:
+        boards = g.pending().copy()
+        p, v = net.predict_on_batch(boards)
+        for b, row in zip(boards, p):
+            legal = ora.legal_moves(b[None]) == 0
+            on_illegal += not legal[int(np.argmax(row))]
+            n_zero += int((row[legal] == 0).sum())
+            n_denormal += int(((row[legal] > 0) & (row[legal] < tiny)).sum())
+        g.submit(p, v)
+    print("async_15: %d evaluations with the largest prior on an illegal point; %d zero and %d denormal priors on legal moves"
+          % (on_illegal, n_zero, n_denormal))
+    assert on_illegal >= 10 and n_zero >= 100 and n_denormal >= 100
 
 
 def test_dummy_net_restates_reference_dummy_model():

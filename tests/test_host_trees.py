@@ -3,7 +3,7 @@ They read like the reference's test/tree_util_tests.py and are pinned by tests/g
 reference's own selectors)."""
 import numpy as np
 
-from tests.helpers import load
+from tests.helpers import load, selector_tables
 
 
 def _subtree(P, N, Q, V, EX, f64):
@@ -16,15 +16,23 @@ def _subtree(P, N, Q, V, EX, f64):
     return sub
 
 
-def test_selectors_match_reference_outputs():
+def _check_selectors(z, tag):
     from sejonggo_amd.play import top_one_with_virtual_loss, top_one_action, top_n_actions
-    z = load("puct.npz")
     for c in range(len(z["F64"])):
         sub = _subtree(z["P"][c], z["N"][c], z["Q"][c], z["V"][c], z["EX"][c], int(z["F64"][c]))
         r = top_one_with_virtual_loss({'subtree': sub})
-        assert (r['action'] if r else -1) == z["out_vl"][c], c
-        assert top_one_action(sub)['action'] == z["out_one"][c], c
-        assert [d['action'] for d in top_n_actions(sub, 8)] == [a for a in z["out_top"][c] if a >= 0], c
+        assert (r['action'] if r else -1) == z["out_vl"][c], (tag, c)
+        assert top_one_action(sub)['action'] == z["out_one"][c], (tag, c)
+        assert [d['action'] for d in top_n_actions(sub, 8)] == [a for a in z["out_top"][c] if a >= 0], (tag, c)
+
+
+def test_selectors_match_reference_outputs():
+    _check_selectors(load("puct.npz"), "puct")
+
+
+def test_selectors_match_reference_outputs_on_near_ties():
+    for A, z, _ in selector_tables("puct_ties.npz"):
+        _check_selectors(z, A)
 
 
 def _leaf(index, p, value=0):
