@@ -139,7 +139,8 @@ long sgo_conv3x3_tower_packed_bytes(void);
 int sgo_conv3x3_tower_prepack_dev(const void *d_w, void *d_wp, void *stream);
 int sgo_conv3x3_tower_packed_dev(int n, int h, int w, const void *d_x, const void *d_wp, const void *d_bias, const void *d_skip,
                                  void *d_y, void *stream);
-/* Schedule variant of k_conv4r (A/B builds with -DSGO_CONV4W_VARIANTS; 1 = the product).  Returns the previous one; negative = query. */
+/* Schedule variant of k_conv4r (A/B builds with -DSGO_CONV4W_VARIANTS: 0, 3, 17; 1 = the product, which any other value and
+ * every product build runs).  Returns the previous one; negative = query. */
 int sgo_conv_packed_variant(int v);
 /* The hand-written CDNA4 kernel for the stem (c = 32: the 17 input planes zero-padded, k = 256, pad 0, no skip;
  * csrc/sgo_stem.hpp; model.py:57-60).  x [n][h][w][32] is layout 2 of sgo_nn_pack_dev: the route of callers that hold board
@@ -156,7 +157,8 @@ int sgo_stem_packed_dev(int S, int n, const uint32_t *d_records, const int32_t *
                         const void *d_w10, const void *d_bias, const float *d_wcol, void *d_y, void *stream);
 /* Which hand-written kernel sgo_conv3x3_tower_dev launches: 1 = k_conv4w (csrc/sgo_conv4w.hpp: two 256-thread workgroups per
  * CU, 256 pixels x 128 channels each; the default), 0 = k_conv8w (csrc/sgo_conv8w.hpp: one 512-thread workgroup per CU,
- * 256 pixels x 256 channels).  Same results bit for bit.  Returns the previous choice; other values only query. */
+ * 256 pixels x 256 channels); 16 + v = k_conv4w's schedule variant v (A/B builds with -DSGO_CONV4W_VARIANTS: 0, 4, 5, 6; any other
+ * v and every product build run the product's 7).  Same results bit for bit.  Returns the previous choice; other values only query. */
 int sgo_conv_tower_kernel(int mode);
 /* Tile order of the tower kernel's launches: 1 = every XCD walks a contiguous range of pixel tiles (default: the halo rows
  * a tile shares with its neighbour are then in that XCD's L2), 0 = identity.  Returns the previous mode; other values query. */

@@ -1,8 +1,9 @@
 // sgo_conv.hip -- the 3x3 convolutions of the resident policy/value net with the bias / skip / ReLU epilogue fused
 // into the kernel (model.py:37-46, :57-60 of the reference: Conv2D -> BatchNorm (folded) -> [Add] -> ReLU).  Both shapes
 // the reference's topology needs are hand-written CDNA4 kernels:
-//   * sgo_conv8w.hpp -- the residual tower (256 -> 256 channels, 'same' padding, board width <= 19): sgo_conv3x3_tower_dev,
-//     40 of the 41 convolutions of a forward pass and 98 % of a self-play step's GPU time;
+//   * sgo_conv4w.hpp (default) / sgo_conv8w.hpp / sgo_conv4r.hpp, what they share in sgo_conv_tile.hpp -- the residual tower
+//     (256 -> 256 channels, 'same' padding, board width <= 19): sgo_conv3x3_tower_dev, 40 of the 41 convolutions of a forward
+//     pass and 98 % of a self-play step's GPU time;
 //   * sgo_stem.hpp   -- the stem (17 planes presented as 32 channels -> 256, 'valid'): sgo_conv3x3_stem_dev.
 // sgo_conv3x3_bias_act_dev dispatches on the shape and reports SGO_ERR_UNSUPPORTED for anything else (other channel
 // counts: the host then runs that layer through the framework's convolution + sgo_bias_act_dev, net.FusedInferenceNet).
@@ -16,7 +17,7 @@
 
 namespace {
 int g_tower_kernel = 1;       // 1: k_conv4w (two 256-thread workgroups per CU; default, +2-3 %), 0: k_conv8w (one 512-thread workgroup per CU)
-int g_packed_variant = 1;     // schedule variant of k_conv4r (A/B builds; 1 = product)
+int g_packed_variant = 1;     // schedule variant of k_conv4r (A/B builds: 0, 3, 17; 1 = product)
 long g_tower_slice_cap = 0;   // > 0: samples per launch of the tower kernel are capped (tests of the slice loop)
 }
 
@@ -28,7 +29,7 @@ extern "C" long sgo_conv_tower_slice_cap(long cap) {
 
 extern "C" int sgo_conv_tower_kernel(int mode) {
     const int old = g_tower_kernel;
-    if (mode == 0 || mode == 1 || (mode >= 16 && mode < 16 + 4096)) g_tower_kernel = mode;   // 16 + v: k_conv4w schedule variant v (A/B builds)
+    if (mode == 0 || mode == 1 || (mode >= 16 && mode < 16 + 4096)) g_tower_kernel = mode;   // 16 + v: k_conv4w schedule variant v (A/B builds: 0, 4, 5, 6; else 7)
     return old;
 }
 

@@ -35,37 +35,15 @@
 //   processing), every lane adds bias/skip, applies ReLU and writes its 8-byte pieces back in place, and whole 512-B rows
 //   leave as 16 B per lane.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "sgo_conv_tile.hpp"
 
 namespace sgo_conv8w {
+using namespace sgo_conv_tile;   // vector types, CIN, COUT, ROWB, MAXW, LZ_BYTES, launch_geometry
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef int intx2 __attribute__((ext_vector_type(2)));
-typedef int intx4 __attribute__((ext_vector_type(4)));
-
-#define SGW_AS1 __attribute__((address_space(1)))
-#define SGW_AS3 __attribute__((address_space(3)))
-
-constexpr int CIN = 256, COUT = 256, NTILE = 36;
-constexpr int ROWB = CIN * 2;        // bytes per pixel row of x / y
+constexpr int NTILE = 36;
 constexpr int WROWB = 9 * CIN * 2;   // bytes per output channel of the weights
-constexpr int MAXW = 19;             // board width limit (window = 256 + 2 (w + 1) <= 296 of 320 rows)
 // LDS map
-constexpr int LW0 = 0, LB0 = 40960, LB1 = 73728, LW1 = 106496, LZ = 147456, LZ_BYTES = 3 * 2048 + 256, LDS_BYTES = LZ + LZ_BYTES;
-
-// LDS accesses the compiler must not order against in-flight LDS-DMA (it would drain vmcnt to 0 before each of its own
-// ds_read once a DMA is pending): issued as asm, waited for by hand (SGW_LGKM0 = lgkmcnt(0) + a scheduling fence).
-#define SGW_DS_READ64(dst, addr, OFF) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory")
-#define SGW_DS_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory")
-#define SGW_DS_WRITE64(addr, val, OFF) asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(OFF) : "memory")
-#define SGW_LGKM0()                                    \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_sched_barrier(0)
-#define SGW_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#define SGW_VMWAIT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+constexpr int LW0 = 0, LB0 = 40960, LB1 = 73728, LW1 = 106496, LZ = 147456, LDS_BYTES = LZ + LZ_BYTES;
 
 template <bool HAS_SKIP>
 __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, const char *__restrict__ wb,
@@ -108,24 +86,14 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
     const int rdB0 = (wc * 32 + (lane & 15)) * 128 + fragB, rdB1 = rdB0 ^ 64;
     const int rowA = HALO + wr * 64 + (lane & 15);   // window row of (G = 0, mt = 0) at tap shift 0
 
-    floatx4 acc[2][2][4][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-#pragma unroll
-                for (int d = 0; d < 2; d++) acc[a][b][c][d] = floatx4{0.f, 0.f, 0.f, 0.f};
+    SGT_ACC_INIT();
     half8 pa[4][2], wlo[2][2], whi[2][2];
 
 #ifdef SGW_NODMA   // ablation build: no DMA inside the K loop
 #define SGW_GLDS_LOOP(src, ldsoff) asm volatile("" ::"v"(src))
 #else
-#define SGW_GLDS_LOOP(src, ldsoff) SGW_GLDS(src, ldsoff)
+#define SGW_GLDS_LOOP(src, ldsoff) SGT_GLDS(src, ldsoff)
 #endif
-#define SGW_GLDS(src, ldsoff) \
-    __builtin_amdgcn_global_load_lds((const SGW_AS1 void *)(src), (SGW_AS3 void *)((SGW_AS3 char *)smem + (ldsoff)), 16, 0, 0)
 
 // stage the channel granule G (0 lo, 1 hi) of the K-tile whose weights start at byte koff_ of a filter row into buffer BUF
 #define SGW_STAGE_BK(BUF, G, koff_)                                                                   \
@@ -157,15 +125,13 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
         }                                                                                             \
     } while (0)
 #define SGW_STAGE_W(cc, pc) SGW_STAGE_WK((cc) & 1, (cc) * 128, pc)
-#define SGW_LDS16(off) (*reinterpret_cast<const half8 *>(smem + (off)))
 // pixel fragments of half G for tap T (compile time) from window buffer WPAR: window row = rowA + G*128 + mt*16 + shift(T),
 // zeros where the tap is off the board
-#define SGW_SHIFT(T) (((T) / 3 == 0 ? -W : (T) / 3 == 2 ? W : 0) + (T) % 3 - 1)
 #define SGW_READ_A(G, T, WPAR)                                                                        \
     do {                                                                                              \
         int ra_ = rowA;                                                                               \
         asm volatile("" : "+v"(ra_));   /* opaque: keeps 36 phases of address arithmetic from being hoisted / kept live */ \
-        const int rl_ = ra_ + SGW_SHIFT(T);                                                           \
+        const int rl_ = ra_ + SGT_SHIFT(T);                                                           \
         const int c0_ = (((lane >> 4) ^ rl_) & 7) << 4;                                               \
         const int b0_ = ((WPAR) ? LW1 : LW0) + (G) * 16384 + (rl_ << 7) + c0_, b1_ = b0_ ^ 64;        \
         /* an off-board tap reads zeros from the SAME bank slot its window address has (row parity, chunk): no new */ \
@@ -175,14 +141,14 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
         asm volatile("" : "+v"(mka_), "+v"(mkb_));   /* opaque: 144 loop-invariant lane masks would live in SGPR pairs */ \
         _Pragma("unroll") for (int mt_ = 0; mt_ < 4; mt_++) {                                         \
             const bool ok_ = (((mt_ >> 1) ? mkb_ : mka_) & (1 << ((mt_ & 1) * 9 + (T)))) != 0;        \
-            pa[mt_][0] = SGW_LDS16((ok_ ? b0_ : z0_) + mt_ * 2048);                                   \
-            pa[mt_][1] = SGW_LDS16((ok_ ? b1_ : z1_) + mt_ * 2048);                                   \
+            pa[mt_][0] = SGT_LDS16((ok_ ? b0_ : z0_) + mt_ * 2048);                                   \
+            pa[mt_][1] = SGT_LDS16((ok_ ? b1_ : z1_) + mt_ * 2048);                                   \
         }                                                                                             \
     } while (0)
 #define SGW_READ_B(BUF, G, dst)                                                                       \
     _Pragma("unroll") for (int nt_ = 0; nt_ < 2; nt_++) {                                             \
-        dst[nt_][0] = SGW_LDS16(((BUF) ? LB1 : LB0) + (G) * 16384 + nt_ * 2048 + rdB0);               \
-        dst[nt_][1] = SGW_LDS16(((BUF) ? LB1 : LB0) + (G) * 16384 + nt_ * 2048 + rdB1);               \
+        dst[nt_][0] = SGT_LDS16(((BUF) ? LB1 : LB0) + (G) * 16384 + nt_ * 2048 + rdB0);               \
+        dst[nt_][1] = SGT_LDS16(((BUF) ? LB1 : LB0) + (G) * 16384 + nt_ * 2048 + rdB1);               \
     }
 // end of a read/stage interval: own LDS reads retired BEFORE the barrier, so the partner group may re-stage what was
 // read from the very next interval on
@@ -191,7 +157,7 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
     __builtin_amdgcn_sched_barrier(0);                 \
     __builtin_amdgcn_s_barrier();                      \
     __builtin_amdgcn_sched_barrier(0);                 \
-    SGW_PRIO(1)
+    SGT_PRIO(1)
 #ifdef SGW_NOMFMA   // ablation build: fragments kept live, no matrix work
 #define SGW_MFMA(QM, QN, wfrag)                                                                        \
     _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ks_++) {                                              \
@@ -205,16 +171,16 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
             __builtin_amdgcn_mfma_f32_16x16x32_f16(wfrag[nt_][ks_], pa[mt_][ks_], acc[QM][QN][mt_][nt_], 0, 0, 0)
 #endif
 #define SGW_SYNC_OUT()                 \
-    SGW_PRIO(0);                       \
+    SGT_PRIO(0);                       \
     __builtin_amdgcn_sched_barrier(0); \
     __builtin_amdgcn_s_barrier()
 // counted wait of phase B: retires the weights of K-tile t+1 (4 DMAs issued one K-tile ago); younger than those are the
 // window piece of the previous K-tile, the 4 weight DMAs and the window piece of this one
 #define SGW_WAIT_B(nyoung)                     \
     do {                                       \
-        if ((nyoung) == 4) SGW_VMWAIT(4);      \
-        else if ((nyoung) == 5) SGW_VMWAIT(5); \
-        else SGW_VMWAIT(6);                    \
+        if ((nyoung) == 4) SGT_VMWAIT(4);      \
+        else if ((nyoung) == 5) SGT_VMWAIT(5); \
+        else SGT_VMWAIT(6);                    \
     } while (0)
 
 // One K-tile with everything but the chunk pair index kk (0 / 1) known at compile time: tap T, chunk parity CP (chunk cc =
@@ -249,7 +215,7 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
             if (wp_) SGW_STAGE_WK(((CP) + 1) & 1, (2 * kk + (CP) + 1) * 128, T);                          \
             SGW_WAIT_B(4 + (wp_ ? 1 : 0) + (wpprev_ ? 1 : 0));                                            \
         } else if ((T) == 7) {                                                                            \
-            SGW_VMWAIT(0);   /* K-tile 34: K-tile 35's weights */                                         \
+            SGT_VMWAIT(0);   /* K-tile 34: K-tile 35's weights */                                         \
         } else {                                                                                          \
             if (HAS_SKIP) SGW_SKIP_LO(1);                                                                 \
         }                                                                                                 \
@@ -266,29 +232,8 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
     SGW_STAGE_B(0, 1, 0);
     SGW_STAGE_B(1, 0, 1);
     SGW_STAGE_B(1, 1, 1);
-    // ---- tap-validity masks of the lane's 8 fragment rows: row (G, mt) = G*128 + wr*64 + mt*16 + (lane&15);
-    //      mk[G][mt>>1] holds 9 bits per row at bit (mt&1)*9.  Divisions by h*w and w through the host's magic numbers
-    //      (ceil(2^32/d): exact for p*d < 2^32).
-    int mk[2][2];
-#pragma unroll
-    for (int g = 0; g < 2; g++)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; h2++) {
-            int v = 0;
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const int p = tile * 256 + g * 128 + wr * 64 + (h2 * 2 + e) * 16 + (lane & 15);
-                // (a divisor of 1 has no 32-bit magic number -- ceil(2^32 / 1) wraps to 0 -- so x / 1 is added back by hand)
-                const int q = p - (int)(__umulhi((unsigned)p, magicHW) + (HW == 1 ? (unsigned)p : 0u)) * HW;
-                const int yy = (int)(__umulhi((unsigned)q, magicW) + (W == 1 ? (unsigned)q : 0u)), xx = q - yy * W;
-                const int cm = (xx >= 1 ? 1 : 0) | 2 | (xx <= W - 2 ? 4 : 0);
-                int m = (yy >= 1 ? cm : 0) | (cm << 3) | (yy <= H - 2 ? cm << 6 : 0);
-                m = p < M ? m : 0;
-                v |= m << (9 * e);
-            }
-            mk[g][h2] = v;
-        }
-    SGW_VMWAIT(4);
+    SGT_MASKS();
+    SGT_VMWAIT(4);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zero row
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();   // the hi pixel group runs one barrier behind
@@ -303,7 +248,7 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
         const int r_ = (wid * 8 + (j)) * 2 + (elane >> 5);                                             \
         int p_ = tile * 256 + (HF) * 128 + r_;                                                         \
         p_ = p_ < M ? p_ : M - 1;                                                                      \
-        SGW_GLDS(skipb + (unsigned)(p_ * ROWB + (((elane & 31) ^ (r_ & 15)) << 4)), (HF) * 65536 + (wid * 8 + (j)) * 1024); \
+        SGT_GLDS(skipb + (unsigned)(p_ * ROWB + (((elane & 31) ^ (r_ & 15)) << 4)), (HF) * 65536 + (wid * 8 + (j)) * 1024); \
     } while (0)
 #define SGW_NOEXTRA(ph) do { } while (0)
 #define SGW_SKIP_LO(ph) \
@@ -358,10 +303,10 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
             for (int mt = 0; mt < 4; mt++)
 #pragma unroll
                 for (int qn = 0; qn < 2; qn++) {
-                    SGW_DS_READ64(sk[mt][qn][0], a0, mt * 8192 + qn * 256);
-                    SGW_DS_READ64(sk[mt][qn][1], a1, mt * 8192 + qn * 256);
+                    SGT_DS_READ64(sk[mt][qn][0], a0, mt * 8192 + qn * 256);
+                    SGT_DS_READ64(sk[mt][qn][1], a1, mt * 8192 + qn * 256);
                 }
-            SGW_LGKM0();
+            SGT_LGKM0();
         }
 #pragma unroll
         for (int mt = 0; mt < 4; mt++)
@@ -382,18 +327,18 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
                         o[j] = (_Float16)(f > 0.f ? f : 0.f);
                     }
                     const intx2 oi = __builtin_bit_cast(intx2, o);
-                    if (nt == 0) SGW_DS_WRITE64(a0, oi, mt * 8192 + qn * 256);
-                    else SGW_DS_WRITE64(a1, oi, mt * 8192 + qn * 256);
+                    if (nt == 0) SGT_DS_WRITE64(a0, oi, mt * 8192 + qn * 256);
+                    else SGT_DS_WRITE64(a1, oi, mt * 8192 + qn * 256);
                 }
-        SGW_LGKM0();
+        SGT_LGKM0();
         __builtin_amdgcn_s_barrier();
         intx4 ov[8];
         const int a2 = hf * 65536 + wid * 8192 + elane * 16;
 #pragma unroll
-        for (int j = 0; j < 8; j++) SGW_DS_READ128(ov[j], a2, j * 1024);
+        for (int j = 0; j < 8; j++) SGT_DS_READ128(ov[j], a2, j * 1024);
         const int p0 = tile * 256 + hf * 128 + wid * 16 + (elane >> 5);
         char *dst = yb + (size_t)p0 * ROWB;   // row (wid*16 + 2j + (lane>>5)) of the half; its swizzle key is 2j + (lane>>5)
-        SGW_LGKM0();
+        SGT_LGKM0();
         if (tile * 256 + hf * 128 + 128 <= M) {   // whole half inside the tensor (wave-uniform)
 #pragma unroll
             for (int j = 0; j < 8; j++)
@@ -430,21 +375,16 @@ static inline int launch(int n, int h, int w, const void *x, const void *wgt, co
                          , long long *stamps
 #endif
                          ) {
-    const long M = (long)n * h * w;
-    if (M <= 0 || M * ROWB >= (1L << 31) || w > MAXW || w < 1 || h < 1) return -1;
-    // the pixel -> (sample, y, x) split uses magic-number division, exact only while p * (h*w) < 2^32 for every pixel
-    // index the kernel forms (p < M + 256)
-    if ((unsigned long long)(M + 256) * (unsigned long long)(h * w) >= (1ULL << 32)) return -1;
-    const int tiles = (int)((M + 255) / 256);
-    const int xq = tile_order() ? tiles / 8 : -1, xr = tiles % 8;
-    const unsigned mhw = (unsigned)(((1ULL << 32) + (unsigned)(h * w) - 1) / (unsigned)(h * w)), mw = (unsigned)(((1ULL << 32) + (unsigned)w - 1) / (unsigned)w);
+    launch_geom g;
+    if (!launch_geometry(n, h, w, g)) return -1;
+    const int xq = tile_order() ? g.xcd_q : -1;
 #ifdef SGO_CONV8_STAMPS
-#define SGW_ARGS (const char *)x, (const char *)wgt, (const _Float16 *)bias, (const char *)skip, (char *)y, (int)M, h, w, mhw, mw, xq, xr, stamps
+#define SGW_ARGS (const char *)x, (const char *)wgt, (const _Float16 *)bias, (const char *)skip, (char *)y, g.M, h, w, g.magic_hw, g.magic_w, xq, g.xcd_r, stamps
 #else
-#define SGW_ARGS (const char *)x, (const char *)wgt, (const _Float16 *)bias, (const char *)skip, (char *)y, (int)M, h, w, mhw, mw, xq, xr
+#define SGW_ARGS (const char *)x, (const char *)wgt, (const _Float16 *)bias, (const char *)skip, (char *)y, g.M, h, w, g.magic_hw, g.magic_w, xq, g.xcd_r
 #endif
-    if (skip) hipLaunchKernelGGL(k_conv8w<true>, dim3(tiles), dim3(512), 0, st, SGW_ARGS);
-    else hipLaunchKernelGGL(k_conv8w<false>, dim3(tiles), dim3(512), 0, st, SGW_ARGS);
+    if (skip) hipLaunchKernelGGL(k_conv8w<true>, dim3(g.tiles), dim3(512), 0, st, SGW_ARGS);
+    else hipLaunchKernelGGL(k_conv8w<false>, dim3(g.tiles), dim3(512), 0, st, SGW_ARGS);
 #undef SGW_ARGS
     return 0;
 }
@@ -452,20 +392,11 @@ static inline int launch(int n, int h, int w, const void *x, const void *wgt, co
 }  // namespace sgo_conv8w
 
 // the kernel's working macros stay private to this header
-#undef SGW_ARGS
-#undef SGW_DS_READ128
-#undef SGW_DS_READ64
-#undef SGW_DS_WRITE64
-#undef SGW_GLDS
 #undef SGW_GLDS_LOOP
-#undef SGW_LDS16
-#undef SGW_LGKM0
 #undef SGW_MFMA
 #undef SGW_NOEXTRA
-#undef SGW_PRIO
 #undef SGW_READ_A
 #undef SGW_READ_B
-#undef SGW_SHIFT
 #undef SGW_SKIP_LO
 #undef SGW_STAGE_B
 #undef SGW_STAGE_BK
@@ -475,6 +406,6 @@ static inline int launch(int n, int h, int w, const void *x, const void *wgt, co
 #undef SGW_SYNC_IN
 #undef SGW_SYNC_OUT
 #undef SGW_TILE_U
-#undef SGW_VMWAIT
 #undef SGW_WAIT_B
 #undef SGW_WP_COND
+#include "sgo_conv_tile_undef.hpp"

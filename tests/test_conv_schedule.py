@@ -7,15 +7,37 @@ as run-to-run differences on the GPU; round 1 shipped such a bug for a few hours
 by SOME waves only -- those whose rows of the piece exist -- and the count must follow the wave).  This model replays,
 per wave, the order in which the kernel issues its DMAs / loads / stores and checks at every wait that what is read next is
 older than the N youngest.  It is tied to the source: the wait expressions and the piece condition are read from the
-header and the test fails when they change, so the model cannot silently drift from the kernel."""
+header and the test fails when they change, so the model cannot silently drift from the kernel.  What the kernels share
+(csrc/sgo_conv_tile.hpp: helper macros, masks, and for the two 256-thread kernels window staging, fragment reads and the epilogue)
+is pinned once, in test_shared_tile_code_is_in_step_with_the_models; each kernel's own test pins that it uses the shared piece
+and defines no private copy."""
 import os
 import re
 
 HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sejonggo_amd", "csrc", "sgo_conv8w.hpp")
+HDRT = os.path.join(os.path.dirname(HDR), "sgo_conv_tile.hpp")
 
 
 def _src():
     return open(HDR).read()
+
+
+def test_shared_tile_code_is_in_step_with_the_models():
+    s = open(HDRT).read()
+    assert "#define SGT_VMWAIT(n) asm volatile(\"s_waitcnt vmcnt(\" #n \")\" ::: \"memory\")" in s     # SGT_VMWAIT(N) is vmcnt(N), nothing else
+    assert "#define SGT_SHIFT(T) (((T) / 3 == 0 ? -W : (T) / 3 == 2 ? W : 0) + (T) % 3 - 1)" in s
+    # window pieces of the 256-thread kernels: piece pc * 4 + wid, issued by the waves whose rows exist; one DMA each
+    assert "const int id_ = pc_ * 4 + swid;" in s and "if (id_ * 8 < NROWS)" in s
+    assert s.count("#define SGT_STAGE_WP(") == 1 and s.count("#define SGT_READ_A(") == 1
+    assert re.search(r"if \(id_ \* 8 < NROWS\) \{[^}]*SGT_GLDS\(src_, LW \+ id_ \* 1024\);", s)
+    assert "for (int pc = 4; pc < 10; pc++) nlate += ((pc * 4 + wid) * 8 < NROWS) ? 1 : 0" in s
+    # epilogue of the 256-thread kernels: 4 bias loads, 2 x 8 skip DMAs, per half a counted wait and 8 row stores
+    assert s.count("#define SGT_EPILOGUE(") == 1
+    assert re.search(r"for \(int qn = 0; qn < 2; qn\+\+\) _Pragma\(\"unroll\"\) for \(int nt = 0; nt < 2; nt\+\+\)\s*\\\s*asm volatile\(\"global_load_dwordx2", s)
+    assert re.search(r"for \(int hf = 0; hf < 2; hf\+\+\) _Pragma\(\"nounroll\"\) for \(int j = 0; j < 8; j\+\+\) \{[^}]*SGT_GLDS\(skipb", s)
+    assert s.count("asm volatile(\"s_waitcnt vmcnt(8)\" ::: \"memory\");") == 2       # half 0 and half 1, with skip
+    assert s.count("asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");   /* the bias */") == 1
+    assert "for (int j = 0; j < 8; j++)                                                                 \\\n            if (p0 + j * 4 < M)" in s
 
 
 def test_model_is_in_step_with_the_kernel_source():
@@ -30,13 +52,16 @@ def test_model_is_in_step_with_the_kernel_source():
     # prologue: 5 pieces, weights of K-tiles 0 and 1, wait for all but K-tile 1's
     assert re.search(r"for \(int pc = 0; pc < 5; pc\+\+\) SGW_STAGE_W\(0, pc\);\s*SGW_STAGE_B\(0, 0, 0\);\s*SGW_STAGE_B\(0, 1, 0\);\s*"
                      r"SGW_STAGE_B\(1, 0, 1\);\s*SGW_STAGE_B\(1, 1, 1\);", s)
-    assert "SGW_VMWAIT(4);\n    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");   // the zero row" in s
+    assert "SGT_VMWAIT(4);\n    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");   // the zero row" in s
     # tail of the loop and the epilogue
     assert "const bool last2_ = (CP) == 1 && (T) >= 7 && kk == 1;" in s
-    assert "SGW_VMWAIT(0);   /* K-tile 34: K-tile 35's weights */" in s
+    assert "SGT_VMWAIT(0);   /* K-tile 34: K-tile 35's weights */" in s
     assert "if (HAS_SKIP && (CP) == 1 && (T) == 8 && kk == 1) SGW_SKIP_LO(0);" in s and "if (HAS_SKIP) SGW_SKIP_LO(1);" in s
     assert s.count("asm volatile(\"s_waitcnt vmcnt(8)\" ::: \"memory\");") == 1
     assert "for (int j = 0; j < 8; j++) SGW_STAGE_SKIP(1, j);" in s
+    # shared pieces come from csrc/sgo_conv_tile.hpp; no private copies
+    assert "#include \"sgo_conv_tile.hpp\"" in s and "SGT_MASKS();" in s and "__umulhi" not in s
+    assert "#define SGW_VMWAIT" not in s and "#define SGW_GLDS(" not in s and "#define SGW_SHIFT" not in s
 
 
 class Wave(object):
@@ -183,18 +208,20 @@ HDR4 = os.path.join(os.path.dirname(HDR), "sgo_conv4w.hpp")
 def test_conv4w_model_is_in_step_with_the_kernel_source():
     s = open(HDR4).read()
     assert "const bool boundary_ = (T) == 8 && cc < 3;" in s
-    assert "if ((VAR & 4) && boundary_) S4_STAGE_WP((cc + 1) * 128, 0, 4);" in s          # early pieces: rows [0, 128), 4 per wave
-    assert "if ((VAR & 4) && boundary_) S4_VMWAIT(8);" in s and "else S4_VMWAIT(4);" in s
-    assert "if (boundary_) S4_STAGE_WP((cc + 1) * 128, (VAR & 4) ? 4 : 0, 10);" in s
-    assert "if ((VAR & 6) != 6) S4_VMWAIT(0);" in s
-    assert "else if (nlate == 6) S4_VMWAIT(10);" in s and "else if (nlate == 5) S4_VMWAIT(9);" in s and "else if (nlate == 4) S4_VMWAIT(8);" in s
-    assert re.search(r"if \(\(VAR & 6\) == 6 && \(T\) == 0 && cc > 0\) \{[^}]*S4_VMWAIT\(0\);[^}]*S4_KBARRIER\(\);", s)
-    assert "for (int pc = 4; pc < 10; pc++) nlate += ((pc * 4 + wid) * 8 < NROWS) ? 1 : 0;" in s
-    assert "const int id_ = pc_ * 4 + swid;" in s and "if (id_ * 8 < NROWS)" in s
-    assert "S4_VMWAIT(0);                        /* K-tile 34: K-tile 35's weights */" in s
-    assert re.search(r"S4_STAGE_W\(0\);\s*S4_STAGE_BK\(0, 0, 0\);\s*S4_STAGE_BK\(0, 1, 0\);\s*S4_STAGE_BK\(1, 0, CIN \* 2\);\s*S4_STAGE_BK\(1, 1, CIN \* 2\);", s)
-    assert "S4_VMWAIT(4);\n    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");   // the zero area" in s
-    assert "#define S4_SHIFT(T) (((T) / 3 == 0 ? -W : (T) / 3 == 2 ? W : 0) + (T) % 3 - 1)" in s
+    assert "if ((VAR & 4) && boundary_) SGT_STAGE_WP((cc + 1) * 128, 0, 4);" in s          # early pieces: rows [0, 128), 4 per wave
+    assert "if ((VAR & 4) && boundary_) SGT_VMWAIT(8);" in s and "else SGT_VMWAIT(4);" in s
+    assert "if (boundary_) SGT_STAGE_WP((cc + 1) * 128, (VAR & 4) ? 4 : 0, 10);" in s
+    assert "if ((VAR & 6) != 6) SGT_VMWAIT(0);" in s
+    assert "else if (nlate == 6) SGT_VMWAIT(10);" in s and "else if (nlate == 5) SGT_VMWAIT(9);" in s and "else if (nlate == 4) SGT_VMWAIT(8);" in s
+    assert re.search(r"if \(\(VAR & 6\) == 6 && \(T\) == 0 && cc > 0\) \{[^}]*SGT_VMWAIT\(0\);[^}]*SGT_BARRIER\(\);", s)
+    # nlate, the window pieces and the tap shift are the shared header's (pinned above); no private copies
+    assert "SGT_NLATE();" in s and "nlate +=" not in s
+    assert "SGT_STAGE_WP(" in s and "#define S4_STAGE_WP" not in s and "const int id_" not in s
+    assert "SGT_READ_A(0, T);" in s and "SGT_READ_A(1, T);" in s and "#define S4_READ_A" not in s and "#define S4_SHIFT" not in s
+    assert "SGT_EPILOGUE();" in s and "global_load_dwordx2" not in s and "__umulhi" not in s
+    assert "SGT_VMWAIT(0);                       /* K-tile 34: K-tile 35's weights */" in s
+    assert re.search(r"SGT_STAGE_WP\(0, 0, 10\);\s*S4_STAGE_BK\(0, 0, 0\);\s*S4_STAGE_BK\(0, 1, 0\);\s*S4_STAGE_BK\(1, 0, CIN \* 2\);\s*S4_STAGE_BK\(1, 1, CIN \* 2\);", s)
+    assert "SGT_VMWAIT(4);\n    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");   // the zero area" in s
     assert "default: return launch_var<7>(n, h, w, x, wgt, bias, skip, y, st);" in s          # the modelled variant is the shipped one
 
 
@@ -291,19 +318,22 @@ def test_conv4r_model_is_in_step_with_the_kernel_source():
     assert "constexpr int SLO_ = (2 * (T)) % 3, SHI_ = (2 * (T) + 1) % 3, SNX_ = (2 * (T) + 2) % 3;" in s
     assert s.count("(T) == 8 && cc < 3;") == 2 and s.count("(T) == 0 && cc > 0;") == 2
     # grouped form (R4_TILE): L(2t+2) at the start of phase A, L(2t+3) between the two MFMA groups of phase B
-    assert re.search(r"R4_LOADW\(SNX_\);[^\n]*\n\s*R4_READ_A\(0, T\);", s)
+    assert re.search(r"R4_LOADW\(SNX_\);[^\n]*\n\s*SGT_READ_A\(0, T\);", s)
     assert "if (restaged_) R4_VMWAIT_LATE(8);" in s and "else R4_VMWAITW(8);" in s
-    assert "if (boundary_) R4_VMWAIT(8);" in s and "else R4_VMWAITW(4);" in s
+    assert "if (boundary_) SGT_VMWAIT(8);" in s and "else R4_VMWAITW(4);" in s
     assert "if (!(VAR & 2)) R4_LOADW(SLO_);" in s and "R4_VMWAIT_LATE(4);" in s
     # spread form (R4_TILE_S): two pieces of L(2t+2) in each half of phase A's burst, L(2t+3) in the second half of phase B's
-    assert "if (restaged_) R4_VMWAIT_LATE(4);" in s and "if (boundary_) R4_VMWAIT(6);" in s and "else R4_VMWAITW(2);" in s
+    assert "if (restaged_) R4_VMWAIT_LATE(4);" in s and "if (boundary_) SGT_VMWAIT(6);" in s and "else R4_VMWAITW(2);" in s
     assert "R4_G2(0, 0, SLO_, SNX_, 0);" in s and "R4_G2(0, 1, SHI_, SNX_, 2);" in s and "R4_G4(1, 1, SHI_, SLO_);" in s
     assert "R4_VMWAIT_LATE(8);" in s
     assert "if (nlate == 6) { R4_VMWAIT_SUM(base, 6); }" in s and "else { R4_VMWAIT_SUM(base, 0); }" in s
-    assert "for (int pc = 4; pc < 10; pc++) nlate += ((pc * 4 + wid) * 8 < NROWS) ? 1 : 0;" in s
-    assert re.search(r"if \(!\(VAR & 32\)\) R4_STAGE_WP\(0, 0, 10\);[^\n]*\n\s*R4_LOADW\(0\);\s*R4_LOADW\(1\);", s)
-    assert "R4_VMWAIT(8);                                        // the window has landed; in flight: L(0), L(1)" in s
-    assert "R4_STAGE_WP((cc + 1) * 128, 0, 4);" in s and "R4_STAGE_WP((cc + 1) * 128, 4, 10);" in s
+    assert "#define R4_VMWAITW(n) SGT_VMWAIT(n)" in s
+    assert "SGT_NLATE();" in s and "nlate +=" not in s
+    assert "#define R4_STAGE_WP" not in s and "#define R4_READ_A" not in s and "const int id_" not in s
+    assert "SGT_READ_A(1, T);" in s and "SGT_EPILOGUE();" in s and "global_load_dwordx2" not in s and "__umulhi" not in s
+    assert re.search(r"    SGT_STAGE_WP\(0, 0, 10\);[^\n]*\n\s*R4_LOADW\(0\);\s*R4_LOADW\(1\);", s)
+    assert "SGT_VMWAIT(8);                                       // the window has landed; in flight: L(0), L(1)" in s
+    assert "SGT_STAGE_WP((cc + 1) * 128, 0, 4);" in s and "SGT_STAGE_WP((cc + 1) * 128, 4, 10);" in s
     assert "default: return launch_var<1>(n, h, w, x, wpk, bias, skip, y, st);" in s       # grouped form + priorities is what ships
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One tower-convolution kernel, launched back to back: the subject of a rocprofv3 --pmc pass (tools/pmc_conv4r.sh).
-usage: conv_one.py <4w|4r> [variant] [n=8192] [iters=8]      data: ReLU(random) activations + skip, what the tower sees."""
+usage: conv_one.py <4w|4r> [variant] [n=8192] [iters=8]      data: ReLU(random) activations + skip, what the tower sees.
+variant: 4w 0 / 4 / 5 / 6, 4r 0 / 3 / 17 in a library built with -DSGO_CONV4W_VARIANTS; default (and any other number) = the product's."""
 import sys
 import os
 
