@@ -289,8 +289,9 @@ int64_t sgo_tree_dump(sgo_ctx *ctx, int slot, uint8_t *buf, int64_t cap, int64_t
 int sgo_game_board(sgo_ctx *ctx, int slot, int32_t *board17);
 /* test hook: stop slot right before the move choice of move_n == k (phase becomes done, error 0) */
 int sgo_set_halt(sgo_ctx *ctx, int slot, int move_n);
-/* Diagnostic: cycles per phase of k_search, summed over games and calls (zeros unless the library was built with
- * -DSGO_KSEARCH_PROFILE): [0] consuming evaluations, [2] selection, [7] round back-propagation, [3] move step, [4] wave-calls. */
+/* Diagnostic: cycles per phase of k_search (csrc/sgo_search.hpp), summed over games and calls (zeros unless the library was built
+ * with -DSGO_KSEARCH_PROFILE): [0] consuming evaluations, [1] round set-up, [2] selection, [7] round back-propagation,
+ * [3] move step, [4] wave-calls. */
 int sgo_debug_counters(sgo_ctx *ctx, unsigned long long *out, int n);
 /* Test hook: the PUCT selector of the search (play.py:308-323 top_one_with_virtual_loss) on caller-supplied child tables.
  * DEVICE pointers to flat [n_cases][A] arrays: priors as float32 and, when f64 != 0, as the float64 root priors (P64 may be

@@ -80,25 +80,43 @@ void build_sym_lut(int S, int k, int32_t *lut) {
 }
 
 // ------------------------------------------------------------------------------------ kernels
+// What every board_advance kernel resolves for leaf i before it plays the move: the input record, the output record and the
+// legal words through the optional index lists, and who moves -- the colour to play in the record, unless `colors` names the
+// other one (then the record's first plane pair is read swapped).
+struct AdvanceLeaf {
+    const uint32_t *src;
+    uint32_t *dst, *lg;
+    int mover;
+    bool swap_first;
+};
+template <int S>
+__device__ __forceinline__ AdvanceLeaf advance_leaf(int i, const uint32_t *in, const int32_t *in_idx, const int32_t *colors,
+                                                    uint32_t *out, const int32_t *out_idx, uint32_t *legal,
+                                                    const int32_t *legal_idx) {
+    using G = Geo<S>;
+    AdvanceLeaf a;
+    a.src = in + (size_t)(in_idx ? in_idx[i] : i) * G::RW;
+    a.dst = out + (size_t)(out_idx ? out_idx[i] : i) * G::RW;
+    a.lg = legal ? legal + (size_t)(legal_idx ? legal_idx[i] : i) * G::NW : nullptr;
+    a.swap_first = false;
+    a.mover = white_to_play<S>(a.src) ? -1 : 1;
+    if (colors) {
+        int c = colors[i];
+        if (c != 0 && c != a.mover) { a.swap_first = true; a.mover = -a.mover; }
+    }
+    return a;
+}
+
 template <int S>
 __global__ __launch_bounds__(256) void k_advance_legal(int n, const uint32_t *in, const int32_t *in_idx,
                                                        const int32_t *moves, const int32_t *colors, uint32_t *out,
                                                        const int32_t *out_idx, uint32_t *legal,
                                                        const int32_t *legal_idx, int32_t *status) {
-    using G = Geo<S>;
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t *src = in + (size_t)(in_idx ? in_idx[i] : i) * G::RW;
-    uint32_t *dst = out + (size_t)(out_idx ? out_idx[i] : i) * G::RW;
-    uint32_t *lg = legal ? legal + (size_t)(legal_idx ? legal_idx[i] : i) * G::NW : nullptr;
-    bool swap_first = false;
-    int mover = white_to_play<S>(src) ? -1 : 1;
-    if (colors) {
-        int c = colors[i];
-        if (c != 0 && c != mover) { swap_first = true; mover = -mover; }
-    }
-    int st = advance_record<S>(src, dst, moves[i], swap_first, lg);
-    if (status) status[i] = st ? st : mover;
+    const AdvanceLeaf a = advance_leaf<S>(i, in, in_idx, colors, out, out_idx, legal, legal_idx);
+    int st = advance_record<S>(a.src, a.dst, moves[i], a.swap_first, a.lg);
+    if (status) status[i] = st ? st : a.mover;
 }
 
 // ---- split form of board_advance for non-aliasing in/out (the engine's leaf step, dense out-of-place batches)
@@ -171,21 +189,12 @@ __global__ __launch_bounds__(64) void k_advance_planes(int n, const int *n_dev, 
                                                        const int32_t *moves, const int32_t *colors, uint32_t *out,
                                                        const int32_t *out_idx, uint32_t *legal, const int32_t *legal_idx,
                                                        int32_t *status) {
-    using G = Geo<S>;
     if (n_dev) n = *n_dev;
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t *src = in + (size_t)(in_idx ? in_idx[i] : i) * G::RW;
-    uint32_t *dst = out + (size_t)(out_idx ? out_idx[i] : i) * G::RW;
-    uint32_t *lg = legal ? legal + (size_t)(legal_idx ? legal_idx[i] : i) * G::NW : nullptr;
-    bool swap_first = false;
-    int mover = white_to_play<S>(src) ? -1 : 1;
-    if (colors) {
-        int c = colors[i];
-        if (c != 0 && c != mover) { swap_first = true; mover = -mover; }
-    }
-    int st = advance_planes<S>(src, dst, moves[i], swap_first, lg);
-    if (status) status[i] = st ? st : mover;
+    const AdvanceLeaf a = advance_leaf<S>(i, in, in_idx, colors, out, out_idx, legal, legal_idx);
+    int st = advance_planes<S>(a.src, a.dst, moves[i], a.swap_first, a.lg);
+    if (status) status[i] = st ? st : a.mover;
 }
 
 // One launch, two kinds of 64-thread blocks: blocks [0, n_compute_blocks) run the register kernel (one lane per leaf),
@@ -196,7 +205,6 @@ __global__ __launch_bounds__(64) void k_board_advance(int n, const int *n_dev, i
                                                       const int32_t *in_idx, const int32_t *moves, const int32_t *colors,
                                                       uint32_t *out, const int32_t *out_idx, uint32_t *legal,
                                                       const int32_t *legal_idx, int32_t *status) {
-    using G = Geo<S>;
     if (n_dev) n = *n_dev;
     if ((int)blockIdx.x >= n_compute_blocks) {
         const long b = (long)blockIdx.x - n_compute_blocks;
@@ -205,17 +213,9 @@ __global__ __launch_bounds__(64) void k_board_advance(int n, const int *n_dev, i
     }
     int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const uint32_t *src = in + (size_t)(in_idx ? in_idx[i] : i) * G::RW;
-    uint32_t *dst = out + (size_t)(out_idx ? out_idx[i] : i) * G::RW;
-    uint32_t *lg = legal ? legal + (size_t)(legal_idx ? legal_idx[i] : i) * G::NW : nullptr;
-    bool swap_first = false;
-    int mover = white_to_play<S>(src) ? -1 : 1;
-    if (colors) {
-        int c = colors[i];
-        if (c != 0 && c != mover) { swap_first = true; mover = -mover; }
-    }
-    int st = advance_planes<S>(src, dst, moves[i], swap_first, lg);
-    if (status) status[i] = st ? st : mover;
+    const AdvanceLeaf a = advance_leaf<S>(i, in, in_idx, colors, out, out_idx, legal, legal_idx);
+    int st = advance_planes<S>(a.src, a.dst, moves[i], a.swap_first, a.lg);
+    if (status) status[i] = st ? st : a.mover;
 }
 
 // The row-per-lane form (sgo_rows.hpp): one 32-lane half per leaf, history move included.  For the engine's small
@@ -226,22 +226,13 @@ __global__ __launch_bounds__(64) void k_board_advance_rows(int n, const int *n_d
                                                            const int32_t *moves, const int32_t *colors, uint32_t *out,
                                                            const int32_t *out_idx, uint32_t *legal, const int32_t *legal_idx,
                                                            int32_t *status) {
-    using G = Geo<S>;
     if (n_dev) n = *n_dev;
     const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
     const int i = blockIdx.x * 2 + half;
     if (i >= n) return;
-    const uint32_t *src = in + (size_t)(in_idx ? in_idx[i] : i) * G::RW;
-    uint32_t *dst = out + (size_t)(out_idx ? out_idx[i] : i) * G::RW;
-    uint32_t *lg = legal ? legal + (size_t)(legal_idx ? legal_idx[i] : i) * G::NW : nullptr;
-    bool swap_first = false;
-    int mover = white_to_play<S>(src) ? -1 : 1;
-    if (colors) {
-        int c = colors[i];
-        if (c != 0 && c != mover) { swap_first = true; mover = -mover; }
-    }
-    const int st = rows::advance_record_rows<S>(src, dst, moves[i], swap_first, lg, half, y);
-    if (status && y == 0) status[i] = st ? st : mover;
+    const AdvanceLeaf a = advance_leaf<S>(i, in, in_idx, colors, out, out_idx, legal, legal_idx);
+    const int st = rows::advance_record_rows<S>(a.src, a.dst, moves[i], a.swap_first, a.lg, half, y);
+    if (status && y == 0) status[i] = st ? st : a.mover;
 }
 
 

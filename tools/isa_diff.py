@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Are the kernels of two device listings of csrc/sgo_conv.hip the same machine code?  The check behind a source-only change of
-the tower kernels (csrc/sgo_conv_tile.hpp: shared pieces are macros so that this holds): per kernel symbol, the text from its
-label to .end_amdhsa_kernel with `;` comments removed, and VGPRs / LDS bytes / scratch bytes from its descriptor.  Local labels
-carry the ordinal of their function in the file (.LBB64_2); it is dropped, so that removing an instantiation does not make every
-later kernel look different.
+"""Are the kernels of two device listings of one translation unit (csrc/sgo_conv.hip, sgo_engine.hip, sgo_rules.hip) the same
+machine code?  The check behind a source-only change: the tower kernels (csrc/sgo_conv_tile.hpp: shared pieces are macros so
+that this holds), the engine's split into sgo_engine_state.hpp / sgo_search.hpp / sgo_engine_inspect.hpp, the board_advance
+preamble of sgo_rules.hip.  Per kernel symbol: the text from its label to .end_amdhsa_kernel with `;` comments removed, and
+VGPRs / LDS bytes / scratch bytes from its descriptor.  Local labels carry the ordinal of their function in the file (.LBB64_2);
+it is dropped, so that removing an instantiation does not make every later kernel look different.
 
-usage: isa_diff.py OLD.s NEW.s [symbol prefix ...]     (listings: vmcnt_isa_check.device_asm(), or hipcc --cuda-device-only -S
-       with the flags of sejonggo_amd/build.py; add -DSGO_CONV4W_VARIANTS for the selectable schedule variants)
+usage: isa_diff.py OLD.s NEW.s [symbol prefix ...]     (listings: vmcnt_isa_check.device_asm(source="sgo_engine.hip"), or
+       hipcc --cuda-device-only -S with the flags of sejonggo_amd/build.py, run inside a sejonggo_amd/csrc-shaped tree because
+       sgo_common.hpp includes ../../include/sgo.h; add -DSGO_CONV4W_VARIANTS for the conv's selectable schedule variants)
 Without prefixes every kernel of OLD is compared; a kernel missing from NEW is reported and is no failure (retired variants).
 Exit status 1 if a kernel present in both differs."""
 import re

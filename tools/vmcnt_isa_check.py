@@ -19,14 +19,23 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def device_asm(extra_flags=()):
-    """Device assembly of csrc/sgo_conv.hip for gfx950 (a few seconds); None without hipcc."""
+def build_cflags():
+    """CFLAGS of sejonggo_amd/build.py (the flags libsgo_hip.so is compiled with), read without importing the package."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("sgo_build", os.path.join(ROOT, "sejonggo_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(mod.CFLAGS)
+
+
+def device_asm(extra_flags=(), source="sgo_conv.hip"):
+    """Device assembly of csrc/<source> for gfx950 with build.py's flags (a few seconds); None without hipcc."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         return None
-    out = os.path.join(tempfile.mkdtemp(prefix="sgo_isa_"), "sgo_conv.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
-           "--cuda-device-only", "-S", "-o", out, os.path.join(ROOT, "sejonggo_amd", "csrc", "sgo_conv.hip")] + list(extra_flags)
+    out = os.path.join(tempfile.mkdtemp(prefix="sgo_isa_"), os.path.splitext(source)[0] + ".s")
+    cmd = [hipcc] + build_cflags() + ["-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", out,
+                                      os.path.join(ROOT, "sejonggo_amd", "csrc", source)] + list(extra_flags)
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
     return open(out).read()
 
