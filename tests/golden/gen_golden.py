@@ -507,6 +507,247 @@ def child_puct_ties(out):
     print("puct_ties: %d bytes" % os.path.getsize(out))
 
 
+
+# ---- constructed rule positions (rule_shapes_S*.npz) -----------------------------------------------------------------------
+# Positions that playouts do not reach, built as board tensors and handed to the reference: flood fills of ~S*S/2 steps,
+# the shortcut branches of the legal-set kernels (empty points without an empty neighbour, here "c points"), captures and
+# suicides of half a board, ko histories with 0 / 1 / 2 vanished stones.  tests/rule_shapes.py restates the kernels'
+# fill and measures the reach; tests/test_rule_shapes.py and tests/test_gpu_rule_shapes.py consume the files.
+RULE_SHAPES_DENSE = {5: 24, 7: 24, 9: 19, 13: 12, 19: 8}      # seeded dense boards per size (the file-size budget is cut here)
+RULE_SHAPES_MAX_BYTES = 84287                                    # the size of rules_S19.npz
+
+
+def _rs_serpentine(n):
+    """Column serpentine on an n x n board (n odd): columns 0, 2, 4, ... full, joined alternately at the bottom and the top.
+    Returns the cells in path order, (row, col)."""
+    path = []
+    for k, c in enumerate(range(0, n, 2)):
+        rows = range(n) if k % 2 == 0 else range(n - 1, -1, -1)
+        path += [(r, c) for r in rows]
+        if c + 2 < n:
+            path.append((n - 1 if k % 2 == 0 else 0, c + 1))
+    return path
+
+
+def _rs_groups(rb):
+    """[(colour, stones, liberties)] of a plain board (+1 / -1 / 0)."""
+    n = len(rb)
+    seen, out = set(), []
+    for r0 in range(n):
+        for c0 in range(n):
+            if rb[r0][c0] == 0 or (r0, c0) in seen:
+                continue
+            col, stones, libs, stack = rb[r0][c0], [], set(), [(r0, c0)]
+            seen.add((r0, c0))
+            while stack:
+                r, c = stack.pop()
+                stones.append((r, c))
+                for rr, cc in ((r - 1, c), (r + 1, c), (r, c - 1), (r, c + 1)):
+                    if not (0 <= rr < n and 0 <= cc < n):
+                        continue
+                    if rb[rr][cc] == 0:
+                        libs.add((rr, cc))
+                    elif rb[rr][cc] == col and (rr, cc) not in seen:
+                        seen.add((rr, cc))
+                        stack.append((rr, cc))
+            out.append((col, stones, libs))
+    return out
+
+
+def _rs_shapes(S, rng):
+    """[(name, board, variants)]: boards with black (+1) as the shape's colour; variants: 't' also transposed (row form),
+    'k' gets ko histories."""
+    import numpy as np
+    out = []
+    path = _rs_serpentine(S)
+    on = np.zeros((S, S), dtype=bool)
+    for r, c in path:
+        on[r, c] = True
+
+    def nb(r, c, n=S):
+        return [(rr, cc) for rr, cc in ((r - 1, c), (r + 1, c), (r, c - 1), (r, c + 1)) if 0 <= rr < n and 0 <= cc < n]
+
+    # serpentine group, the gaps empty: alive through every gap
+    rb = np.zeros((S, S), dtype=np.int8)
+    rb[on] = 1
+    out.append(("serp_open", rb, "t"))
+    # the gaps filled by the opponent, one empty point per gap (a c point shared by the serpentine and the gap's stones);
+    # the serpentine's last two stones taken off: its only liberties with an empty neighbour are at that far end
+    rb = np.where(on, 1, -1).astype(np.int8)
+    for r, c in path[-2:]:
+        rb[r, c] = 0
+    for k, c in enumerate(range(1, S, 2)):
+        cells = [r for r in range(S) if not on[r, c]]
+        if c == S - 2:                        # the last gap: next to its connector, away from the two points taken off
+            rb[cells[-1] if on[S - 1, c] else cells[0], c] = 0
+        else:
+            rb[cells[(3 * k + 1) % len(cells)], c] = 0
+    out.append(("serp_tight", rb, "tk"))
+    # ringed serpentine: the (S-2)-serpentine inside a ring of the opponent, who also fills the gaps and lives on a corner eye;
+    # one liberty (capture / suicide of the whole group) and two liberties (both c points)
+    inner = [(r + 1, c + 1) for r, c in _rs_serpentine(S - 2)]
+    base = -np.ones((S, S), dtype=np.int8)
+    for r, c in inner:
+        base[r, c] = 1
+    base[0, 0] = 0
+
+    def c_liberty(rb, cell, avoid):
+        for r, c in nb(*cell):
+            if rb[r, c] == -1 and (r, c) not in avoid and all(rb[p] != 0 and p not in avoid for p in nb(r, c)):
+                return (r, c)
+        raise AssertionError("no c point next to %s" % (cell,))
+
+    l1 = c_liberty(base, inner[-1], [])
+    l2 = c_liberty(base, inner[0], [l1])
+    rb = base.copy()
+    rb[l1] = 0
+    out.append(("ring_1lib", rb, "tk"))
+    rb = rb.copy()
+    rb[l2] = 0
+    out.append(("ring_2lib", rb, "tk"))
+    # four groups, one point: white arms (two stones up / down where they fit, one left / right) around p, walled by black
+    mid = S // 2
+    for where, p in (("centre", (mid, mid)), ("edge", (0, mid)), ("corner", (0, 0)), ("corner2", (S - 1, S - 1))):
+        rb = np.zeros((S, S), dtype=np.int8)
+        arms = []
+        for dr, dc, ln in ((-1, 0, 2), (1, 0, 2), (0, -1, 1), (0, 1, 1)):
+            arm = [(p[0] + dr * i, p[1] + dc * i) for i in range(1, ln + 1)]
+            arm = [q for q in arm if 0 <= q[0] < S and 0 <= q[1] < S]
+            if arm:
+                arms.append(arm)
+                for q in arm:
+                    rb[q] = -1
+        for arm in arms:
+            for q in arm:
+                for r, c in nb(*q):
+                    if rb[r, c] == 0 and (r, c) != p:
+                        rb[r, c] = 1
+        out.append(("four_%s" % where, rb, "k" if where == "centre" else ""))
+        # one arm keeps an outside liberty: p is shared by capturable groups and one that is not; for white p joins the arms alive
+        rb = rb.copy()
+        q = arms[0][-1]
+        r, c = [x for x in nb(*q) if rb[x] == 1][0]
+        rb[r, c] = 0
+        out.append(("four_%s_open" % where, rb, ""))
+    # empty corridors for the score: the serpentine left empty between walls of one colour
+    rb = np.where(on, 0, 1).astype(np.int8)
+    out.append(("corr_walled", rb, "t"))
+    rb = rb.copy()
+    rb[path[-1]] = -1
+    out.append(("corr_enemy_end", rb, "t"))
+    # the corridor meets the other colour only at its far end: the wall stone next to its last cell is white
+    rb = np.where(on, 0, 1).astype(np.int8)
+    q = [x for x in nb(*path[-1]) if not on[x]][0]
+    rb[q] = -1
+    out.append(("corr_both_at_end", rb, "t"))
+    out.append(("empty", np.zeros((S, S), dtype=np.int8), ""))
+    rb = np.ones((S, S), dtype=np.int8)
+    rb[S - 1, 0] = 0                          # one colour everywhere; a group needs a liberty, so one point stays empty
+    out.append(("full_but_one", rb, ""))
+    # seeded dense boards, zero-liberty groups stripped
+    for i in range(RULE_SHAPES_DENSE[S]):
+        frac = (0.03, 0.06, 0.10, 0.20)[i % 4]
+        share = rng.uniform(0.3, 0.7)
+        u = rng.rand(S, S)
+        rb = np.where(u < frac, 0, np.where(rng.rand(S, S) < share, 1, -1)).astype(np.int8)
+        if not (rb == 0).any():
+            rb[rng.randint(S), rng.randint(S)] = 0
+        for col, stones, libs in _rs_groups(rb.tolist()):
+            if not libs:
+                for q in stones:
+                    rb[q] = 0
+        out.append(("dense%02d_%02d" % (i, int(frac * 100)), rb, "k" if i % 2 == 0 else ""))
+    return out
+
+
+def child_rule_shapes(size, out):
+    import numpy as np
+    _setup_reference(size, 8, 8)
+    import play
+    S, N, A = size, size * size, size * size + 1
+    rng = np.random.RandomState(777 + size)
+    shapes = _rs_shapes(S, rng)
+    boards = []                                   # (name, plain board)
+    for name, rb, var in shapes:
+        forms = [("", rb)] + ([("_T", rb.T.copy())] if "t" in var else [])
+        for sfx, b in forms:
+            boards.append((name + sfx, b, var))
+            if (b != 0).any():              # the colour mirror (of a dense board: without ko histories of its own)
+                boards.append((name + sfx + "_w", (-b).astype(np.int8), "" if name.startswith("dense") else var))
+    positions = []                                # (name, plain board, to_play, gone mask)
+    for name, b, var in boards:
+        for tp in (1, -1):
+            positions.append((name + ("_b" if tp == 1 else "_wtm"), b, tp, np.zeros((S, S), dtype=bool), "k" in var))
+
+    def tensor(b, tp, gone):
+        t = np.zeros((1, S, S, 17), dtype=np.int32)
+        own, opp = (b == tp), (b == -tp)
+        t[0, :, :, 0], t[0, :, :, 1] = own, opp
+        t[0, :, :, 2], t[0, :, :, 3] = own | gone, opp
+        t[0, :, :, 16] = tp
+        return t
+
+    # ko histories: 1 and 2 of the mover's stones vanished on the last ply, on points that are legal without the history
+    extra = []
+    for name, b, tp, gone, with_ko in positions:
+        if not with_ko:
+            continue
+        mask = np.asarray(play.legal_moves(tensor(b, tp, gone))).astype(np.uint8)[:N]
+        cand = np.flatnonzero(mask == 0)
+        if len(cand) < 2:
+            cand = np.flatnonzero(b.reshape(-1) == 0)
+        for k in (1, 2):
+            if len(cand) < k:
+                continue
+            g = np.zeros(N, dtype=bool)
+            g[rng.choice(cand, size=k, replace=False)] = True
+            extra.append(("%s_ko%d" % (name, k), b, tp, g.reshape(S, S), False))
+    positions += extra
+
+    planes = np.zeros((len(positions), 4, (N + 7) // 8), dtype=np.uint8)
+    colour = np.zeros(len(positions), dtype=np.int8)
+    legal = np.zeros((len(positions), (A + 7) // 8), dtype=np.uint8)
+    winner = np.zeros((len(positions), 3), dtype=np.float64)
+    p_pos, p_a, p_col, p_mover, p_hash, p_lhash = [], [], [], [], [], []
+    for pi, (name, b, tp, gone, _) in enumerate(positions):
+        groups = _rs_groups(b.tolist())
+        assert all(libs for _, _, libs in groups), name                          # validity 1: every group has a liberty
+        t = tensor(b, tp, gone)
+        own, prev = t[0, :, :, 0] != 0, t[0, :, :, 2] != 0
+        assert (prev >= own).all() and not ((prev & ~own) & (b != 0)).any(), name  # validity 2: the history plane
+        for k in range(4):
+            planes[pi, k] = np.packbits(t[0, :, :, k].reshape(-1).astype(np.uint8))
+        colour[pi] = tp
+        legal[pi] = np.packbits(np.asarray(play.legal_moves(t)).astype(np.uint8))
+        winner[pi] = play.get_winner(t)
+        empties = np.flatnonzero(b.reshape(-1) == 0)
+        if len(empties) <= 24:
+            pts = set(int(a) for a in empties)
+        else:
+            pts = set(int(a) for a in rng.choice(empties, size=24, replace=False))
+            for _, _, libs in groups:
+                if len(libs) == 1:
+                    pts |= set(r * S + c for r, c in libs)
+        for a in sorted(pts):
+            for col in (0, -tp):
+                t2 = np.copy(t)
+                _, mover = play.make_play(a % S, a // S, t2, None if col == 0 else col)
+                p_pos.append(pi); p_a.append(a); p_col.append(col); p_mover.append(int(mover))
+                p_hash.append(_sha8(t2))
+                p_lhash.append(_sha8(np.asarray(play.legal_moves(t2)).astype(np.uint8))[:4])
+    data = {"size": np.array(S, dtype=np.int32), "komi": np.array(5.5),
+            "names": np.frombuffer("\n".join(p[0] for p in positions).encode(), dtype=np.uint8),
+            "planes": planes, "colour": colour, "legal": legal, "winner": winner,
+            "play_pos": np.array(p_pos, dtype=np.int16), "play_a": np.array(p_a, dtype=np.int16),
+            "play_colour": np.array(p_col, dtype=np.int8), "play_mover": np.array(p_mover, dtype=np.int8),
+            "play_hash": np.array(p_hash, dtype=np.uint8).reshape(-1, 8),
+            "play_legal_hash": np.array(p_lhash, dtype=np.uint8).reshape(-1, 4)}
+    np.savez_compressed(out, **data)
+    size_b = os.path.getsize(out)
+    print("rule_shapes S=%d: %d positions, %d plays, %d bytes" % (S, len(positions), len(p_pos), size_b))
+    assert size_b <= RULE_SHAPES_MAX_BYTES, size_b
+
+
 def _tree_hash(root):
     """Canonical serialisation: pre-order, ascending action; per child
     <i action, i count, f value, f mean_value, d p, i virtual_loss, i expanded>."""
@@ -1210,6 +1451,8 @@ def main():
             child_puct_ties(a.child[1])
         elif what == "units":
             child_units(a.child[1])
+        elif what == "rule_shapes":
+            child_rule_shapes(int(a.child[1]), a.child[2])
         elif what == "gtp":
             child_gtp(a.child[1])
         elif what == "sync":
@@ -1227,6 +1470,9 @@ def main():
     if only in (None, "rules", "seeded_rules"):
         for s, seed in SEEDED_RULES_CASES:
             run_child(["rules", s, os.path.join(HERE, "rules_S%d_seed%d.npz" % (s, seed))], scratch, SGO_GOLDEN_SEED=str(seed))
+    if only in (None, "rule_shapes"):
+        for s in (5, 7, 9, 13, 19):
+            run_child(["rule_shapes", s, os.path.join(HERE, "rule_shapes_S%d.npz" % s)], scratch)
     if only in (None, "entry"):
         entry_imports(os.path.join(HERE, "main_selfplay_imports.json"))
     if only in (None, "sgf"):
