@@ -301,6 +301,17 @@ int sgo_debug_counters(sgo_ctx *ctx, unsigned long long *out, int n);
  * the root blocks of all slots are overwritten. */
 int sgo_debug_top_one(sgo_ctx *ctx, int n_cases, const float *P32, const double *P64, const int32_t *N, const float *Q,
                       const int8_t *busy, const uint8_t *legal, int f64, int32_t *out, void *stream);
+/* Test hooks (tests/block_audit.py): the raw tree-block accounting, copied to HOST buffers and not interpreted.  Both
+ * synchronise the device.  Every array pointer may be NULL; a first call with hdr alone gives the sizes.
+ * Slot: hdr[20] = {phase, error, root_blk, other_root, free_top, min_free, ovf_hi, fifo_head, fifo_tail, cap, L, ovf_cap, APAD,
+ * NW, E, rows, A, F = FIFO ring length, 0, 0}; free_list[L]; ovf_map[ovf_cap]; per local id of [0, rows): b_parent[rows],
+ * b_slot[rows], c_b[rows][APAD], legal[rows][NW], where rows = cap + 1 + the highest backed overflow index (rows of overflow
+ * ids that are not backed are left as the caller filled them); fifo[4][F] = the ring arrays parent, slot, block, evaluated.
+ * A failed slot gives hdr (rows = 0) and ovf_map only.
+ * Context: hdr[4] = {top of the free stack, returned entries, low-water mark, pool blocks}; pool_free / pool_ret[pool blocks]. */
+int sgo_debug_block_state(sgo_ctx *ctx, int slot, int32_t *hdr, int32_t *free_list, int32_t *ovf_map, int32_t *b_parent,
+                          int32_t *b_slot, int32_t *c_b, uint32_t *legal, int32_t *fifo);
+int sgo_debug_pool_state(sgo_ctx *ctx, int32_t *hdr, int32_t *pool_free, int32_t *pool_ret);
 
 /* average duration (ms) and launch count of the board_advance kernel inside sgo_step since the last
  * call (HIP events on the step's stream); used by bench.py for the roofline object */

@@ -279,3 +279,7 @@ class Game(object):
         buf = np.zeros(sz, dtype=np.uint8)
         lib().ora_game_tree_serialize(self._g, _p(buf), C.c_size_t(sz), C.byref(nn), C.byref(ne))
         return buf, nn.value, ne.value
+
+    def tree_depth(self):
+        """Links from the root to the deepest expanded node of the current tree (0: the root alone, -1: no tree)."""
+        return int(lib().ora_game_tree_depth(self._g))

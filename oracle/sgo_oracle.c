@@ -895,6 +895,17 @@ static size_t ser_rec(const ONode *n, int A, uint8_t *buf, size_t cap, size_t of
     }
     return off;
 }
+/* Links from the root to the deepest EXPANDED node (a node with a child table: one tree block of the engine); 0 = the root
+ * alone, -1 = no tree. */
+static int depth_rec(const ONode *n, int A) {
+    int d = 0;
+    for (int a = 0; a < A; a++) {
+        const ONode *c = n->child[a];
+        if (c && c->child) { const int e = 1 + depth_rec(c, A); if (e > d) d = e; }
+    }
+    return d;
+}
+int ora_game_tree_depth(const OraGame *g) { return (g->tree && g->tree->child) ? depth_rec(g->tree, g->A) : -1; }
 size_t ora_game_tree_serialize(const OraGame *g, uint8_t *buf, size_t cap, long *n_nodes, long *n_expanded) {
     long nn = 0, ne = 0;
     size_t off = 0;

@@ -1,7 +1,7 @@
 // sgo_engine_inspect.hpp -- HOST code used by tests and tools only; nothing here runs in a step.  Included at the end of
 // sgo_engine.hip (it needs sgo_ctx and the kernels).  A snapshot of one game's blocks walked on the host (sgo_root_table,
-// sgo_tree_serialize, sgo_tree_dump, sgo_game_board) and the debug entry points (sgo_debug_counters, sgo_debug_top_one,
-// sgo_advance_timing).
+// sgo_tree_serialize, sgo_tree_dump, sgo_game_board), the raw block-accounting dumps (sgo_debug_block_state,
+// sgo_debug_pool_state) and the debug entry points (sgo_debug_counters, sgo_debug_top_one, sgo_advance_timing).
 #pragma once
 
 extern "C" {
@@ -57,6 +57,63 @@ static int snapshot(Ctx &c, int g, Snap &sn) {
 }
 static bool snap_exists(const Ctx &c, const Snap &sn, int blk, int i) {
     return (sn.legal[(size_t)blk * c.NW + (i >> 5)] >> (i & 31)) & 1u;
+}
+
+/* Test hooks (tests/block_audit.py): the raw tree-block accounting of one slot and of the context, copied and not interpreted.
+ * hdr[20] = {phase, error, root_blk, other_root, free_top, min_free, ovf_hi, fifo_head, fifo_tail, cap, L, ovf_cap, APAD, NW, E,
+ * rows, A, 2 * MAXE, 0, 0}; rows = cap + hi block rows follow (hi as in snapshot(): 1 + the highest backed map index), 0 for a
+ * failed slot, whose block arrays are left out.  Any array pointer may be NULL (a first call with hdr alone gives the sizes);
+ * rows of overflow ids that are not backed are left as the caller filled them. */
+int sgo_debug_block_state(sgo_ctx *x, int slot, int32_t *hdr, int32_t *free_list, int32_t *ovf_map, int32_t *b_parent,
+                          int32_t *b_slot, int32_t *c_b, uint32_t *legal, int32_t *fifo) {
+    if (!x || slot < 0 || slot >= x->c.G || !hdr) { set_error("sgo_debug_block_state: bad argument"); return SGO_ERR_ARG; }
+    Ctx &c = x->c;
+    SGO_HIP(hipDeviceSynchronize());
+    GameState s;
+    SGO_HIP(hipMemcpy(&s, c.gs + slot, sizeof s, hipMemcpyDeviceToHost));
+    std::vector<int32_t> ovf;
+    CK(ovf_row(c, slot, ovf));
+    int hi = 0;
+    for (int j = 0; j < c.ovf_cap; j++)
+        if (ovf[j] >= 0) hi = j + 1;
+    const int rows = s.error ? 0 : c.cap + hi;
+    auto backed = [&](int j) { return ovf[j] >= 0 && ovf[j] < c.pool_blocks; };   // a map entry beyond the pool has no row to copy
+    const int32_t h[20] = {s.phase, s.error, s.root_blk, s.other_root, s.free_top, s.min_free, s.ovf_hi, s.fifo_head, s.fifo_tail,
+                           c.cap, c.L, c.ovf_cap, c.APAD, c.NW, c.E, rows, c.A, 2 * MAXE, 0, 0};
+    memcpy(hdr, h, sizeof h);
+    if (ovf_map && c.ovf_cap > 0) memcpy(ovf_map, ovf.data(), sizeof(int32_t) * c.ovf_cap);
+    if (s.error) return SGO_OK;
+    if (free_list) SGO_HIP(hipMemcpy(free_list, c.freeList + (size_t)slot * c.L, sizeof(int32_t) * c.L, hipMemcpyDeviceToHost));
+    auto pull = [&](size_t dst, size_t src, size_t n) -> int {
+        if (b_parent) SGO_HIP(hipMemcpy(b_parent + dst, c.bParent + src, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        if (b_slot) SGO_HIP(hipMemcpy(b_slot + dst, c.bSlot + src, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        if (c_b) SGO_HIP(hipMemcpy(c_b + dst * c.APAD, c.cB + src * c.APAD, sizeof(int32_t) * n * c.APAD, hipMemcpyDeviceToHost));
+        if (legal) SGO_HIP(hipMemcpy(legal + dst * c.NW, c.legal + src * c.NW, sizeof(uint32_t) * n * c.NW, hipMemcpyDeviceToHost));
+        return SGO_OK;
+    };
+    const bool want_rows = b_parent || b_slot || c_b || legal;
+    if (want_rows) CK(pull(0, (size_t)slot * c.cap, c.cap));
+    // every backed overflow block on its own, as snapshot() does
+    for (int j = 0; want_rows && j < hi; j++)
+        if (backed(j)) CK(pull((size_t)c.cap + j, (size_t)c.G * c.cap + ovf[j], 1));
+    if (fifo) {                                            // [4][2 * MAXE]: fParent, fSlot, fBlk, fEvaluated
+        const int32_t *src[4] = {c.fParent, c.fSlot, c.fBlk, c.fEvaluated};
+        for (int k = 0; k < 4; k++)
+            SGO_HIP(hipMemcpy(fifo + (size_t)k * 2 * MAXE, src[k] + (size_t)slot * 2 * MAXE, sizeof(int32_t) * 2 * MAXE, hipMemcpyDeviceToHost));
+    }
+    return SGO_OK;
+}
+
+/* hdr[4] = {poolCtl[0], poolCtl[1], poolCtl[2], pool_blocks}; pool_free / pool_ret (pool_blocks entries each) may be NULL */
+int sgo_debug_pool_state(sgo_ctx *x, int32_t *hdr, int32_t *pool_free, int32_t *pool_ret) {
+    if (!x || !hdr) { set_error("sgo_debug_pool_state: bad argument"); return SGO_ERR_ARG; }
+    Ctx &c = x->c;
+    SGO_HIP(hipDeviceSynchronize());
+    SGO_HIP(hipMemcpy(hdr, c.poolCtl, sizeof(int32_t) * 3, hipMemcpyDeviceToHost));
+    hdr[3] = (int32_t)c.pool_blocks;
+    if (pool_free && c.pool_blocks > 0) SGO_HIP(hipMemcpy(pool_free, c.poolFree, sizeof(int32_t) * c.pool_blocks, hipMemcpyDeviceToHost));
+    if (pool_ret && c.pool_blocks > 0) SGO_HIP(hipMemcpy(pool_ret, c.poolRet, sizeof(int32_t) * c.pool_blocks, hipMemcpyDeviceToHost));
+    return SGO_OK;
 }
 
 int sgo_root_table(sgo_ctx *x, int slot, int32_t *N, float *W, float *Q, double *P, int8_t *EX, int32_t *root_count,

@@ -549,6 +549,52 @@ class SelfPlayEngine(object):
         return {"private_per_game": int(out[0]), "ids_per_game": int(out[1]), "shared_blocks": int(out[2]),
                 "shared_free": int(out[3]), "shared_free_low_water": int(out[4]), "games": int(out[5])}
 
+    _BLOCK_HDR = ("phase", "error", "root_blk", "other_root", "free_top", "min_free", "ovf_hi", "fifo_head", "fifo_tail",
+                  "cap", "L", "ovf_cap", "APAD", "NW", "E", "rows", "A", "F")
+
+    def block_state(self, slot, blocks=True):
+        """Test hook: the raw block accounting of one slot (sgo_debug_block_state), uninterpreted.  Scalars by name, then
+        freeList [L], ovfMap [ovf_cap], and for the local ids [0, rows): bParent, bSlot, cB [rows][APAD], legal [rows][NW]
+        (rows of overflow ids that are not backed hold -9 / 0), and the FIFO rings fParent, fSlot, fBlk, fEvaluated [F].
+        A failed slot has rows == 0 and only the scalars and the map.  blocks=False leaves the per-block arrays and the
+        FIFO out (scalars, free stack and map row only: one small copy each)."""
+        hdr = np.zeros(20, np.int32)
+        z = [None] * 7
+        _lib.check(self.lib.sgo_debug_block_state(self.ctx, C.c_int(slot), _lib.ptr(hdr), *z), "sgo_debug_block_state")
+        d = dict(zip(self._BLOCK_HDR, (int(v) for v in hdr)))
+        rows, F = d["rows"], d["F"]
+        d["freeList"] = np.full(d["L"], -9, np.int32)
+        d["ovfMap"] = np.full(max(1, d["ovf_cap"]), -1, np.int32)
+        if not blocks:
+            _lib.check(self.lib.sgo_debug_block_state(self.ctx, C.c_int(slot), _lib.ptr(hdr), _lib.ptr(d["freeList"]),
+                                                      _lib.ptr(d["ovfMap"]), None, None, None, None, None), "sgo_debug_block_state")
+            d["ovfMap"] = d["ovfMap"][:d["ovf_cap"]]
+            return d
+        d["bParent"] = np.full(max(1, rows), -9, np.int32)
+        d["bSlot"] = np.full(max(1, rows), -9, np.int32)
+        d["cB"] = np.full((max(1, rows), d["APAD"]), -9, np.int32)
+        d["legal"] = np.zeros((max(1, rows), d["NW"]), np.uint32)
+        fifo = np.zeros((4, F), np.int32)
+        _lib.check(self.lib.sgo_debug_block_state(self.ctx, C.c_int(slot), _lib.ptr(hdr), _lib.ptr(d["freeList"]),
+                                                  _lib.ptr(d["ovfMap"]), _lib.ptr(d["bParent"]), _lib.ptr(d["bSlot"]),
+                                                  _lib.ptr(d["cB"]), _lib.ptr(d["legal"]), _lib.ptr(fifo)),
+                   "sgo_debug_block_state")
+        assert int(hdr[15]) == rows, "the slot changed between the two calls of block_state"
+        d["ovfMap"] = d["ovfMap"][:d["ovf_cap"]]
+        for k in ("bParent", "bSlot", "cB", "legal"):
+            d[k] = d[k][:rows]
+        d["fParent"], d["fSlot"], d["fBlk"], d["fEvaluated"] = fifo
+        return d
+
+    def pool_state(self):
+        """Test hook: the shared pool's control words and both of its lists (sgo_debug_pool_state), uninterpreted."""
+        hdr = np.zeros(4, np.int32)
+        _lib.check(self.lib.sgo_debug_pool_state(self.ctx, _lib.ptr(hdr), None, None), "sgo_debug_pool_state")
+        n = int(hdr[3])
+        pf, pr = np.full(max(1, n), -9, np.int32), np.full(max(1, n), -9, np.int32)
+        _lib.check(self.lib.sgo_debug_pool_state(self.ctx, _lib.ptr(hdr), _lib.ptr(pf), _lib.ptr(pr)), "sgo_debug_pool_state")
+        return {"poolCtl": [int(v) for v in hdr[:3]], "pool_blocks": n, "poolFree": pf[:n], "poolRet": pr[:n]}
+
     def set_halt(self, slot, move_n):
         _lib.check(self.lib.sgo_set_halt(self.ctx, C.c_int(slot), C.c_int(move_n)), "sgo_set_halt")
 
@@ -713,6 +759,13 @@ class DualEngine(object):
 
     def pool_info(self):
         return [e.pool_info() for e in self.halves]
+
+    def block_state(self, slot, blocks=True):
+        e, local = self._half_of(slot)
+        return e.block_state(local, blocks)
+
+    def pool_state(self):
+        return [e.pool_state() for e in self.halves]
 
     def advance_timing(self):
         t = [e.advance_timing() for e in self.halves]

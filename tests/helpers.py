@@ -170,3 +170,54 @@ def read_sample(path):
             return r['board'], r['policy_target'], r['value_target']
     with mod.File(path, "r") as f:
         return f['board'][...], f['policy_target'][...], f['value_target'][()]
+
+
+class PackedProbe(object):
+    """A stub net behind the resident net's PACKED-RECORD input contract (engine route: net.predict_packed -> sgo_stem_packed_dev),
+    built so that the evaluation stays rounding-free: the real stem kernel runs with 0/1 weights that copy plane c of tap t into
+    output channel 16 t + c (and the colour term into channel 144), the full S x S x 17 board tensor is re-assembled from those
+    (S-2)^2 x 145 values -- every board point is under some tap of some output pixel -- and handed to the hash net.  Any wrong bit,
+    tap, symmetry, colour flip or list index in the kernel changes the game."""
+    packed_ok = True
+
+    def __init__(self, net, S):
+        import torch
+        from sejonggo_amd import _lib
+        self.net, self.name, self.S, self.t = net, net.name, S, S - 2
+        self._lib, self.lib = _lib, _lib.require_gpu()
+        w10 = torch.zeros(256, 10, 16)
+        for t in range(9):
+            for c in range(16):
+                w10[16 * t + c, t, c] = 1.0
+        self.w10 = w10.half().cuda().contiguous()
+        self.bias = torch.zeros(256, dtype=torch.float16, device="cuda")
+        wcol = torch.zeros(256)
+        wcol[144] = 1.0                                   # relu(+1) = 1 black to play, relu(-1) = 0 white to play
+        self.wcol = wcol.cuda().contiguous()
+        ys = torch.arange(S)
+        o = (ys - 1).clamp(0, S - 3)                      # an output pixel row whose window covers board row y, and the tap row
+        d = ys - o
+        self.oy, self.ox = o.cuda()[:, None].expand(S, S), o.cuda()[None, :].expand(S, S)
+        self.tap = (d[:, None] * 3 + d[None, :]).cuda()
+
+    def predict_packed(self, records_ptr, index_ptr, n, k=0, k_dev_ptr=None):
+        import torch
+        S, t = self.S, self.t
+        y = torch.full((n, t, t, 256), 7.0, dtype=torch.float16, device="cuda")
+        self._lib.check(self.lib.sgo_stem_packed_dev(S, n, records_ptr, index_ptr, int(k), k_dev_ptr, self.w10.data_ptr(),
+                                                     self.bias.data_ptr(), self.wcol.data_ptr(), y.data_ptr(),
+                                                     torch.cuda.current_stream().cuda_stream), "sgo_stem_packed_dev")
+        capturing = torch.cuda.is_current_stream_capturing()      # captured rounds: no host read-backs inside the graph
+        if not capturing:
+            assert float(y[..., 145:].abs().max()) == 0.0
+        g = y[:, self.oy, self.ox, :]                                                  # [n, S, S, 256]
+        ch = (self.tap[..., None] * 16 + torch.arange(16, device="cuda"))[None].expand(n, S, S, 16)
+        planes = torch.gather(g, 3, ch)
+        col = (2.0 * y[:, 0, 0, 144] - 1.0)[:, None, None, None].expand(n, S, S, 1)
+        X = torch.cat([planes, col.to(planes.dtype)], dim=3)
+        if not capturing:
+            assert bool(((X[..., :16] == 0) | (X[..., :16] == 1)).all())
+        return self.net.predict_on_batch(X)
+
+    def predict_on_batch(self, X):
+        raise AssertionError("the engine must take the packed-record route for this net")

@@ -8,7 +8,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from tests.helpers import load, sha8, ASYNC_FILES, TWO_MODEL_FILES
+from tests.helpers import load, sha8, ASYNC_FILES, TWO_MODEL_FILES, PackedProbe as _PackedProbe
 
 pytestmark = pytest.mark.gpu
 
@@ -255,6 +255,15 @@ def test_headline_batch_shape_from_the_shared_pool(L):
     held = sum(max(0, int(r["blocks_high_water"]) - 10) for r in res)         # an upper bound of what the games still hold
     assert info["shared_blocks"] == pool and 0 < info["shared_free_low_water"] <= info["shared_free"] <= pool
     assert pool - info["shared_free"] <= held                                 # nothing leaked: blocks out of the pool are in trees
+    # ... exactly: every shared block is on the free stack, on the return list or behind one overflow id of one of the 1 024
+    # games, and on the sampled slots free stack, child links, parent view and FIFO describe one set of blocks
+    from tests import block_audit as BA
+    sampled = [0, 1, 63, 64, 500, 777, 1023]
+    dumps, pstate = BA.dump_engine(eng, full=sampled)
+    assert len(dumps) == G and pstate["pool_blocks"] == pool
+    v = BA.audit(dumps, pstate)
+    assert v == [], v[:10]
+    assert sum(int(np.sum(d["ovfMap"] >= 0)) for d in dumps.values()) == pool - info["shared_free"] > 0
     eng.start_games(np.arange(G), noises=noises, uniforms=uni)                # restarts hand everything back
     eng.step()
     assert eng.pool_info()["shared_free"] == pool
@@ -393,57 +402,6 @@ class _SymNet(object):
             pol = pol / np.float32(len(self.ks))
             val = val / np.float32(len(self.ks))
         return pol, val
-
-
-class _PackedProbe(object):
-    """A stub net behind the resident net's PACKED-RECORD input contract (engine route: net.predict_packed -> sgo_stem_packed_dev),
-    built so that the evaluation stays rounding-free: the real stem kernel runs with 0/1 weights that copy plane c of tap t into
-    output channel 16 t + c (and the colour term into channel 144), the full S x S x 17 board tensor is re-assembled from those
-    (S-2)^2 x 145 values -- every board point is under some tap of some output pixel -- and handed to the hash net.  Any wrong bit,
-    tap, symmetry, colour flip or list index in the kernel changes the game."""
-    packed_ok = True
-
-    def __init__(self, net, S):
-        import torch
-        from sejonggo_amd import _lib
-        self.net, self.name, self.S, self.t = net, net.name, S, S - 2
-        self._lib, self.lib = _lib, _lib.require_gpu()
-        w10 = torch.zeros(256, 10, 16)
-        for t in range(9):
-            for c in range(16):
-                w10[16 * t + c, t, c] = 1.0
-        self.w10 = w10.half().cuda().contiguous()
-        self.bias = torch.zeros(256, dtype=torch.float16, device="cuda")
-        wcol = torch.zeros(256)
-        wcol[144] = 1.0                                   # relu(+1) = 1 black to play, relu(-1) = 0 white to play
-        self.wcol = wcol.cuda().contiguous()
-        ys = torch.arange(S)
-        o = (ys - 1).clamp(0, S - 3)                      # an output pixel row whose window covers board row y, and the tap row
-        d = ys - o
-        self.oy, self.ox = o.cuda()[:, None].expand(S, S), o.cuda()[None, :].expand(S, S)
-        self.tap = (d[:, None] * 3 + d[None, :]).cuda()
-
-    def predict_packed(self, records_ptr, index_ptr, n, k=0, k_dev_ptr=None):
-        import torch
-        S, t = self.S, self.t
-        y = torch.full((n, t, t, 256), 7.0, dtype=torch.float16, device="cuda")
-        self._lib.check(self.lib.sgo_stem_packed_dev(S, n, records_ptr, index_ptr, int(k), k_dev_ptr, self.w10.data_ptr(),
-                                                     self.bias.data_ptr(), self.wcol.data_ptr(), y.data_ptr(),
-                                                     torch.cuda.current_stream().cuda_stream), "sgo_stem_packed_dev")
-        capturing = torch.cuda.is_current_stream_capturing()      # captured rounds: no host read-backs inside the graph
-        if not capturing:
-            assert float(y[..., 145:].abs().max()) == 0.0
-        g = y[:, self.oy, self.ox, :]                                                  # [n, S, S, 256]
-        ch = (self.tap[..., None] * 16 + torch.arange(16, device="cuda"))[None].expand(n, S, S, 16)
-        planes = torch.gather(g, 3, ch)
-        col = (2.0 * y[:, 0, 0, 144] - 1.0)[:, None, None, None].expand(n, S, S, 1)
-        X = torch.cat([planes, col.to(planes.dtype)], dim=3)
-        if not capturing:
-            assert bool(((X[..., :16] == 0) | (X[..., :16] == 1)).all())
-        return self.net.predict_on_batch(X)
-
-    def predict_on_batch(self, X):
-        raise AssertionError("the engine must take the packed-record route for this net")
 
 
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "captured_rounds"])
@@ -694,7 +652,8 @@ def test_golden_games_from_the_shared_block_pool(L, fn):
     assert gd["blocks_high_water"] > E + 2
     eng.start_games([0], noises=z["noises"][:1], uniforms=np.zeros((1, max(1, eng.max_moves))))
     eng.step()
-    assert eng.pool_info()["shared_free"] >= after["shared_blocks"] - 2               # ... and a restart hands all of it back
+    assert eng.pool_info()["shared_free"] >= after["shared_blocks"] - 2               # ... and a restart hands all of it back:
+    assert eng.pool_info()["shared_free"] == after["shared_blocks"]                   # the step has merged the returns
     eng.close()
     k = len(z["move_index"]) - 1
     eng = _engine(z, net, halt_at=k, **kw)
