@@ -9,6 +9,25 @@ from .conf import conf
 from .play import game_init, get_winner, index2coord, make_play, new_tree
 
 
+def game_result_fields(winner, end_reason, last_player, black_points, white_points, nameB, nameW, black_is_model1=True,
+                       async_winner_rule=False):
+    """The result fields of a game_data dict, for the host loop below and for the device engine alike.  winner: 1 black, -1
+    white, 0 draw; last_player: who a resignation is scored for.  A one-model game is the two-model form with nameB == nameW."""
+    tag = {1: "B", 0: "D", -1: "W"}
+    result = "%s+R" % tag[last_player] if end_reason == "resign" else "%s+%s" % (tag[winner], abs(black_points - white_points))
+    if winner == 0:
+        winner_model = None
+    elif async_winner_rule and conf.get('COMPAT_WINNER_MODEL', True):
+        # nomodel_self_play.py:247: `modelB_name if (winner == 1) == model1_isblack else modelW_name` -- right while model1
+        # plays black, the LOSER's name when model1 plays white (self_play.py:258 has the correct rule).  Reproduced behind
+        # conf['COMPAT_WINNER_MODEL'] because evaluate_worker.py:141 counts wins from this field.
+        winner_model = nameB if (winner == 1) == black_is_model1 else nameW
+    else:
+        winner_model = nameB if winner == 1 else nameW
+    return {'modelB_name': nameB, 'modelW_name': nameW, 'winner': {1: 1, -1: 0, 0: None}[winner], 'winner_model': winner_model,
+            'result': result, 'end_reason': end_reason}
+
+
 def play_loop(size, first, second, evaluate, choose, name_of, stop_exploration, self_play=False, num_moves=None,
               resign_first=None, resign_second=None, first_is_model1=True, async_winner_rule=False):
     """first/second: the handles (model objects or indicator strings) that play black/white.
@@ -50,19 +69,6 @@ def play_loop(size, first, second, evaluate, choose, name_of, stop_exploration, 
         current, other = other, current
         mcts_tree, other_mcts = other_mcts, mcts_tree
     winner, black_points, white_points = get_winner(board)
-    tag = {1: "B", 0: "D", -1: "W"}
-    result = "%s+R" % tag[player] if end_reason == "resign" else "%s+%s" % (tag[winner], abs(black_points - white_points))
-    nameB, nameW = name_of(first), name_of(second)
-    if winner == 0:
-        winner_model = None
-    elif async_winner_rule and conf.get('COMPAT_WINNER_MODEL', True):
-        # nomodel_self_play.py:247: `modelB_name if (winner == 1) == model1_isblack else modelW_name` -- right while model1
-        # plays black, the LOSER's name when model1 plays white (self_play.py:258 has the correct rule).  Reproduced behind
-        # conf['COMPAT_WINNER_MODEL'] because evaluate_worker.py:141 counts wins from this field.
-        winner_model = nameB if (winner == 1) == first_is_model1 else nameW
-    else:
-        winner_model = nameB if winner == 1 else nameW
     r1, r2 = (resign_first, resign_second) if first_is_model1 else (resign_second, resign_first)
-    return {'moves': moves, 'modelB_name': nameB, 'modelW_name': nameW, 'winner': {1: 1, -1: 0, 0: None}[winner],
-            'winner_model': winner_model, 'result': result, 'resign_model1': r1, 'resign_model2': r2,
-            'end_reason': end_reason}
+    return dict(game_result_fields(winner, end_reason, player, black_points, white_points, name_of(first), name_of(second),
+                                   first_is_model1, async_winner_rule), moves=moves, resign_model1=r1, resign_model2=r2)

@@ -69,6 +69,7 @@ def run_rank(backend="nccl", sync_every=4, max_steps=None):
     import torch.distributed as dist
     from concurrent.futures import ThreadPoolExecutor
     from .conf import conf
+    from ._slot_loop import SlotLoop
     from .distributed import TupleGather, broadcast_net, init_from_env, shard_games, tuple_dtype
     from .engine import SelfPlayEngine
     from .predicting_queue_worker import get_model, init_predicting_workers, put_name_request
@@ -88,82 +89,51 @@ def run_rank(backend="nccl", sync_every=4, max_steps=None):
     S = conf['SIZE']
     mine = shard_games(conf['N_GAMES'], world, rank)
     G = max(1, min(conf['GAMES_PER_GPU'], len(mine)))
-    sched = GameScheduler(conf['SELF_PLAY_DIR'], model_name, 0, conf['RESIGNATION_PERCENT'], conf['RESIGNATION_ALLOWED_ERROR'])
+    # the rank's own shard, minus the game numbers that already exist (the reference's resume rule); rank 0 alone writes
+    sched = GameScheduler(conf['SELF_PLAY_DIR'], model_name, conf['N_GAMES'], conf['RESIGNATION_PERCENT'],
+                          conf['RESIGNATION_ALLOWED_ERROR'], candidates=mine, create=False)
     eng = SelfPlayEngine(net, size=S, n_games=G, sims=conf['MCTS_SIMULATIONS'], energy=conf['ENERGY'],
                          stop_exploration=conf['STOP_EXPLORATION'], komi=conf['KOMI'], self_play=True,
                          symmetry=conf.get('SYMMETRY_MODE', 'random1'), device=local, seed=1000 + rank, raise_on_error=False,
                          num_moves=conf.get('NUM_MOVES'))
-    todo = list(mine)
-    slot_game, slot_resign = {}, {}
+    slot_resign = {}
+    outbox = []
 
-    def fill(slots):
-        start, res = [], []
-        for s in slots:
-            g = None
-            while todo:
-                cand = todo.pop(0)
-                if not os.path.isdir(os.path.join(conf['SELF_PLAY_DIR'], model_name, "game_%05d" % cand)):   # resume rule
-                    g = cand
-                    break
-            if g is None:
-                continue
-            r = sched.pick_resign()
-            slot_game[s], slot_resign[s] = g, r
-            start.append(s); res.append(r)
-        if start:
-            eng.start_games(start, resign=res)
-        return len(start)
+    def start(slots, games):
+        res = [sched.pick_resign() for _ in slots]
+        slot_resign.update(zip(slots, res))
+        eng.start_games(slots, resign=res)
+
+    def failed(s, g, error):
+        print("rank %d: slot %d (game %d) failed with engine error %d; game dropped" % (rank, s, g, error), file=sys.stderr)
+        slot_resign.pop(s)
+
+    def finished(s, g, result):
+        gd = eng.game_data(s, result, model_name)
+        sched.finished(gd, slot_resign.pop(s))
+        if gd['moves']:
+            outbox.append(_tuples_of(g, gd, rank, S))
 
     pool = ThreadPoolExecutor(max_workers=max(1, int(conf.get('WRITER_THREADS', 2)))) if rank == 0 else None
-    pending, outbox = [], []
-    played = written = steps = 0
+    pending = []
+    played = written = 0
     dev = torch.device("cuda", local) if backend == "nccl" else torch.device("cpu")
     exchange = TupleGather(tuple_dtype(S), device=dev)     # three-stage pipeline: the host never waits for a collective it has just issued
     try:
-        active = fill(range(G))
-        idle = G - active
+        loop = SlotLoop(eng, G, sched.reserve, start, finished, failed, max_steps)
         while True:
             for _ in range(sync_every):
-                if active == 0:
+                if not loop.playing:       # nothing left to play, or max_steps reached: the meeting still takes place
                     break
-                st = eng.step()
-                steps += 1
-                if st.n_records >= G:
-                    eng.drain()
-                if st.n_done > idle or (st.error and st.error_game in slot_game):
-                    eng.drain()
-                    res = eng.results()
-                    free = []
-                    for s in list(slot_game):
-                        if res[s]["done"] == 0:
-                            continue
-                        g = slot_game.pop(s)
-                        r = slot_resign.pop(s)
-                        free.append(s)
-                        active -= 1
-                        if res[s]["done"] < 0:
-                            print("rank %d: slot %d (game %d) failed with engine error %d; game dropped" % (rank, s, g, res[s]["done"]),
-                                  file=sys.stderr)
-                            eng.records[s] = []
-                            continue
-                        gd = eng.game_data(s, res[s], model_name)
-                        eng.records[s] = []
-                        sched.finished(gd, r)
-                        if gd['moves']:
-                            outbox.append(_tuples_of(g, gd, rank, S))
-                            played += 1
-                    refilled = fill(free)
-                    active += refilled
-                    idle += len(free) - refilled
-                if max_steps is not None and steps >= max_steps:
-                    active = 0
+                loop.step()
             # the meeting: finished games to rank 0, and does anybody still play?
             batch = np.concatenate(outbox) if outbox else np.zeros(0, dtype=tuple_dtype(S))
-            outbox = []
+            played += len(outbox)
+            del outbox[:]
             for got in exchange.submit(batch):               # batches of EARLIER meetings whose gather has completed
                 if rank == 0:
                     _write_games(got, model_name, S, pool, pending)
-            flag = torch.tensor([1 if active > 0 else 0], dtype=torch.int32, device=dev)
+            flag = torch.tensor([1 if loop.playing else 0], dtype=torch.int32, device=dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MAX)
             if int(flag.item()) == 0:
                 break

@@ -18,6 +18,7 @@ import random as pyrandom
 import numpy as np
 
 from . import _lib
+from ._game_loop import game_result_fields
 from .conf import conf
 
 END_REASONS = {0: "PLAYED ALL MOVES", 1: "resign", 2: "BOTH_PASSED"}
@@ -53,6 +54,21 @@ class MoveRecord(dict):
         if key == 'board':
             return unpack_positions(self['packed'][None], self.size)
         raise KeyError(key)
+
+
+def run_to_end(eng, max_steps=None):
+    """SelfPlayEngine.run / DualEngine.run: steps until no game is active (or max_steps); the finished games' game_data dicts."""
+    steps = 0
+    while True:
+        st = eng.step()
+        steps += 1
+        if st.n_records >= eng.G:
+            eng.drain()
+        if st.n_active == 0 or (max_steps is not None and steps >= max_steps):
+            break
+    eng.drain()
+    res = eng.results()
+    return [eng.game_data(s, res[s]) for s in range(eng.G) if res[s]["done"] == 1]
 
 
 class SelfPlayEngine(object):
@@ -147,58 +163,58 @@ class SelfPlayEngine(object):
             pass
 
     # ------------------------------------------------------------------ game slots
+    def _prepare_start(self, slots, uniforms):
+        """What both kinds of start share: slots as int32, the per-move uniform draws (default: this engine's generator)."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        if uniforms is None:
+            uniforms = self.rng.random_sample((len(slots), max(1, self.max_moves)))
+        return slots, np.ascontiguousarray(uniforms, dtype=np.float64).reshape(len(slots), -1)
+
+    @staticmethod
+    def _resign_array(resign, n):
+        """`if resign and value <= resign` (nomodel_self_play.py:171): None AND 0.0 mean "never resign" (NaN on the device)."""
+        if resign is None:
+            return None
+        return np.array([np.nan if not r else r for r in (resign if np.ndim(resign) else [resign] * n)], dtype=np.float32)
+
+    def _reset_records(self, slots, ids):
+        for i, s in enumerate(slots):
+            self.records[int(s)] = []
+            self.game_ids[int(s)] = None if ids is None else ids[i]
+
     def start_games(self, slots, noises=None, uniforms=None, resign=None, ids=None):
         """(Re)start game slots.  Draws default to numpy's own generators (np.random.dirichlet /
         random_sample -- the same distributions the reference draws from, play.py:401, and
         nomodel_self_play.py:135 through np.random.choice); tests inject recorded draws instead."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n = len(slots)
         if n == 0:
             return
         if noises is None:
             noises = self.rng.dirichlet([self.alpha] * self.A, size=n)
         noises = np.ascontiguousarray(noises, dtype=np.float64).reshape(n, self.A)
-        if uniforms is None:
-            uniforms = self.rng.random_sample((n, max(1, self.max_moves)))
-        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
-        res = None
-        if resign is not None:
-            # `if resign and value <= resign` (nomodel_self_play.py:171): None AND 0.0 mean "never resign"
-            res = np.array([np.nan if not r else r for r in resign], dtype=np.float32)
+        slots, uniforms = self._prepare_start(slots, uniforms)
+        res = self._resign_array(resign, n)
         with self._on_stream():
             _lib.check(self.lib.sgo_start_games(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(noises), _lib.ptr(uniforms),
                                                 C.c_int(uniforms.shape[1]), _lib.ptr(res), _lib.stream_ptr()), "sgo_start_games")
-        for i, s in enumerate(slots):
-            self.records[int(s)] = []
-            self.game_ids[int(s)] = None if ids is None else ids[i]
+        self._reset_records(slots, ids)
 
     def start_eval_games(self, slots, first_model=None, uniforms=None, resign_model1=None, resign_model2=None, ids=None):
         """(Re)start two-model game slots.  first_model[i] = 0: model1 moves first (plays black).  Default: the reference's
         coin, play.choose_first_player (one draw of Python's `random` per game, model1 first below .5)."""
         from . import play
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n = len(slots)
         if n == 0:
             return
         if first_model is None:
             first_model = [0 if play.choose_first_player(0, 1)[0] == 0 else 1 for _ in range(n)]
         first_model = np.ascontiguousarray(first_model, dtype=np.int32)
-        if uniforms is None:
-            uniforms = self.rng.random_sample((n, max(1, self.max_moves)))
-        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(n, -1)
-
-        def thr(r):
-            if r is None:
-                return None
-            return np.array([np.nan if not v else v for v in (r if np.ndim(r) else [r] * n)], dtype=np.float32)
-
-        r1, r2 = thr(resign_model1), thr(resign_model2)
+        slots, uniforms = self._prepare_start(slots, uniforms)
+        r1, r2 = self._resign_array(resign_model1, n), self._resign_array(resign_model2, n)
         with self._on_stream():
             _lib.check(self.lib.sgo_start_games2(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(uniforms), C.c_int(uniforms.shape[1]),
                                                  _lib.ptr(r1), _lib.ptr(r2), _lib.ptr(first_model), _lib.stream_ptr()), "sgo_start_games2")
-        for i, s in enumerate(slots):
-            self.records[int(s)] = []
-            self.game_ids[int(s)] = None if ids is None else ids[i]
+        self._reset_records(slots, ids)
 
     # ------------------------------------------------------------------ one engine step
     def _lut(self, k):
@@ -423,74 +439,28 @@ class SelfPlayEngine(object):
         return out
 
     def game_data(self, slot, result, model_name=None):
-        """The reference's game_data dict (nomodel_self_play.py:261-270) for a finished slot."""
+        """The reference's game_data dict (nomodel_self_play.py:227-270) for a finished slot.  Two-model games name the models
+        by colour and take the reference's winner rule (_game_loop.game_result_fields)."""
         if self.two_model:
-            return self._eval_game_data(slot, result)
-        name = model_name or getattr(self.net, "name", "model")
-        winner = int(result["winner"])
-        player_string = {1: "B", 0: "D", -1: "W"}
-        if int(result["end_reason"]) == 1:
-            winner_string = "%s+R" % player_string[int(result["last_player"])]
+            names = (getattr(self.net, "name", "model1"), getattr(self.net2, "name", "model2"))
         else:
-            winner_string = "%s+%s" % (player_string[winner], abs(int(result["black"]) - float(result["white"])))
-        return {
-            'moves': self.records.get(int(slot), []),
-            'modelB_name': name, 'modelW_name': name,
-            'winner': {1: 1, -1: 0, 0: None}[winner],
-            'winner_model': None if winner == 0 else name,
-            'result': winner_string,
-            'resign_model1': None, 'resign_model2': None,
-            'end_reason': END_REASONS[int(result["end_reason"])],
-            'black_points': int(result["black"]), 'white_points': float(result["white"]),
-            'slot': int(slot), 'id': self.game_ids.get(int(slot)),
-            'blocks_high_water': int(result["blocks_high_water"]),
-        }
-
-    def _eval_game_data(self, slot, result):
-        """game_data of a two-model game (nomodel_self_play.py:227-270): model names by colour, winner_model with the
-        reference's rule -- right while model1 plays black, the loser's name otherwise (:247) -- behind COMPAT_WINNER_MODEL."""
-        names = (getattr(self.net, "name", "model1"), getattr(self.net2, "name", "model2"))
-        model1_black = int(result["first_model"]) == 0
-        nameB, nameW = (names[0], names[1]) if model1_black else (names[1], names[0])
-        winner = int(result["winner"])
-        tag = {1: "B", 0: "D", -1: "W"}
-        if int(result["end_reason"]) == 1:
-            winner_string = "%s+R" % tag[int(result["last_player"])]
+            names = (model_name or getattr(self.net, "name", "model"),) * 2
+        model1_black = int(result["first_model"]) == 0 or not self.two_model
+        nameB, nameW = names if model1_black else names[::-1]
+        gd = {'moves': self.records.get(int(slot), [])}
+        gd.update(game_result_fields(int(result["winner"]), END_REASONS[int(result["end_reason"])], int(result["last_player"]),
+                                     int(result["black"]), float(result["white"]), nameB, nameW, model1_black, self.two_model))
+        gd.update({'resign_model1': None, 'resign_model2': None, 'black_points': int(result["black"]),
+                   'white_points': float(result["white"]), 'slot': int(slot), 'id': self.game_ids.get(int(slot))})
+        if self.two_model:
+            gd['first_model'] = int(result["first_model"])
         else:
-            winner_string = "%s+%s" % (tag[winner], abs(int(result["black"]) - float(result["white"])))
-        if winner == 0:
-            winner_model = None
-        elif conf.get('COMPAT_WINNER_MODEL', True):
-            winner_model = nameB if (winner == 1) == model1_black else nameW
-        else:
-            winner_model = nameB if winner == 1 else nameW
-        return {
-            'moves': self.records.get(int(slot), []),
-            'modelB_name': nameB, 'modelW_name': nameW,
-            'winner': {1: 1, -1: 0, 0: None}[winner], 'winner_model': winner_model, 'result': winner_string,
-            'resign_model1': None, 'resign_model2': None,
-            'end_reason': END_REASONS[int(result["end_reason"])],
-            'black_points': int(result["black"]), 'white_points': float(result["white"]),
-            'slot': int(slot), 'id': self.game_ids.get(int(slot)), 'first_model': int(result["first_model"]),
-        }
+            gd['blocks_high_water'] = int(result["blocks_high_water"])
+        return gd
 
     def run(self, max_steps=None):
         """Steps until no game is active; returns finished game_data dicts (slots are not restarted)."""
-        steps = 0
-        while True:
-            st = self.step()
-            if st.n_records >= self.G:
-                self.drain()
-            steps += 1
-            if st.n_active == 0 or (max_steps is not None and steps >= max_steps):
-                break
-        self.drain()
-        res = self.results()
-        out = []
-        for s in range(self.G):
-            if res[s]["done"] == 1:
-                out.append(self.game_data(s, res[s]))
-        return out
+        return run_to_end(self, max_steps)
 
     # ------------------------------------------------------------------ introspection (parity tests)
     def root_table(self, slot):
@@ -733,17 +703,7 @@ class DualEngine(object):
         return gd
 
     def run(self, max_steps=None):
-        steps = 0
-        while True:
-            st = self.step()
-            steps += 1
-            if st.n_records >= self.G:
-                self.drain()
-            if st.n_active == 0 or (max_steps is not None and steps >= max_steps):
-                break
-        self.drain()
-        res = self.results()
-        return [self.game_data(s, res[s]) for s in range(self.G) if res[s]["done"] == 1]
+        return run_to_end(self, max_steps)
 
     def root_table(self, slot):
         e, local = self._half_of(slot)

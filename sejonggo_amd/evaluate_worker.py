@@ -11,17 +11,17 @@ time.  Who plays black is the reference's coin per game (play.choose_first_playe
 conf['COMPAT_LATEST_SYM'] (default on) reproduces predicting_queue_worker.py:92: LATEST_SYM requests are answered by the BEST
 model, i.e. the reference's evaluation games are best-vs-best under the latest model's name.  Switch it off to evaluate the
 latest model for real."""
-import os
 import sys
 import traceback
 from multiprocessing import Process
 
 from .conf import conf
-from .selfplay_worker import _GpuWorker
+from .selfplay_worker import GameScheduler, _GpuWorker
 
 
 def run_evaluation(gpu_id, n_games=None, games_per_gpu=None, engine_kwargs=None):
     """The worker body.  Returns (wins of the latest model, games played)."""
+    from ._slot_loop import SlotLoop
     from .engine import SelfPlayEngine
     from .evaluator import save_eval_game
     from .predicting_queue_worker import init_predicting_workers, get_model, put_name_request
@@ -51,73 +51,24 @@ def run_evaluation(gpu_id, n_games=None, games_per_gpu=None, engine_kwargs=None)
               komi=conf['KOMI'], symmetry=conf.get('SYMMETRY_MODE', 'random1'), device=gpu_id, seed=gpu_id, raise_on_error=False)
     kw.update(engine_kwargs or {})
     eng = SelfPlayEngine(_Named(net1, best_name), net2=_Named(net2, latest_name), **kw)
-    next_game = [0]
+    # evaluate_worker.py:123-130: the next game number whose directory EVAL_DIR/<latest>/game_%03d could be created
+    sched = GameScheduler(conf['EVAL_DIR'], latest_name, n_games, None, None, pattern="game_%03d")
+    won = []         # per finished game: did the latest model win
 
-    def reserve():
-        """evaluate_worker.py:123-130: the next game number whose directory could be created."""
-        while next_game[0] < n_games:
-            g = next_game[0]
-            next_game[0] += 1
-            d = os.path.join(conf['EVAL_DIR'], latest_name, "game_%03d" % g)
-            if os.path.isdir(d):
-                continue
-            try:
-                os.makedirs(d)
-            except Exception:
-                continue
-            return g
-        return None
+    def failed(s, g, error):
+        print("evaluation slot %d (game %d) failed with engine error %d; game dropped" % (s, g, error), file=sys.stderr)
 
-    slot_game = {}
+    def finished(s, g, result):
+        gd = eng.game_data(s, result)
+        won.append(gd['winner_model'] == latest_name)
+        save_game_data(latest_name, g, gd, game_name="eval_game")
+        save_eval_game(latest_name, g, gd['winner_model'])
 
-    def fill(slots):
-        start = []
-        for s in slots:
-            g = reserve()
-            if g is None:
-                continue
-            slot_game[s] = g
-            start.append(s)
-        if start:
-            eng.start_eval_games(start, ids=[slot_game[s] for s in start])
-        return len(start)
-
-    wins = total = 0
     try:
-        active = fill(range(G))
-        idle = G - active
-        while active > 0:
-            st = eng.step()
-            if st.n_records >= G:
-                eng.drain()
-            if st.n_done > idle or (st.error and st.error_game in slot_game):
-                eng.drain()
-                res = eng.results()
-                free = []
-                for s in list(slot_game):
-                    if res[s]["done"] == 0:
-                        continue
-                    g = slot_game.pop(s)
-                    free.append(s)
-                    active -= 1
-                    if res[s]["done"] < 0:
-                        print("evaluation slot %d (game %d) failed with engine error %d; game dropped" % (s, g, res[s]["done"]),
-                              file=sys.stderr)
-                        eng.records[s] = []
-                        continue
-                    gd = eng.game_data(s, res[s])
-                    eng.records[s] = []
-                    if gd['winner_model'] == latest_name:
-                        wins += 1
-                    total += 1
-                    save_game_data(latest_name, g, gd, game_name="eval_game")
-                    save_eval_game(latest_name, g, gd['winner_model'])
-                refilled = fill(free)
-                active += refilled
-                idle += len(free) - refilled
+        SlotLoop(eng, G, sched.reserve, lambda slots, games: eng.start_eval_games(slots, ids=games), finished, failed).run()
     finally:
         eng.close()
-    return wins, total
+    return sum(won), len(won)
 
 
 class NoModelEvaluateWorker(_GpuWorker):

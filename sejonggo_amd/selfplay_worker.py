@@ -30,32 +30,39 @@ from .conf import conf
 
 
 class GameScheduler(object):
-    """Host logic shared by both workers: which game number a free slot plays next, and the resign
+    """Host logic shared by the workers: which game number a free slot plays next, and the resign
     threshold (selfplay_worker.py:82-112).  Pure bookkeeping; no compute."""
 
-    def __init__(self, self_play_dir, model_name, n_games, resignation_percent, allowed_error, rand=random, only_game=None):
-        self.dir, self.model_name, self.n_games = self_play_dir, model_name, n_games
+    def __init__(self, self_play_dir, model_name, n_games, resignation_percent, allowed_error, rand=random, only_game=None,
+                 pattern="game_%05d", candidates=None, create=True):
+        """Game directories are <self_play_dir>/<model_name>/<pattern % g>.  candidates: the game numbers to try, in order
+        (default range(n_games); a rank of dist_selfplay passes its shard).  create=False only skips numbers whose directory
+        exists (the ranks' resume rule: rank 0 alone writes)."""
+        self.dir, self.model_name, self.n_games, self.pattern = self_play_dir, model_name, n_games, pattern
         self.only_game = only_game     # self_play.py:303-304: `one_game_only` plays exactly that game number
         self.resignation_percent, self.allowed_error = resignation_percent, allowed_error
         self.rand = rand
-        self.next_game = 0
+        self.candidates = iter(range(n_games) if candidates is None else candidates)
+        self.create = create
         self.current_resign = None
         self.min_values = []
 
+    def _directory(self, game_no):
+        return os.path.join(self.dir, self.model_name, self.pattern % game_no)
+
     def reserve(self):
-        """Next game number whose directory could be created, or None when range(n_games) is exhausted."""
-        while self.next_game < self.n_games:
-            g = self.next_game
-            self.next_game += 1
+        """Next game number whose directory could be created, or None when the candidates are exhausted."""
+        for g in self.candidates:
             if self.only_game is not None and g != self.only_game:
                 continue
-            directory = os.path.join(self.dir, self.model_name, "game_%05d" % g)
+            directory = self._directory(g)
             if os.path.isdir(directory):
                 continue
-            try:
-                os.makedirs(directory)
-            except Exception:
-                continue
+            if self.create:
+                try:
+                    os.makedirs(directory)
+                except Exception:
+                    continue
             return g
         return None
 
@@ -76,7 +83,7 @@ class GameScheduler(object):
 
     def discard(self, game_no):
         try:
-            os.rmdir(os.path.join(self.dir, self.model_name, "game_%05d" % game_no))
+            os.rmdir(self._directory(game_no))
         except OSError:
             pass
 
@@ -90,6 +97,7 @@ def run_selfplay(gpu_id, model_indicator="BEST_SYM", n_games=None, games_per_gpu
     sample files; `stats` (a dict) receives wall-clock totals per activity."""
     import time
     from concurrent.futures import ThreadPoolExecutor
+    from ._slot_loop import SlotLoop
     from .engine import SelfPlayEngine
     from .predicting_queue_worker import init_predicting_workers, get_model, put_name_request
     from .sgfsave import save_self_play_data
@@ -121,7 +129,7 @@ def run_selfplay(gpu_id, model_indicator="BEST_SYM", n_games=None, games_per_gpu
         eng = DualEngine(net, **kw)            # refuses large rounds (DualEngine.MAX_ROUND_PIXELS): an explicit setting fails loudly
     else:
         eng = SelfPlayEngine(net, graph=bool(conf.get('ENGINE_GRAPH', False)), **kw)
-    slot_game, slot_resign = {}, {}
+    slot_resign = {}
     t = {"step": 0.0, "turnover": 0.0, "writer_wait": 0.0, "steps": 0, "moves": 0, "games": 0, "files": 0}
     # Finished games leave the stepping thread at once.  Default: conf['WRITER_THREADS'] threads of this process (libhdf5
     # is not thread-safe, so the file writes themselves are serialised on its lock: ~4-8 k files/s on the GPU box, plenty at
@@ -161,73 +169,41 @@ def run_selfplay(gpu_id, model_indicator="BEST_SYM", n_games=None, games_per_gpu
                 keep.append(f)
         pending[:] = keep
 
-    def fill(slots):
-        start, res, ids = [], [], []
-        for s in slots:
-            g = sched.reserve()
-            if g is None:
-                continue
-            r = sched.pick_resign()
-            slot_game[s], slot_resign[s] = g, r
-            start.append(s); res.append(r); ids.append(g)
-        if start:
-            eng.start_games(start, resign=res, ids=ids)
-        return len(start)
+    def start(slots, games):
+        res = [sched.pick_resign() for _ in slots]
+        slot_resign.update(zip(slots, res))
+        eng.start_games(slots, resign=res, ids=games)
 
-    played = 0
-    idle = 0          # finished slots that could not be refilled (no game numbers left)
+    def failed(s, g, error):
+        # the slot failed (typically SGO_ERR_CAPACITY: its tree outgrew blocks_per_game): give the game number back, drop
+        # what was recorded, and let the slot start a fresh game -- loudly
+        print("self-play slot %d (game %d) failed with engine error %d; game discarded" % (s, g, error), file=sys.stderr)
+        sched.discard(g)
+        slot_resign.pop(s, None)
+
+    def finished(s, g, result):
+        gd = eng.game_data(s, result, model_name)
+        gd['resign_model1'] = gd['resign_model2'] = r = slot_resign.pop(s)
+        sched.finished(gd, r)
+        if len(gd['moves']) == 0:
+            sched.discard(g)
+        else:
+            pending.append(submit(g, gd))
+            t["games"] += 1
+            t["moves"] += len(gd['moves'])
+
     t_loop0 = time.perf_counter()
     try:
-        active = fill(range(G))
-        idle = G - active
-        steps = 0
-        while active > 0:
+        loop = SlotLoop(eng, G, sched.reserve, start, finished, failed, max_steps)
+        while loop.playing:
             t0 = time.perf_counter()
-            st = eng.step()
-            steps += 1
-            if st.n_records >= G:
-                eng.drain()
+            st = loop.advance()
             t1 = time.perf_counter()
             t["step"] += t1 - t0
-            if st.n_done > idle or (st.error and st.error_game in slot_game):
-                eng.drain()
-                res = eng.results()
-                free = []
-                for s in list(slot_game):
-                    if res[s]["done"] < 0:
-                        # the slot failed (typically SGO_ERR_CAPACITY: its tree outgrew blocks_per_game): give the game
-                        # number back, drop what was recorded, and let the slot start a fresh game -- loudly
-                        print("self-play slot %d (game %d) failed with engine error %d; game discarded" % (
-                            s, slot_game[s], res[s]["done"]), file=sys.stderr)
-                        sched.discard(slot_game.pop(s))
-                        slot_resign.pop(s, None)
-                        eng.records[s] = []
-                        free.append(s)
-                        active -= 1
-                        continue
-                    if res[s]["done"] != 1:
-                        continue
-                    gd = eng.game_data(s, res[s], model_name)
-                    eng.records[s] = []        # the finished game owns its move list now
-                    gd['resign_model1'] = gd['resign_model2'] = slot_resign[s]
-                    g = slot_game.pop(s)
-                    sched.finished(gd, slot_resign.pop(s))
-                    if len(gd['moves']) == 0:
-                        sched.discard(g)
-                    else:
-                        pending.append(submit(g, gd))
-                        played += 1
-                        t["moves"] += len(gd['moves'])
-                    free.append(s)
-                    active -= 1
-                refilled = fill(free)
-                active += refilled
-                idle += len(free) - refilled
+            if loop.turn_over(st):
                 reap()
                 t["turnover"] += time.perf_counter() - t1
-            if max_steps is not None and steps >= max_steps:
-                break
-        t["steps"] = steps
+        t["steps"] = loop.steps
     finally:
         t0 = time.perf_counter()
         try:
@@ -236,12 +212,11 @@ def run_selfplay(gpu_id, model_indicator="BEST_SYM", n_games=None, games_per_gpu
             writers.shutdown(wait=True)
             t["writer_wait"] = time.perf_counter() - t0
             t["loop_s"] = time.perf_counter() - t_loop0   # first restart batch .. last sample file on disk
-            t["games"] = played
             t["net_calls"], t["net_positions"] = eng.n_net_calls, eng.n_net_positions
             if stats is not None:
                 stats.update(t)
             eng.close()
-    return played
+    return t["games"]
 
 
 class _GpuWorker(Process):
