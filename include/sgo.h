@@ -46,8 +46,9 @@ extern "C" {
 /* Bumped whenever a signature or a struct layout below changes.  A binding compares it with sgo_version() of the
  * library it loaded and refuses a mismatch (sejonggo_amd/_lib.py load(); INTEGRATION.md §B does the same).
  *   1: round 1.   2: sgo_start_games(+stream), sgo_game_result.first_model (40 bytes), sgo_config.two_model,
- *   sgo_conv_backend removed.   3: this round's additions (see the "half-populations" and "packed stem" sections). */
-#define SGO_ABI_VERSION 3
+ *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
+ *   as one kernel, the whole-net forward). */
+#define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
 int sgo_version(void);            /* SGO_ABI_VERSION the library was built with */
@@ -121,8 +122,9 @@ int sgo_bias_act_dev(long n_elems, int channels, const void *d_x, const void *d_
 
 /* The 3x3 convolutions of the resident net with the epilogue fused: y = relu(conv3x3(x, w) + bias[k] (+ skip)),
  * stride 1, pad 0 or 1, NHWC fp16 (x [n][h][w][c], w [k][3][3][c] = PyTorch channels_last weight storage,
- * y / skip [n][ho][wo][k]), fp32 accumulation on MFMA.  Dispatches to the two hand-written kernels below; any other
- * shape returns SGO_ERR_UNSUPPORTED (net.FusedInferenceNet then runs that layer through the framework's convolution and
+ * y / skip [n][ho][wo][k]), fp32 accumulation on MFMA.  Dispatches to the hand-written kernels below (the tower's and the
+ * stem's; together with sgo_stem_packed_dev and sgo_heads_dev they are every layer of the resident net); any other shape
+ * returns SGO_ERR_UNSUPPORTED (net.FusedInferenceNet then runs that layer through the framework's convolution and
  * sgo_bias_act_dev). */
 int sgo_conv3x3_bias_act_dev(int n, int h, int w, int c, int k, int pad, const void *d_x, const void *d_w,
                              const void *d_bias, const void *d_skip, void *d_y, void *stream);
@@ -166,6 +168,57 @@ int sgo_conv_tile_order(int mode);
 /* Test hook: cap the samples per launch of sgo_conv3x3_tower_dev / _stem_dev (0 = no cap) so that the slice loop, which
  * otherwise needs tensors beyond 2^31 bytes, can be exercised on small inputs.  Returns the previous cap; negative = query. */
 long sgo_conv_tower_slice_cap(long cap);
+
+/* ---- the heads of the resident net as ONE kernel (csrc/sgo_heads.hpp, k_heads; model.py:62-95) -------------------------- */
+/* Policy head Conv1x1(->2) + ReLU + Flatten + Dense(S*S+1, softmax) and value head Conv1x1(->2) + ReLU + Flatten + Dense(256,
+ * relu) + Dense(1, tanh), BatchNorm folded, on the tower's output.  Weights in the layouts net.FusedInferenceNet holds:
+ * head_w [4][256] fp16 (rows p0 p1 v0 v1), head_b [4], p_fc_w [A][2 t t], v_fc1_w [256][2 t t] with the K index in Keras'
+ * flatten order pixel * 2 + channel (t = S - 2, A = S*S + 1).  The two wide FC layers are read from a BANK in MFMA fragment
+ * order (K zero-padded to a multiple of 32, N to a multiple of 16), sgo_heads_packed_bytes(S) bytes, 16-byte aligned, written
+ * once per weight update by sgo_heads_prepack_dev.
+ * Arithmetic: every accumulation is fp32; h = relu(conv1x1 + bias) is rounded to fp16 once (an MFMA operand); logits, v1, the
+ * pre-tanh value, the softmax (row maximum subtracted) and the tanh stay fp32.
+ * sgo_heads_dev: y [n][t][t][256] fp16 NHWC -> policy [n][A] f32, value [n] f32: the shapes sgo_step consumes.  One launch, no
+ * allocation, no synchronisation (capturable); n == 0 is a no-op; rows >= n are neither read nor written.  y, head_w and the
+ * bank must be 16-byte aligned. */
+long sgo_heads_packed_bytes(int S);
+int sgo_heads_prepack_dev(int S, const void *d_p_fc_w, const void *d_v_fc1_w, void *d_bank, void *stream);
+int sgo_heads_dev(int S, int n, const void *d_y, const void *d_head_w, const void *d_head_b, const void *d_bank,
+                  const void *d_p_fc_b, const void *d_v_fc1_b, const void *d_v_fc2_w, const void *d_v_fc2_b, float *d_policy,
+                  float *d_value, void *stream);
+
+/* ---- the resident net as an object of this library: positions in, policy / value out (model.py:55-95) ----------------- */
+/* 256 channels, 'valid' stem, n_blocks residual blocks.  With sgo_eval_list and sgo_step a self-play loop needs this header
+ * alone ("A loop without a framework"). */
+typedef struct sgo_net sgo_net;
+/* Every pointer may be a HOST or a DEVICE pointer (copied with hipMemcpyDefault).  Layouts as net.FusedInferenceNet holds them:
+ * stem_w10 [256][10][16] fp16, stem_b [256] fp16, stem_wcol [256] f32 (see sgo_stem_packed_dev); block_*: n_blocks entries each,
+ * w OHWI [256][3][3][256] fp16, b [256] fp16; the head tensors as sgo_heads_dev / sgo_heads_prepack_dev take them. */
+typedef struct sgo_net_weights {
+    const void *stem_w10, *stem_b;
+    const float *stem_wcol;
+    const void *const *block_w1, *const *block_b1, *const *block_w2, *const *block_b2;
+    const void *head_w, *head_b, *p_fc_w, *p_fc_b, *v_fc1_w, *v_fc1_b, *v_fc2_w, *v_fc2_b;
+} sgo_net_weights;
+/* Allocates the weights, the heads bank and three activation buffers of max_batch * t * t * 256 fp16 (y, z, y'), once.
+ * NULL + sgo_last_error() for an unsupported S, n_blocks < 1, max_batch < 1 or when memory runs out. */
+sgo_net *sgo_net_create(int S, int n_blocks, int max_batch, int device_id);
+/* Copies the weights with hipMemcpyAsync on `stream` and prepacks the heads bank, and the k_conv4r filter banks when that tower
+ * kernel is selected.  PAGEABLE host sources have been read when the call returns; PINNED host sources and device sources are
+ * read when the stream reaches the copies and must stay valid and unchanged until then.  Call again after every weight update.
+ * The calling thread's current device is left as it was (also by sgo_net_create / sgo_net_packed_tower / sgo_net_destroy). */
+int sgo_net_set_weights(sgo_net *net, const sgo_net_weights *w, void *stream);
+/* Tower kernel of this net: on = 0: sgo_conv3x3_tower_dev (default), on = 1: sgo_conv3x3_tower_packed_dev (k_conv4r; the filter
+ * banks are allocated on the first selection and written here, on `stream`, when the net already has weights).  Same bits
+ * either way.  Returns SGO_OK or a negative error (the route is then unchanged; a later call allocates only what is missing). */
+int sgo_net_packed_tower(sgo_net *net, int on, void *stream);
+/* Row i of the outputs = the net on sym_k(record d_index[i]) (d_index NULL: records 0..n-1; d_sym_k, a device int, overrides
+ * sym_k when the kernels run): queues sgo_stem_packed_dev, 2 * n_blocks tower launches and sgo_heads_dev on `stream` and nothing
+ * else -- no allocation, no synchronisation, capturable.  n > max_batch runs in slices.  d_policy [n][A] f32 and d_value [n]
+ * f32 are what sgo_step / sgo_step_enqueue consume.  The tower output is bit-identical to net.FusedInferenceNet's. */
+int sgo_net_predict_packed_dev(sgo_net *net, int n, const uint32_t *d_records, const int32_t *d_index, int sym_k,
+                               const int32_t *d_sym_k, float *d_policy, float *d_value, void *stream);
+void sgo_net_destroy(sgo_net *net);
 
 /* ---- self-play engine: virtual-loss PUCT + game loop, many games resident on one GPU ------------ */
 /* Replaces nomodel_self_play.py:59-82 async_simulate2, :114-140 select_play, :142-271 play_game_async,

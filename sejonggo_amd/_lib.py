@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libsgo_hip.so")
 
 SUPPORTED_SIZES = (5, 7, 9, 13, 19)
 
-ABI_VERSION = 3          # SGO_ABI_VERSION of include/sgo.h these bindings were written against
+ABI_VERSION = 4          # SGO_ABI_VERSION of include/sgo.h these bindings were written against
 SGO_OK = 0
 SGO_ERR_OCCUPIED = -101
 SGO_ERR_RANGE = -102
@@ -24,6 +24,8 @@ SYMBOLS = [
     "sgo_legal_dev", "sgo_score_dev", "sgo_nn_pack_dev", "sgo_bias_act_dev", "sgo_conv3x3_bias_act_dev", "sgo_conv3x3_tower_dev", "sgo_conv3x3_tower_packed_bytes", "sgo_conv3x3_tower_prepack_dev", "sgo_conv3x3_tower_packed_dev", "sgo_conv_packed_variant", "sgo_conv3x3_stem_dev", "sgo_conv_tile_order", "sgo_conv_tower_kernel", "sgo_conv_tower_slice_cap", "sgo_advance_mode", "sgo_debug_counters", "sgo_debug_top_one", "sgo_debug_block_state", "sgo_debug_pool_state", "sgo_ctx_create", "sgo_ctx_destroy", "sgo_blocks_per_game", "sgo_pool_info", "sgo_start_games", "sgo_start_games2", "sgo_eval_models",
     "sgo_step", "sgo_step_enqueue", "sgo_step_status", "sgo_eval_list", "sgo_stem_packed_dev", "sgo_collect", "sgo_drain_records", "sgo_game_results", "sgo_root_table", "sgo_tree_serialize", "sgo_tree_dump",
     "sgo_game_board", "sgo_set_halt", "sgo_advance_timing",
+    "sgo_heads_packed_bytes", "sgo_heads_prepack_dev", "sgo_heads_dev", "sgo_net_create", "sgo_net_set_weights", "sgo_net_packed_tower",
+    "sgo_net_predict_packed_dev", "sgo_net_destroy",
 ]
 
 
@@ -53,6 +55,15 @@ class GameResult(C.Structure):
     _fields_ = [("winner", C.c_int32), ("black", C.c_int32), ("white", C.c_double), ("end_reason", C.c_int32),
                 ("n_moves", C.c_int32), ("last_player", C.c_int32), ("done", C.c_int32), ("first_model", C.c_int32),
                 ("blocks_high_water", C.c_int32)]
+
+
+class NetWeights(C.Structure):
+    """sgo_net_weights: every pointer host or device; block_*: arrays of n_blocks pointers."""
+    _fields_ = [("stem_w10", C.c_void_p), ("stem_b", C.c_void_p), ("stem_wcol", C.c_void_p),
+                ("block_w1", C.POINTER(C.c_void_p)), ("block_b1", C.POINTER(C.c_void_p)),
+                ("block_w2", C.POINTER(C.c_void_p)), ("block_b2", C.POINTER(C.c_void_p)),
+                ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("p_fc_w", C.c_void_p), ("p_fc_b", C.c_void_p),
+                ("v_fc1_w", C.c_void_p), ("v_fc1_b", C.c_void_p), ("v_fc2_w", C.c_void_p), ("v_fc2_b", C.c_void_p)]
 
 
 MOVE_RECORD_DTYPE = np.dtype([("game", "<i4"), ("game_seq", "<i4"), ("move_n", "<i4"), ("action", "<i4"),
@@ -111,6 +122,17 @@ def load():
     lib.sgo_debug_block_state.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
     lib.sgo_debug_pool_state.argtypes = [C.c_void_p] * 4
     lib.sgo_bias_act_dev.argtypes = [C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sgo_heads_packed_bytes.argtypes = [C.c_int]
+    lib.sgo_heads_packed_bytes.restype = C.c_long
+    lib.sgo_heads_prepack_dev.argtypes = [C.c_int] + [C.c_void_p] * 4
+    lib.sgo_heads_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 11
+    lib.sgo_net_create.argtypes = [C.c_int] * 4
+    lib.sgo_net_create.restype = C.c_void_p
+    lib.sgo_net_set_weights.argtypes = [C.c_void_p, C.POINTER(NetWeights), C.c_void_p]
+    lib.sgo_net_packed_tower.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.sgo_net_predict_packed_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_net_destroy.argtypes = [C.c_void_p]
+    lib.sgo_net_destroy.restype = None
     _lib = lib
     return lib
 

@@ -186,6 +186,10 @@ class FusedInferenceNet(object):
         # into registers (k_conv4r, csrc/sgo_conv4r.hpp; same bits, same speed on MI355X: DESIGN.md 4a) -- use_packed_tower()
         self.packed_tower = False
         self._banks = {}
+        # heads route: False = eight framework launches (GEMM, reshapes, three F.linear, softmax, tanh; the default), True = one
+        # hand-written kernel (k_heads, csrc/sgo_heads.hpp) fed from a fragment-order bank of the FC layers -- use_fused_heads()
+        self.fused_heads = False
+        self._heads_bank = None
         self.conv_events = None    # list of (start, end, flops) HIP-event brackets around tower convolutions while set (bench.py)
         self.side_flops = 0.0      # tower FLOPs issued on the side stream while conv_events is set
         self.conv_event_stride = 1  # bracket every k-th tower launch only (small batches: the event calls would bound the host)
@@ -207,6 +211,42 @@ class FusedInferenceNet(object):
                     self._banks[w.data_ptr()] = bank
         self.packed_tower = bool(on) and bool(self._banks)
         return self.packed_tower
+
+    def heads_kernel_ok(self):
+        """True for the shapes k_heads is written for: the reference's 256 channels on a supported board size."""
+        return self.channels == 256 and self.size in self._lib.SUPPORTED_SIZES and self.t == self.size - 2
+
+    def use_fused_heads(self, on=True):
+        """Route the heads through sgo_heads_dev (k_heads: one launch instead of eight).  The bank of the FC layers is written
+        here, once (sgo_heads_prepack_dev), not on the evaluation path.  Returns whether the route is active: never for other
+        channel counts or board sizes."""
+        from . import _lib
+        _lib.require_gpu()                       # no CPU fallback: without a device this raises, whatever `on` says
+        if on and self.heads_kernel_ok() and self._heads_bank is None:
+            self._pack_heads()
+        self.fused_heads = bool(on) and self._heads_bank is not None
+        return self.fused_heads
+
+    def _pack_heads(self):
+        nbytes = self.lib.sgo_heads_packed_bytes(self.size)
+        if self._heads_bank is None:
+            self._heads_bank = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._lib.check(self.lib.sgo_heads_prepack_dev(self.size, self.p_fc_w.data_ptr(), self.v_fc1_w.data_ptr(), self._heads_bank.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream), "sgo_heads_prepack_dev")
+
+    def _heads_kernel(self, y):
+        """(policy [n, A] f32, value [n, 1] f32) of the tower output y [n, 256, t, t] (channels-last memory) through k_heads."""
+        n = y.shape[0]
+        # the kernel reads [n][t][t][256] fp16 bytes: the hand-written convolutions write them so, the framework's fallback need not
+        if y.dtype != torch.float16 or not y.is_contiguous(memory_format=torch.channels_last):
+            y = y.to(torch.float16).contiguous(memory_format=torch.channels_last)
+        p = torch.empty((n, self.A), dtype=torch.float32, device=self.device)
+        v = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+        self._lib.check(self.lib.sgo_heads_dev(self.size, n, y.data_ptr(), self.head_w.data_ptr(), self.head_b.data_ptr(),
+                                               self._heads_bank.data_ptr(), self.p_fc_b.data_ptr(), self.v_fc1_b.data_ptr(),
+                                               self.v_fc2_w.data_ptr(), self.v_fc2_b.data_ptr(), p.data_ptr(), v.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), "sgo_heads_dev")
+        return p, v
 
     def _epilogue(self, y, bias, skip=None):
         L = self._lib
@@ -303,6 +343,8 @@ class FusedInferenceNet(object):
         for (w1, b1, w2, b2) in self.blocks:
             z = self._conv(y, w1, b1, 1)
             y = self._conv(z, w2, b2, 1, skip=y)
+        if self.fused_heads:
+            return self._heads_kernel(y)
         t2 = self.t * self.t
         h = F.relu(F.linear(y.permute(0, 2, 3, 1).reshape(n * t2, self.channels), self.head_w, self.head_b))
         h = h.reshape(n, t2, 4)
@@ -342,6 +384,66 @@ class FusedInferenceNet(object):
         for t in (p1, v1):
             t.record_stream(cur)
         return torch.cat([p0, p1]), torch.cat([v0, v1])
+
+
+class NativeNet(FusedInferenceNet):
+    """The resident net as an object of libsgo_hip.so (sgo_net_*, include/sgo.h): predict_packed is ONE library call that
+    queues the packed stem, the tower and k_heads on the current stream, into two torch-allocated output tensors.  The library
+    holds its own copy of the weights, taken from this object's tensors; after changing them call refresh().  The tensor route
+    (predict_on_batch) is FusedInferenceNet's."""
+
+    def __init__(self, net, dtype=torch.float16, device="cuda", max_batch=4096):
+        super().__init__(net, dtype, device)
+        if not (self.packed_ok and self.heads_kernel_ok() and self.blocks):
+            raise self._lib.SgoError("NativeNet: the library's net is the reference's shape only (256 channels, 'valid' stem, "
+                                     "at least one block, board size in %r)" % (self._lib.SUPPORTED_SIZES,))
+        self.max_batch = int(max_batch)
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._net = self.lib.sgo_net_create(self.size, len(self.blocks), self.max_batch, dev_index)
+        if not self._net:
+            raise self._lib.SgoError("sgo_net_create failed: %s" % self.lib.sgo_last_error().decode())
+        self.refresh()
+
+    def close(self):
+        if getattr(self, "_net", None):
+            self.lib.sgo_net_destroy(self._net)
+            self._net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def refresh(self):
+        """Re-upload this object's weight tensors into the library's net (and re-pack its banks)."""
+        import ctypes as C
+        L = self._lib
+        nb = len(self.blocks)
+        arr = [(C.c_void_p * nb)(*[b[i].data_ptr() for b in self.blocks]) for i in range(4)]
+        w = L.NetWeights(stem_w10=self.stem_w10.data_ptr(), stem_b=self.stem_b.data_ptr(), stem_wcol=self.stem_wcol.data_ptr(),
+                         block_w1=arr[0], block_b1=arr[1], block_w2=arr[2], block_b2=arr[3],
+                         head_w=self.head_w.data_ptr(), head_b=self.head_b.data_ptr(), p_fc_w=self.p_fc_w.data_ptr(),
+                         p_fc_b=self.p_fc_b.data_ptr(), v_fc1_w=self.v_fc1_w.data_ptr(), v_fc1_b=self.v_fc1_b.data_ptr(),
+                         v_fc2_w=self.v_fc2_w.data_ptr(), v_fc2_b=self.v_fc2_b.data_ptr())
+        L.check(self.lib.sgo_net_set_weights(self._net, C.byref(w), torch.cuda.current_stream().cuda_stream), "sgo_net_set_weights")
+        if self._heads_bank is not None:
+            self._pack_heads()
+
+    def use_packed_tower(self, on=True):
+        on = super().use_packed_tower(on)
+        self._lib.check(self.lib.sgo_net_packed_tower(self._net, 1 if on else 0, torch.cuda.current_stream().cuda_stream),
+                        "sgo_net_packed_tower")
+        return on
+
+    @torch.no_grad()
+    def predict_packed(self, records_ptr, index_ptr, n, k=0, k_dev_ptr=None):
+        p = torch.empty((n, self.A), dtype=torch.float32, device=self.device)
+        v = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+        self._lib.check(self.lib.sgo_net_predict_packed_dev(self._net, n, records_ptr, index_ptr, int(k), k_dev_ptr, p.data_ptr(),
+                                                            v.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                        "sgo_net_predict_packed_dev")
+        return p, v
 
 
 def build_fused_net(size, n_blocks, channels=256, name="model_0", seed=0, device="cuda"):

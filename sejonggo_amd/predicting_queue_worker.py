@@ -16,7 +16,8 @@ parent has initialised, so nothing here touches the GPU until a network is actua
   worker, a GTP front-end, a test), and keep it resident there.  A cache inherited over a fork is discarded.
 
 The resident form of a PolicyValueNet is net.FusedInferenceNet: BatchNorm folded, NHWC fp16, every 3x3 convolution
-through the hand-written tower kernel of libsgo_hip.so (conf['NET_DTYPE'] = 'fp32' keeps the plain torch module).
+through the hand-written tower kernel of libsgo_hip.so (conf['NET_DTYPE'] = 'fp32' keeps the plain torch module);
+conf['NATIVE_NET'] = 1 makes it net.NativeNet, the same net evaluated by one call into the library.
 
 Indicators are the reference's: "BEST", "LATEST", "BEST_SYM", "LATEST_SYM" (+ "*_NAME").  The reference evaluates
 LATEST_SYM requests with the BEST model (predicting_queue_worker.py:92); conf['COMPAT_LATEST_SYM'] (default on, like
@@ -53,13 +54,17 @@ def _own_cache():
 def resident_form(net, gpu_id):
     """The inference form of a loaded PolicyValueNet on GPU `gpu_id` (same weights, same contract, `.name` kept)."""
     import torch
-    from .net import FusedInferenceNet, PolicyValueNet
+    from .net import FusedInferenceNet, NativeNet, PolicyValueNet
     if not isinstance(net, PolicyValueNet):
         return net                                   # stub nets and caller-supplied objects are used as they are
     dev = torch.device("cuda", gpu_id)
     if conf.get('NET_DTYPE', 'fp16') == 'fp16' and net.stem.out_channels % 8 == 0:
+        # conf['NATIVE_NET'] (default 0): the whole forward behind the C ABI (net.NativeNet: sgo_net_predict_packed_dev, heads in
+        # k_heads) where the library has the shape; otherwise FusedInferenceNet with the framework's heads
+        native = conf.get('NATIVE_NET', 0) and net.stem.out_channels == 256 and net.size in _lib.SUPPORTED_SIZES \
+            and net.tower_side == net.size - 2 and len(net.blocks) > 0
         with torch.cuda.device(dev):
-            fused = FusedInferenceNet(net, torch.float16, dev)
+            fused = (NativeNet if native else FusedInferenceNet)(net, torch.float16, dev)
         fused.name = net.name
         return fused
     m = net.fused(torch.float32).to(dev)
