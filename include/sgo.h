@@ -43,11 +43,12 @@ extern "C" {
 #define SGO_ERR_DRAWS (-202)      /* ran out of injected random draws */
 #define SGO_ERR_STATE (-203)      /* call sequence violated */
 
-/* Bumped whenever a signature or a struct layout below changes.  A binding compares it with sgo_version() of the
+/* Bumped whenever a signature or a struct layout below changes; PURE ADDITIONS (new entry points, new error codes) do not bump
+ * it -- a binding finds out that a library is older than its header when a symbol is missing (sejonggo_amd/_lib.py load()).  A binding compares it with sgo_version() of the
  * library it loaded and refuses a mismatch (sejonggo_amd/_lib.py load(); INTEGRATION.md §B does the same).
  *   1: round 1.   2: sgo_start_games(+stream), sgo_game_result.first_model (40 bytes), sgo_config.two_model,
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
- *   as one kernel, the whole-net forward). */
+ *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -331,6 +332,44 @@ int sgo_collect(sgo_ctx *ctx, int sym_k, int layout, int dtype, void *d_nn_in, v
  * policy targets [cap][A] float64.  Returns the number written (>=0) and clears the buffer. */
 int sgo_drain_records(sgo_ctx *ctx, int cap, sgo_move_record *recs, uint32_t *packed, double *policy);
 int sgo_game_results(sgo_ctx *ctx, int n, const int32_t *slots, sgo_game_result *out);
+
+/* ---- interactive games: session slots that take external moves and answer genmove on demand ----------------------------- */
+/* Replaces sejonggo_nomodel.py:20-100 SejongGoEngine (play / genmove on a persistent tree), for 1..n_games resident games at
+ * once.  A slot becomes a SESSION by sgo_session_open; between commands it HOLDS: it keeps its board and tree, sgo_step skips
+ * it, and sgo_status counts it neither in n_active nor in n_done.  Session and ordinary slots may share one context (not a
+ * two_model one); sgo_start_games on a session slot turns it back into an ordinary game.  Every sgo_session_* call on a slot
+ * that runs an ordinary game fails with SGO_ERR_STATE.  slots / actions / colors / status / resign are HOST arrays of n entries
+ * (a slot may be listed once per call); all three calls wait for `stream` (use the stream the steps run on).
+ *
+ * sgo_session_open: as sgo_start_games without noise or draws -- empty board, empty tree, whatever the slot held (shared-pool
+ * blocks included) released -- but the slot is a session, holds, and plays at temperature 0 without Dirichlet noise for its
+ * whole life (sejonggo_nomodel.py:22 defaults).  It never ends by num_moves or by two passes: a GTP game goes on after both
+ * players pass.  resign: thresholds as in sgo_start_games (NULL, NaN or 0 = never).  Also serves clear_board (:135-140). */
+int sgo_session_open(sgo_ctx *ctx, int n, const int32_t *slots, const float *resign, void *stream);
+/* SejongGoEngine.play (sejonggo_nomodel.py:45-56) as ONE launch, one wavefront per listed slot.  actions[i] = y*S + x, pass = S*S;
+ * colors[i] = 0 for the side to move, or +1 / -1.  status[i] receives SGO_OK, SGO_ERR_STATE (not a session, or not holding),
+ * SGO_ERR_RANGE (action outside [0, S*S]) or SGO_ERR_OCCUPIED (play.py:233-234); a slot with a non-zero status is left
+ * untouched in every word.  Otherwise move_n is incremented and
+ *   - the move is in turn and the root holds an evaluated child for it: the tree is re-rooted onto that child (:49-51), its
+ *     statistics become the root's, every block that is no longer reachable is recycled (shared blocks go back to the pool);
+ *   - any other in-turn move (the child was never evaluated, the root is unexpanded, or the move is playable by make_play but
+ *     not in the legal set -- a suicide, which play.py:200-215 executes): the tree is dropped, the root holds
+ *     make_play(position, action, colour) (play.py:226-242) and the next genmove builds its tree from the root evaluation
+ *     (play.py:376-389 new_tree);
+ *   - an out-of-turn colour: the board is exactly make_play(x, y, board, color) and the tree is dropped.  DEVIATION: the
+ *     reference keeps the subtree's statistics there and replays them over the changed board; tree blocks store positions.
+ * Returns SGO_OK when the batch ran. */
+int sgo_session_play(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *actions, const int32_t *colors, int32_t *status,
+                     void *stream);
+/* SejongGoEngine.genmove (sejonggo_nomodel.py:58-76): ARMS the listed holding slots; the ordinary sgo_step loop then runs, per
+ * armed slot, one turn of play_game_async's loop body (nomodel_self_play.py:165-216): root evaluation; the resign test (value <=
+ * resign: a move record with action = -1 and a zero policy row; board, tree and move_n unchanged); new_tree without noise when
+ * the root is unexpanded; the search; the sgo_move_record with policy target and packed board; the re-root; move_n + 1 -- and
+ * then the slot holds again instead of asking for its next root evaluation.  The move is read from sgo_drain_records.
+ * A listed slot that is not a holding session (an ordinary game, a session that is still searching, a failed slot) gives
+ * SGO_ERR_STATE, and then NO slot of the call is armed. */
+int sgo_session_genmove(sgo_ctx *ctx, int n, const int32_t *slots, void *stream);
+
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */
 int sgo_root_table(sgo_ctx *ctx, int slot, int32_t *N, float *W, float *Q, double *P, int8_t *EX, int32_t *root_count,

@@ -15,6 +15,7 @@ SGO_OK = 0
 SGO_ERR_OCCUPIED = -101
 SGO_ERR_RANGE = -102
 SGO_ERR_UNSUPPORTED = -3
+SGO_ERR_STATE = -203
 
 # every symbol include/sgo.h declares (tests/test_abi.py checks the built library exports them all)
 SYMBOLS = [
@@ -26,6 +27,7 @@ SYMBOLS = [
     "sgo_game_board", "sgo_set_halt", "sgo_advance_timing",
     "sgo_heads_packed_bytes", "sgo_heads_prepack_dev", "sgo_heads_dev", "sgo_net_create", "sgo_net_set_weights", "sgo_net_packed_tower",
     "sgo_net_predict_packed_dev", "sgo_net_destroy",
+    "sgo_session_open", "sgo_session_play", "sgo_session_genmove",
 ]
 
 
@@ -92,6 +94,11 @@ def load():
     if lib.sgo_version() != ABI_VERSION:
         raise SgoError("libsgo_hip.so speaks ABI version %d, these bindings version %d (include/sgo.h SGO_ABI_VERSION): "
                        "rebuild with `python -m sejonggo_amd.build`" % (lib.sgo_version(), ABI_VERSION))
+    # entry points are added without a version bump (include/sgo.h), so a library older than these bindings shows as a missing symbol
+    missing = [name for name in SYMBOLS if not hasattr(lib, name)]
+    if missing:
+        raise SgoError("libsgo_hip.so lacks %s, which include/sgo.h declares (a stale build): rebuild with "
+                       "`python -m sejonggo_amd.build`" % ", ".join(missing))
     lib.sgo_last_error.restype = C.c_char_p
     lib.sgo_ctx_create.restype = C.c_void_p
     lib.sgo_ctx_create.argtypes = [C.POINTER(Config)]
@@ -133,6 +140,9 @@ def load():
     lib.sgo_net_predict_packed_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     lib.sgo_net_destroy.argtypes = [C.c_void_p]
     lib.sgo_net_destroy.restype = None
+    lib.sgo_session_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sgo_session_play.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_session_genmove.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

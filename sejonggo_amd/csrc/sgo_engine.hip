@@ -24,18 +24,6 @@
 
 namespace sgo {
 
-struct HostSide {  // not passed to kernels
-    uint8_t *stage = nullptr;                  // pinned host twin of Ctx::stage
-    size_t stage_cap = 0;
-    hipEvent_t ev_stage = nullptr;             // k_start has consumed the staged batch (host block and device twin)
-    bool stage_busy = false;
-    hipStream_t last_stream = nullptr;         // stream of the last sgo_step (records are drained behind it)
-    bool lds_attr_set = false;                 // k_search's > 64 KiB dynamic-LDS attribute has been set
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // bracket board_advance inside sgo_step
-    double adv_ms = 0;
-    long long adv_launches = 0, adv_positions = 0;
-};
-
 // ---------------------------------------------------------------------------------------- k_compact
 // One block.  Exclusive prefix sums of the per-game request counts -> dense evaluation list (block ids
 // in game-major order) and dense leaf list for board_advance; also folds the status words.
@@ -145,9 +133,10 @@ __global__ __launch_bounds__(1024) void k_compact(Ctx c) {
 
 // (re)start listed game slots: empty board in block 0, everything else free
 // Inputs come from the staging area filled by ONE host-to-device copy: slots[n], resign[n] (NaN = None), then
-// (optionally) noise[n][APAD] and uniforms[n][nu].
+// (optionally) noise[n][APAD] and uniforms[n][nu].  session != 0 (sgo_session_open): the same empty board and empty tree, but the
+// slot is a session that holds (PH_HOLD) at temperature 0 until a command arrives.
 template <int S>
-__global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int has_noise, int has_uniforms) {
+__global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int has_noise, int has_uniforms, int session) {
     using G = Geo<S>;
     const int k = blockIdx.x;
     if (k >= n) return;
@@ -183,6 +172,7 @@ __global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int h
     st.cur_model = st.first_model;
     st.other_root = -1;
     if (c.max_moves == 0) st.phase = PH_DONE;
+    if (session) { st.session = 1; st.phase = PH_HOLD; st.temperature = 0; }
     for (int i = lane; i < G::RW; i += 64) c.pos[gb0 * G::RW + i] = 0;
     for (int i = lane; i < G::NW; i += 64) {
         uint32_t w = 0xffffffffu;
@@ -208,11 +198,6 @@ __global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int h
 }  // namespace sgo
 
 using namespace sgo;
-
-struct sgo_ctx {
-    Ctx c;
-    HostSide h;
-};
 
 #define CK(call)                      \
     do {                              \
@@ -401,7 +386,7 @@ void sgo_ctx_destroy(sgo_ctx *x) {
 }
 
 static int start_games_impl(sgo_ctx *x, int n, const int32_t *slots, const double *noise, const double *uniforms, int n_uniforms,
-                            const float *resign, const float *resign2, const int32_t *first_model, void *stream);
+                            const float *resign, const float *resign2, const int32_t *first_model, void *stream, int session = 0);
 
 int sgo_start_games(sgo_ctx *x, int n, const int32_t *slots, const double *noise, const double *uniforms, int n_uniforms,
                     const float *resign, void *stream) {
@@ -415,7 +400,7 @@ int sgo_start_games2(sgo_ctx *x, int n, const int32_t *slots, const double *unif
 }
 
 static int start_games_impl(sgo_ctx *x, int n, const int32_t *slots, const double *noise, const double *uniforms, int n_uniforms,
-                            const float *resign, const float *resign2, const int32_t *first_model, void *stream) {
+                            const float *resign, const float *resign2, const int32_t *first_model, void *stream, int session) {
     if (!x || n < 0 || (n && !slots)) { set_error("sgo_start_games: bad argument"); return SGO_ERR_ARG; }
     Ctx &c = x->c;
     if (n == 0) return SGO_OK;
@@ -450,13 +435,36 @@ static int start_games_impl(sgo_ctx *x, int n, const int32_t *slots, const doubl
     }
     // one host-to-device copy, then one kernel, both on the caller's stream: ordered against the steps before and after
     SGO_HIP(hipMemcpyAsync(c.stage, h, L.total, hipMemcpyHostToDevice, st));
-    SGO_DISPATCH(c.S, k_start<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, L, noise != nullptr, nu > 0));
+    SGO_DISPATCH(c.S, k_start<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, L, noise != nullptr, nu > 0, session));
     SGO_HIP(hipGetLastError());
     // recorded BEHIND k_start: the event guards the pinned block and its device twin `c.stage` alike, so the next batch
     // (whatever stream it arrives on) is staged only after this one's kernel has read its slots / draws
     SGO_HIP(hipEventRecord(x->h.ev_stage, st));
     x->h.stage_busy = true;
     return SGO_OK;
+}
+
+// sejonggo_nomodel.py:20-35 SejongGoEngine.__init__ and GTPEngine.clear_board (:135-140): the listed slots become sessions on the
+// empty board.  The other two session entry points are in sgo_session.hip.
+int sgo_session_open(sgo_ctx *x, int n, const int32_t *slots, const float *resign, void *stream) {
+    if (!x || n < 0 || (n && !slots)) { set_error("sgo_session_open: bad argument"); return SGO_ERR_ARG; }
+    Ctx &c = x->c;
+    if (c.cfg.two_model) { set_error("sgo_session_open: a two_model context has no sessions"); return SGO_ERR_STATE; }
+    if (n == 0) return SGO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    std::vector<GameState> all(c.G);
+    SGO_HIP(hipMemcpyAsync(all.data(), c.gs, sizeof(GameState) * c.G, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_open: slot out of range"); return SGO_ERR_ARG; }
+        const GameState &s = all[slots[i]];
+        if (!s.session && (s.phase == PH_WAIT_ROOT || s.phase == PH_SEARCH)) {
+            set_error("sgo_session_open: the slot is running an ordinary game");
+            return SGO_ERR_STATE;
+        }
+    }
+    return start_games_impl(x, n, slots, nullptr, nullptr, 0, resign, nullptr, nullptr, stream, 1);
 }
 
 // Everything a step runs on the GPU, queued on `st` without waiting: k_search (consumes the evaluations of the list the previous

@@ -5,13 +5,17 @@
 //   Counters / DevStatus   running totals; the status words k_compact folds for the host
 //   StageLayout staging area of sgo_start_games (one host-to-device copy per batch of restarts)
 //   search_lds  the ONLY statement of k_search's dynamic LDS size, and the id-space limit that follows from it
+//   HostSide / sgo_ctx   what the host keeps per context beside Ctx (shared by sgo_engine.hip and sgo_session.hip)
 #pragma once
 #include "sgo_bits.hpp"
 #include "sgo_common.hpp"
 
 namespace sgo {
 
-enum { PH_IDLE = 0, PH_WAIT_ROOT = 1, PH_SEARCH = 2, PH_DONE = 3 };
+// PH_HOLD: a SESSION slot (sgo_session_open) between two commands -- it keeps its board and tree, takes external moves
+// (sgo_session_play) and waits to be armed (sgo_session_genmove); k_search skips it like PH_DONE, k_compact counts it neither as
+// active nor as done
+enum { PH_IDLE = 0, PH_WAIT_ROOT = 1, PH_SEARCH = 2, PH_DONE = 3, PH_HOLD = 4 };
 #define MAXE 64
 
 struct GameState {
@@ -26,7 +30,8 @@ struct GameState {
     int32_t i_uniform, n_uniform;
     int32_t noise_used, game_seq, n_req, req_kind;
     int32_t eval_base, root_requested, winner, black;
-    int32_t list_base, pad2_;              // k_compact: base of the game's requests in the leaf list (or among the root requests)
+    int32_t list_base;                     // k_compact: base of the game's requests in the leaf list (or among the root requests)
+    int32_t session;                       // 1: an interactive slot (csrc/sgo_session.hpp): a move ends in PH_HOLD, the game never ends by itself
     double white;
     int32_t n_moves, last_player;
     int64_t n_predict, none_events;
@@ -141,4 +146,22 @@ static size_t search_lds(const Ctx &c) {
     return search_lds_bytes(c.L, Geo<S>::APAD);
 }
 
+struct HostSide {  // not passed to kernels
+    uint8_t *stage = nullptr;                  // pinned host twin of Ctx::stage
+    size_t stage_cap = 0;
+    hipEvent_t ev_stage = nullptr;             // k_start has consumed the staged batch (host block and device twin)
+    bool stage_busy = false;
+    hipStream_t last_stream = nullptr;         // stream of the last sgo_step (records are drained behind it)
+    bool lds_attr_set = false;                 // k_search's > 64 KiB dynamic-LDS attribute has been set
+    bool lds_attr_session = false;             // ... and k_session_play's
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // bracket board_advance inside sgo_step
+    double adv_ms = 0;
+    long long adv_launches = 0, adv_positions = 0;
+};
+
 }  // namespace sgo
+
+struct sgo_ctx {
+    sgo::Ctx c;
+    sgo::HostSide h;
+};

@@ -410,14 +410,16 @@ struct Search {
         // resign = resign_model1 if current == model1 else resign_model2 (nomodel_self_play.py:170-173)
         const bool use2 = c.cfg.two_model && st.cur_model == 1;
         if (use2 ? (st.has_resign2 && st.value <= st.resign2) : (st.has_resign && st.value <= st.resign)) {
-            finish(1);
+            // a session slot resigns without ending (sejonggo_nomodel.py:58-60 genmove): play_move records action -1 and holds
+            if (st.session) { st.end_reason = 1; st.rounds_left = 0; st.phase = PH_SEARCH; }
+            else finish(1);
             return;
         }
         // "if not mcts_tree or not mcts_tree['subtree']": the root block carries children iff flag set
         bool expanded = c.bSlot[e.ph(st.root_blk)] != -2;  // -2 marks "block holds no children yet"
         if (!expanded) {
             const double *noise = nullptr;
-            if (c.cfg.self_play) {
+            if (c.cfg.self_play && !st.session) {      // a session's tree never gets noise (sejonggo_nomodel.py:22 add_noise=False)
                 if (st.noise_used) fail(SGO_ERR_DRAWS);
                 noise = c.noise + (size_t)g * G::APAD;
                 st.noise_used = 1;
@@ -593,7 +595,7 @@ struct Search {
         for (int i = lane; i < G::RW; i += 64) c.recPacked[(size_t)ri * G::RW + i] = c.pos[e.ph(st.root_blk) * G::RW + i];
         for (int i = lane; i < G::A; i += 64) {
             double p = 0;
-            if (e.legal_bit(st.root_blk, i)) p = st.root_f64 ? c.rootP64[(size_t)g * G::APAD + i] : (double)c.cP[sb + i];
+            if (selected >= 0 && e.legal_bit(st.root_blk, i)) p = st.root_f64 ? c.rootP64[(size_t)g * G::APAD + i] : (double)c.cP[sb + i];
             c.recPolicy[(size_t)ri * G::A + i] = p;
         }
         return true;
@@ -728,13 +730,17 @@ struct Search {
         if (st.halt_at == st.move_n) { st.phase = PH_DONE; run = false; return; }
         const size_t sb = e.slot_base(st.root_blk);
         int selected = -1;
-        const int err = choose_move(sb, selected);
-        if (err) { fail(err); return; }
+        if (!st.end_reason) {                      // set here only by a session slot that resigns: no move is chosen
+            const int err = choose_move(sb, selected);
+            if (err) { fail(err); return; }
+        }
         if (st.temperature == 1) st.i_uniform++;
         if (!record_move(sb, selected)) return;
+        // the resign record (action -1, a zero policy row) is all that happens: board, tree and move_n stay, the slot holds again
+        if (selected < 0) { st.end_reason = 0; st.phase = PH_HOLD; run = false; return; }
         st.n_moves = st.move_n + 1;
         const bool is_pass = (selected == G::N);
-        if (st.skipped_last && is_pass) { finish(2); st.n_moves = st.move_n + 1; return; }   // BOTH_PASSED (:197-199)
+        if (st.skipped_last && is_pass && !st.session) { finish(2); st.n_moves = st.move_n + 1; return; }   // BOTH_PASSED (:197-199)
         st.skipped_last = is_pass ? 1 : 0;
         const int nr = chosen_child(sb, selected);
         if (nr < 0) { fail(SGO_ERR_STATE); return; }
@@ -744,11 +750,16 @@ struct Search {
         // board, player = make_play(...): the new root block already holds the position after the move
         st.player = mover;
         st.move_n++;
-        if (st.move_n >= c.max_moves) { finish(0); return; }
+        // a session slot (csrc/sgo_session.hpp) never ends by itself -- a GTP game goes on after two passes and has no move limit
+        // -- and HOLDS after its move instead of asking for its next root evaluation.  The hold is three selects on the common
+        // path, not an exit of its own: a separate `if (st.session) return` cost 11 VGPRs in every k_search<S> (measured).
+        if (st.move_n >= c.max_moves && !st.session) { finish(0); return; }
         st.last_value = st.value;
         if (st.move_n == c.cfg.stop_exploration) st.temperature = 0;
-        st.phase = PH_WAIT_ROOT;
         request_root();
+        st.phase = st.session ? PH_HOLD : PH_WAIT_ROOT;
+        st.root_requested = st.session ? 0 : 1;
+        st.n_req = st.session ? 0 : 1;
     }
 
     // a game that has just failed (its tree is abandoned; the slot waits for a restart) hands its shared blocks back at once,
@@ -779,7 +790,7 @@ __global__ __launch_bounds__(64) void k_search(Ctx c, const float *policy, const
     Search<S> s(c, g, lds, policy, value, sym_k_imm, sym_k_dev);
     GameState &st = s.st;
     st.n_req = 0;
-    if (st.phase == PH_IDLE || st.phase == PH_DONE) {
+    if (st.phase == PH_IDLE || st.phase == PH_DONE || st.phase == PH_HOLD) {
         if (s.lane == 0) c.gs[g].n_req = 0;
         return;
     }

@@ -574,6 +574,88 @@ class SelfPlayEngine(object):
         return ms.value, n.value, p.value
 
 
+class SessionEngine(SelfPlayEngine):
+    """Interactive games on the device engine (include/sgo.h "interactive games"; sejonggo_nomodel.py:20-100 SejongGoEngine for
+    1..n_games resident games): slots opened as SESSIONS keep their board and tree between commands, take external moves
+    (`play`) and answer `genmove` on demand.  Slots that are not opened stay ordinary game slots (start_games / step / drain), so
+    one context can serve both.  Always eager steps on ONE stream: no captured rounds (graph=True is refused) and no DualEngine
+    -- a genmove is a handful of latency-bound steps, and the host decides after each whether the move is there.
+    board(slot), tree_dict(slot), root_table(slot), block_state and pool_state work on session slots unchanged."""
+
+    def __init__(self, net, **kw):
+        if kw.get("graph") or kw.get("net2") is not None or kw.get("stream") is not None:
+            raise ValueError("SessionEngine runs eager steps of one model on the caller's stream (no graph, net2 or stream)")
+        kw.setdefault("self_play", False)              # sessions never add noise; ordinary slots of a mixed context may
+        super(SessionEngine, self).__init__(net, **kw)
+
+    def _stream_ptr(self):
+        return _lib.stream_ptr()
+
+    def open(self, slots, resign=None):
+        """The listed slots become sessions on the empty board (also: clear_board).  resign: one threshold or one per slot."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        res = self._resign_array(resign, len(slots))
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_open(self.ctx, C.c_int(len(slots)), _lib.ptr(slots), _lib.ptr(res), self._stream_ptr()),
+                       "sgo_session_open")
+        self._reset_records(slots, None)
+
+    def play(self, slots, actions, colors=None):
+        """SejongGoEngine.play for every listed slot in one launch.  actions: y * S + x, pass = S * S; colors: 0 / None = the side
+        to move, +1 black, -1 white.  Returns the int32 status per slot (0, SGO_ERR_STATE, SGO_ERR_RANGE, SGO_ERR_OCCUPIED); a
+        slot with a non-zero status is unchanged."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        actions = np.ascontiguousarray(actions, dtype=np.int32)
+        n = len(slots)
+        if len(actions) != n or (colors is not None and len(colors) != n):
+            raise ValueError("play: slots, actions and colors must have one entry per slot")
+        colors = np.zeros(n, np.int32) if colors is None else np.ascontiguousarray([c or 0 for c in colors], dtype=np.int32)
+        status = np.zeros(n, np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_play(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(actions), _lib.ptr(colors),
+                                                 _lib.ptr(status), self._stream_ptr()), "sgo_session_play")
+        return status
+
+    def genmove_step_bound(self, n_slots):
+        """Steps a genmove may take.  The step after the arming asks for the root evaluation; every later step consumes at
+        least one evaluation of the slot (a round that is blocked waits for a leaf it requested in that very step), a move
+        consumes 1 + sims of them at most, and one more step plays the move: sims + 3.  On top, one step per round
+        (sims // energy) and per listed slot as slack."""
+        return self.sims + 3 + self.sims // self.E + n_slots
+
+    def arm(self, slots):
+        """First half of genmove: the listed holding sessions start their move's search with the next step.  Raises SgoError
+        (and arms nothing) when a listed slot is no holding session."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_genmove(self.ctx, C.c_int(len(slots)), _lib.ptr(slots), self._stream_ptr()),
+                       "sgo_session_genmove")
+
+    def genmove(self, slots):
+        """Arms the listed holding sessions and steps the context until each has recorded its move (ordinary games of a mixed
+        context advance with them).  Returns, per slot, (action, value, policy_target): action y * S + x, S * S = pass,
+        -1 = resign (board and tree unchanged; the policy row is zero).  Raises SgoError when a slot is no holding session
+        (nothing is armed then) or when the step bound is exceeded."""
+        self.arm(slots)
+        return self.wait(slots)
+
+    def wait(self, slots):
+        """Second half of genmove: steps until every listed (armed) slot has recorded its move; the moves as genmove returns them."""
+        got, pending = {}, [int(s) for s in slots]
+        bound = self.genmove_step_bound(len(slots))
+        for _ in range(bound):
+            if self.step().n_records > 0:
+                self.drain()
+            for s in list(pending):
+                if self.records.get(s):
+                    got[s] = self.records[s].pop(0)
+                    pending.remove(s)
+            if not pending:
+                return [(int(got[int(s)]['action']), got[int(s)]['value'], got[int(s)]['policy']) for s in slots]
+        raise _lib.SgoError("genmove: slots %s recorded no move within %d steps (sims %d, energy %d)"
+                            % (pending, bound, self.sims, self.E))
+
+
 class _SumStatus(object):
     """The status of a DualEngine step: counts summed over the halves, the first error with its slot in the whole population."""
     __slots__ = ("n_eval", "n_records", "n_active", "n_done", "error", "error_game", "total_moves", "total_evals", "none_events")

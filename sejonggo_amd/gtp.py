@@ -76,6 +76,102 @@ class SejongGoEngine(object):
         return x, y, policy_target, value, self.board, self.player
 
 
+class DeviceSejongGoEngine(object):
+    """SejongGoEngine on the device engine: the game is a session slot of an engine.SessionEngine (tree, rules and search on
+    the GPU), with the attribute surface GTPEngine drives -- play, genmove, board, player (who moved last, as make_play returns
+    it), move, mcts_tree, model, close.
+    `engine` / `slot` put it on a slot of an existing SessionEngine (many games in one context); otherwise it owns a context
+    of one game (engine_kw go to SessionEngine).  Temperature 0 and no noise only: the host engine remains for the rest.
+    One deviation from the reference: a `play` with an out-of-turn colour drops the tree (include/sgo.h)."""
+
+    def __init__(self, mcts_simulations, board=None, resign=None, temperature=0, add_noise=False, net=None, engine=None, slot=0,
+                 **engine_kw):
+        if temperature != 0 or add_noise:
+            raise ValueError("DeviceSejongGoEngine plays at temperature 0 without noise; use SejongGoEngine for the rest")
+        if board is not None and np.any(np.asarray(board)[..., :16]):
+            raise ValueError("DeviceSejongGoEngine starts from the empty board")
+        self.mcts_simulations = mcts_simulations
+        self.resign = resign
+        self.temperature = 0
+        self.add_noise = False
+        self.move = 1
+        self.player = 1                     # as the reference keeps it: the board's colour plane at first, then who moved last
+        self.slot = int(slot)
+        self._own = engine is None
+        self._workers = False
+        if engine is None:
+            from .engine import SessionEngine
+            if net is None:
+                init_predicting_workers(conf['GPUs'][:1])
+                self._workers = True
+                net = get_model("BEST")
+            engine_kw.setdefault("n_games", 1)
+            engine = SessionEngine(net, sims=mcts_simulations, **engine_kw)
+        self.engine = engine
+        self.size = engine.S
+        self.engine.open([self.slot], resign=resign)
+
+    @property
+    def model(self):
+        return self.engine.net
+
+    @property
+    def board(self):
+        return self.engine.board(self.slot)
+
+    @board.setter
+    def board(self, board):
+        # GTPEngine.clear_board assigns the empty board, then mcts_tree = None and move = 1
+        if np.any(np.asarray(board)[..., :16]):
+            raise ValueError("a session starts from the empty board")
+        self.engine.open([self.slot], resign=self.resign)
+        self.player = 1
+
+    @property
+    def mcts_tree(self):
+        """The device tree as the reference's nested dicts (engine.tree_dict); its subtree is empty while the root is unexpanded."""
+        return self.engine.tree_dict(self.slot)
+
+    @mcts_tree.setter
+    def mcts_tree(self, tree):
+        if tree is not None or self.engine.tree_dict(self.slot)['subtree']:
+            raise ValueError("the device tree is dropped by clear_board only")
+
+    def close(self):
+        if self._own and self.engine is not None:
+            self.engine.close()
+            if self._workers:
+                destroy_predicting_workers(conf['GPUs'][:1])
+        self.engine = None
+
+    def set_temperature(self, temperature):
+        if temperature != 0:
+            raise ValueError("DeviceSejongGoEngine plays at temperature 0")
+
+    def play(self, color, x, y, update_tree=True):
+        index = coord2index(x, y, self.size)
+        status = int(self.engine.play([self.slot], [index], [color or 0])[0])
+        if status:
+            raise ValueError("play %s at (%d, %d) refused: %d (%s)" % (color, x, y, status, {
+                -101: "the point is occupied", -102: "outside the board", -203: "the slot is not a holding session"}.get(status, "?")))
+        self.move += 1
+        board = self.board
+        self.player = -int(board[0, 0, 0, -1])           # make_play returns the player who moved (play.py:226-242)
+        return board, self.player
+
+    def genmove(self, color):
+        board = self.board
+        if color and color != int(board[0, 0, 0, -1]):
+            raise ValueError("genmove for the side that is not to move: play the missing move (or a pass) first")
+        action, value, policy = self.engine.genmove([self.slot])[0]
+        if action < 0:
+            return 0, self.size + 1, policy, value, board, self.player
+        x, y = index2coord(action, self.size)
+        self.move += 1
+        self.player = int(board[0, 0, 0, -1])
+        return x, y, policy, value, self.board, self.player
+
+
 class GTPEngine(object):
     def __init__(self, engine=None):
         self._komi = 0
@@ -153,8 +249,9 @@ class GTPEngine(object):
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 
-def main(inp=sys.stdin, out=sys.stdout):
-    engine = GTPEngine()
+def main(inp=sys.stdin, out=sys.stdout, device=False):
+    """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine)."""
+    engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None)
     for line in inp:
         for cmd in line.split("\n"):
             res = engine.parse_command(cmd)
@@ -167,4 +264,4 @@ def main(inp=sys.stdin, out=sys.stdout):
 
 
 if __name__ == "__main__":
-    main()
+    main(device="--device" in sys.argv[1:])
