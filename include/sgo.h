@@ -258,7 +258,7 @@ typedef struct sgo_status {
     int32_t n_done;       /* game slots finished and not yet restarted */
     int32_t error;        /* first error raised by any game (SGO_ERR_*) or 0 */
     int32_t error_game;
-    int64_t total_moves;  /* moves played since ctx creation */
+    int64_t total_moves;  /* moves played since ctx creation (a session's resign record counts, an analysis record does not) */
     int64_t total_evals;  /* network evaluations consumed since ctx creation */
     int64_t none_events;  /* "No best leaf" events (nomodel_self_play.py:70-75) */
 } sgo_status;
@@ -268,7 +268,7 @@ typedef struct sgo_move_record {
     int32_t game;      /* slot */
     int32_t game_seq;  /* how many games this slot had finished before this one */
     int32_t move_n;
-    int32_t action;
+    int32_t action;    /* y*S + x, S*S = pass; -1 = a session resigned, SGO_ACTION_ANALYSIS (-2) = a search-only record */
     int32_t player;    /* 'player' exactly as the reference records it */
     float value;       /* raw network value at the root */
 } sgo_move_record;
@@ -369,6 +369,49 @@ int sgo_session_play(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *a
  * A listed slot that is not a holding session (an ordinary game, a session that is still searching, a failed slot) gives
  * SGO_ERR_STATE, and then NO slot of the call is armed. */
 int sgo_session_genmove(sgo_ctx *ctx, int n, const int32_t *slots, void *stream);
+/* A position instead of the empty board (GTP undo, loadsgf, handicap stones; a game record under review): for every listed slot
+ * what sgo_session_open followed by the slot's move list through sgo_session_play does -- the empty board, then the moves, with
+ * make_play's rules (play.py:226-242: suicide executed; colors 0 = the side to move, +1 / -1 explicit, an out-of-turn colour is
+ * how set-up and handicap stones are placed, played as sgo_session_play plays it and with its DEVIATION: no tree survives) -- in
+ * ONE launch for all slots, one wavefront per slot, and one host-to-device copy of all lists (a staging buffer of the context
+ * that only grows: no allocation per call once it has).  Slot i replays actions / colors [moves_off[i], moves_off[i] +
+ * n_moves[i]) (colors NULL: all 0).  The slot is left holding with an unexpanded root; everything else it held, shared-pool
+ * blocks included, is released; move_n and player are as the chain of plays leaves them; the slot's resign threshold is KEPT
+ * (a list of zero moves is sgo_session_open without a change of the threshold).
+ * ATOMIC PER SLOT: the list is replayed into a private copy of the record and the slot is written after the last move only.
+ * status[i] = SGO_OK and fail_at[i] = -1, or SGO_ERR_RANGE / SGO_ERR_OCCUPIED with fail_at[i] = the index of the refused move, or
+ * SGO_ERR_STATE (not a holding session; fail_at -1); a refused slot is unchanged in every word, the other slots of the call go
+ * through.  A slot listed twice, a negative length or a list longer than SGO_SETUP_MAX_MOVES(size) returns SGO_ERR_ARG and
+ * nothing runs.  Waits for `stream`. */
+#define SGO_SETUP_MAX_MOVES(size) (4 * (size) * (size))
+int sgo_session_setup(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *n_moves, const int32_t *moves_off,
+                      const int32_t *actions, const int32_t *colors, int32_t *status, int32_t *fail_at, void *stream);
+/* Search without moving: ARMS the listed holding slots as sgo_session_genmove does (all or none, SGO_ERR_STATE otherwise); the
+ * ordinary sgo_step loop then runs, per armed slot: the root evaluation; NO resign test; new_tree without noise when the root is
+ * unexpanded (play.py:376-389); sims / energy rounds of async_simulate2 (nomodel_self_play.py:59-82; sims <= 0: the context's,
+ * 0 < sims < energy: SGO_ERR_ARG) -- select_play's simulation loop (:114-124) without its choice.  Instead of a move the slot
+ * writes ONE sgo_move_record with action = SGO_ACTION_ANALYSIS, the root's net value, the packed root position and the prior row
+ * a genmove from this root would record, and holds.  Board, tree and move_n stay; the searched tree is KEPT: a second analyze
+ * deepens it (one more root evaluation, then its rounds), a following genmove searches on top of it as the reference does with
+ * a kept subtree (sejonggo_nomodel.py:63), a following play follows into it when it can.  A search that outgrows the slot's
+ * blocks fails the slot with SGO_ERR_CAPACITY, as any search does; sgo_game_results then shows done = the error and, for a slot
+ * that failed inside an analysis, end_reason = 2 (the engine's mark of a search-only search, not BOTH_PASSED): a failed session
+ * slot has no result to read, reopen it. */
+#define SGO_ACTION_ANALYSIS (-2)
+int sgo_session_analyze(sgo_ctx *ctx, int n, const int32_t *slots, int sims, void *stream);
+/* The result of many slots at once: ONE launch (one wavefront per slot) and one copy back; waits for `stream`.  HOST outputs,
+ * each may be NULL except status: status[n] (SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: its rows are left
+ * as the caller filled them), to_play[n] (+1 black), root_count[n], root_value[n], root_mean[n], n_children[n]; the root's child
+ * tables N[n][A] (-1 = no child), Q[n][A], P[n][A] float32 -- the values sgo_root_table gives, raw; top_action[n][K]: the K best
+ * children in select_play's temperature-0 order (nomodel_self_play.py:138: count, then mean, then the HIGHER index), -1 padded;
+ * pv[n][K][D]: below each, the principal variation -- the child itself, then the same rule applied down the tree while the
+ * node is expanded and has a visited child, at most D moves, -1 padded.  K <= SGO_REPORT_MAX_TOP, D <= SGO_REPORT_MAX_DEPTH,
+ * SGO_ERR_ARG beyond. */
+#define SGO_REPORT_MAX_TOP 16
+#define SGO_REPORT_MAX_DEPTH 32
+int sgo_session_report(sgo_ctx *ctx, int n, const int32_t *slots, int K, int D, int32_t *status, int32_t *to_play,
+                       int32_t *root_count, float *root_value, float *root_mean, int32_t *n_children, int32_t *N, float *Q,
+                       float *P, int32_t *top_action, int32_t *pv, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

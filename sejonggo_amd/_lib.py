@@ -16,6 +16,10 @@ SGO_ERR_OCCUPIED = -101
 SGO_ERR_RANGE = -102
 SGO_ERR_UNSUPPORTED = -3
 SGO_ERR_STATE = -203
+SGO_ERR_ARG = -1
+SGO_ERR_CAPACITY = -201
+SGO_ACTION_ANALYSIS = -2     # sgo_move_record.action of a search-only record (sgo_session_analyze)
+REPORT_MAX_TOP, REPORT_MAX_DEPTH = 16, 32
 
 # every symbol include/sgo.h declares (tests/test_abi.py checks the built library exports them all)
 SYMBOLS = [
@@ -27,7 +31,7 @@ SYMBOLS = [
     "sgo_game_board", "sgo_set_halt", "sgo_advance_timing",
     "sgo_heads_packed_bytes", "sgo_heads_prepack_dev", "sgo_heads_dev", "sgo_net_create", "sgo_net_set_weights", "sgo_net_packed_tower",
     "sgo_net_predict_packed_dev", "sgo_net_destroy",
-    "sgo_session_open", "sgo_session_play", "sgo_session_genmove",
+    "sgo_session_open", "sgo_session_play", "sgo_session_genmove", "sgo_session_setup", "sgo_session_analyze", "sgo_session_report",
 ]
 
 
@@ -143,6 +147,9 @@ def load():
     lib.sgo_session_open.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sgo_session_play.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
     lib.sgo_session_genmove.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sgo_session_setup.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    lib.sgo_session_analyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.sgo_session_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12
     _lib = lib
     return lib
 

@@ -379,6 +379,8 @@ void sgo_ctx_destroy(sgo_ctx *x) {
     (void)hipDeviceSynchronize();
     ctx_free(x->c);
     if (x->h.stage) (void)hipHostFree(x->h.stage);
+    if (x->h.sess_h) (void)hipHostFree(x->h.sess_h);
+    if (x->h.sess_d) (void)hipFree(x->h.sess_d);
     if (x->h.ev_stage) (void)hipEventDestroy(x->h.ev_stage);
     if (x->h.ev0) (void)hipEventDestroy(x->h.ev0);
     if (x->h.ev1) (void)hipEventDestroy(x->h.ev1);

@@ -43,6 +43,9 @@ struct GameState {
     int32_t has_resign2;
     int32_t min_free;                     // fewest free local ids the game ever had (high-water mark = L - min_free)
     int32_t ovf_hi;                       // overflow local ids [cap, cap + ovf_hi) have been backed at some time in this game
+    // sgo_session_analyze (csrc/sgo_session.hpp), written by the arming kernel: the search this slot was armed for is search-only
+    // (no resign test, no move: one record with action SGO_ACTION_ANALYSIS, then PH_HOLD) and runs an_rounds rounds
+    int32_t analysis, an_rounds;
 };
 
 struct Counters {
@@ -154,6 +157,10 @@ struct HostSide {  // not passed to kernels
     hipStream_t last_stream = nullptr;         // stream of the last sgo_step (records are drained behind it)
     bool lds_attr_set = false;                 // k_search's > 64 KiB dynamic-LDS attribute has been set
     bool lds_attr_session = false;             // ... and k_session_play's
+    // sgo_session_setup / sgo_session_report: a grow-only pair of buffers (pinned host block and its device twin) for move
+    // lists going in and reports coming out; both calls wait for their stream, so the pair is free again on return
+    uint8_t *sess_h = nullptr, *sess_d = nullptr;
+    size_t sess_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // bracket board_advance inside sgo_step
     double adv_ms = 0;
     long long adv_launches = 0, adv_positions = 0;

@@ -51,6 +51,13 @@ __device__ __forceinline__ void wave_argmax(F &score, int &idx) {
     }
 }
 
+// select_play's choice at temperature 0 (nomodel_self_play.py:138 `max((count, mean_value, index))`): child (n, q, i) beats the
+// best so far (bn, bq, bi; bi < 0 = none yet) on count, then mean, then the HIGHER index.  Shared by Search<S>::choose_move and
+// k_session_report (csrc/sgo_session.hpp).
+__device__ __forceinline__ bool child_beats(int n, float q, int i, int bn, float bq, int bi) {
+    return bi < 0 || n > bn || (n == bn && (q > bq || (q == bq && i > bi)));
+}
+
 template <int S>
 struct Eng {
     using G = Geo<S>;
@@ -409,7 +416,8 @@ struct Search {
         if (lane == 0) atomicAdd(&c.counters->total_evals, 1ull);
         // resign = resign_model1 if current == model1 else resign_model2 (nomodel_self_play.py:170-173)
         const bool use2 = c.cfg.two_model && st.cur_model == 1;
-        if (use2 ? (st.has_resign2 && st.value <= st.resign2) : (st.has_resign && st.value <= st.resign)) {
+        // a search-only slot (sgo_session_analyze) has no resign test
+        if (!st.analysis && (use2 ? (st.has_resign2 && st.value <= st.resign2) : (st.has_resign && st.value <= st.resign))) {
             // a session slot resigns without ending (sejonggo_nomodel.py:58-60 genmove): play_move records action -1 and holds
             if (st.session) { st.end_reason = 1; st.rounds_left = 0; st.phase = PH_SEARCH; }
             else finish(1);
@@ -434,7 +442,9 @@ struct Search {
             }
         }
         if (run) {
-            st.rounds_left = c.cfg.sims / c.cfg.energy;
+            st.rounds_left = st.analysis ? st.an_rounds : c.cfg.sims / c.cfg.energy;
+            // search-only: play_move finds end_reason set, as for a session that resigns, and records and holds without choosing
+            if (st.analysis) st.end_reason = 2;
             st.e_left = -1;
             st.original_player = white_to_play<S>(c.pos + e.ph(st.root_blk) * G::RW) ? -1 : 1;
             st.phase = PH_SEARCH;
@@ -566,9 +576,7 @@ struct Search {
                 float bm = 0;
                 for (int i = 0; i < G::A; i++) {
                     if (sN[i] < 0) continue;
-                    if (ba < 0 || sN[i] > bc || (sN[i] == bc && (sQ[i] > bm || (sQ[i] == bm && i > ba)))) {
-                        bc = sN[i]; bm = sQ[i]; ba = i;
-                    }
+                    if (child_beats(sN[i], sQ[i], i, bc, bm, ba)) { bc = sN[i]; bm = sQ[i]; ba = i; }
                 }
                 selected = ba;
             }
@@ -590,12 +598,12 @@ struct Search {
             r.game = g; r.game_seq = st.game_seq; r.move_n = st.move_n; r.action = selected;
             r.player = st.player; r.value = st.value;
             c.recs[ri] = r;
-            atomicAdd(&c.counters->total_moves, 1ull);
+            if (selected != SGO_ACTION_ANALYSIS) atomicAdd(&c.counters->total_moves, 1ull);   // a search-only record is no move
         }
         for (int i = lane; i < G::RW; i += 64) c.recPacked[(size_t)ri * G::RW + i] = c.pos[e.ph(st.root_blk) * G::RW + i];
         for (int i = lane; i < G::A; i += 64) {
             double p = 0;
-            if (selected >= 0 && e.legal_bit(st.root_blk, i)) p = st.root_f64 ? c.rootP64[(size_t)g * G::APAD + i] : (double)c.cP[sb + i];
+            if (selected != -1 && e.legal_bit(st.root_blk, i)) p = st.root_f64 ? c.rootP64[(size_t)g * G::APAD + i] : (double)c.cP[sb + i];
             c.recPolicy[(size_t)ri * G::A + i] = p;
         }
         return true;
@@ -729,14 +737,16 @@ struct Search {
     __device__ __forceinline__ void play_move() {
         if (st.halt_at == st.move_n) { st.phase = PH_DONE; run = false; return; }
         const size_t sb = e.slot_base(st.root_blk);
-        int selected = -1;
-        if (!st.end_reason) {                      // set here only by a session slot that resigns: no move is chosen
+        // end_reason is set here only by a session slot: 1 = it resigns (action -1, a zero policy row), 2 = its search was an
+        // analysis (action SGO_ACTION_ANALYSIS = -2, the root's prior row).  No move is chosen then.
+        int selected = -st.end_reason;
+        if (!st.end_reason) {
             const int err = choose_move(sb, selected);
             if (err) { fail(err); return; }
         }
         if (st.temperature == 1) st.i_uniform++;
         if (!record_move(sb, selected)) return;
-        // the resign record (action -1, a zero policy row) is all that happens: board, tree and move_n stay, the slot holds again
+        // the resign / analysis record is all that happens: board, tree and move_n stay, the slot holds again
         if (selected < 0) { st.end_reason = 0; st.phase = PH_HOLD; run = false; return; }
         st.n_moves = st.move_n + 1;
         const bool is_pass = (selected == G::N);

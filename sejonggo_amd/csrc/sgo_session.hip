@@ -1,4 +1,4 @@
-// sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play and sgo_session_genmove, the
+// sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip;
 // the kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
 // SejongGoEngine a GTP front-end drives.
@@ -34,6 +34,38 @@ static int stage_slots(sgo_ctx *x, const char *who, int n, const int32_t *slots,
     return SGO_OK;
 }
 
+// The arming behind sgo_session_genmove and sgo_session_analyze: all listed slots or none.
+static int arm_slots(sgo_ctx *x, const char *who, int n, const int32_t *slots, int analysis, int rounds, hipStream_t st) {
+    Ctx &c = x->c;
+    StageLayout L;
+    const int rc = stage_slots(x, who, n, slots, nullptr, nullptr, L, st);
+    if (rc != SGO_OK) return rc;
+    k_session_arm<<<dim3(1), dim3(1024), 0, st>>>(c, n, L, analysis, rounds);
+    SGO_HIP(hipGetLastError());
+    int32_t *hs = reinterpret_cast<int32_t *>(x->h.stage + L.first);
+    SGO_HIP(hipMemcpyAsync(hs, c.stage + L.first, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    if (hs[0] != SGO_OK) { set_error(std::string(who) + ": a listed slot is not a holding session; nothing was armed"); return hs[0]; }
+    return SGO_OK;
+}
+
+// The session buffer (HostSide::sess_h / sess_d) holds at least `bytes`: it only grows, so a caller that repeats a call of one
+// size allocates once.  Both users wait for their stream before they return, so nothing is in flight when it is replaced.
+static int session_buffer(sgo_ctx *x, size_t bytes) {
+    HostSide &h = x->h;
+    if (bytes <= h.sess_cap) return SGO_OK;
+    size_t cap = h.sess_cap ? h.sess_cap : 4096;
+    while (cap < bytes) cap *= 2;
+    if (h.sess_h) (void)hipHostFree(h.sess_h);
+    if (h.sess_d) (void)hipFree(h.sess_d);
+    h.sess_h = h.sess_d = nullptr;
+    h.sess_cap = 0;
+    SGO_HIP(hipHostMalloc((void **)&h.sess_h, cap, hipHostMallocDefault));
+    SGO_HIP(hipMalloc((void **)&h.sess_d, cap));
+    h.sess_cap = cap;
+    return SGO_OK;
+}
+
 extern "C" {
 
 int sgo_session_play(sgo_ctx *x, int n, const int32_t *slots, const int32_t *actions, const int32_t *colors, int32_t *status,
@@ -65,17 +97,112 @@ int sgo_session_play(sgo_ctx *x, int n, const int32_t *slots, const int32_t *act
 int sgo_session_genmove(sgo_ctx *x, int n, const int32_t *slots, void *stream) {
     if (!x || n < 0 || (n && !slots)) { set_error("sgo_session_genmove: bad argument"); return SGO_ERR_ARG; }
     if (n == 0) return SGO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return arm_slots(x, "sgo_session_genmove", n, slots, 0, 0, st);
+}
+
+int sgo_session_analyze(sgo_ctx *x, int n, const int32_t *slots, int sims, void *stream) {
+    if (!x || n < 0 || (n && !slots)) { set_error("sgo_session_analyze: bad argument"); return SGO_ERR_ARG; }
+    Ctx &c = x->c;
+    if (sims <= 0) sims = c.cfg.sims;
+    if (sims < c.cfg.energy) { set_error("sgo_session_analyze: fewer simulations than one round (energy) holds"); return SGO_ERR_ARG; }
+    if (n == 0) return SGO_OK;
+    return arm_slots(x, "sgo_session_analyze", n, slots, 1, sims / c.cfg.energy, (hipStream_t)stream);
+}
+
+int sgo_session_setup(sgo_ctx *x, int n, const int32_t *slots, const int32_t *n_moves, const int32_t *moves_off,
+                      const int32_t *actions, const int32_t *colors, int32_t *status, int32_t *fail_at, void *stream) {
+    if (!x || n < 0 || (n && (!slots || !n_moves || !moves_off || !status || !fail_at))) {
+        set_error("sgo_session_setup: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
     Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    StageLayout L;
-    const int rc = stage_slots(x, "sgo_session_genmove", n, slots, nullptr, nullptr, L, st);
+    if (n > c.G) { set_error("sgo_session_setup: more slots than the context has"); return SGO_ERR_ARG; }
+    std::vector<char> seen((size_t)c.G, 0);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_setup: slot out of range"); return SGO_ERR_ARG; }
+        if (seen[slots[i]]) { set_error("sgo_session_setup: a slot is listed twice"); return SGO_ERR_ARG; }
+        seen[slots[i]] = 1;
+        if (n_moves[i] < 0 || n_moves[i] > SGO_SETUP_MAX_MOVES(c.S) || moves_off[i] < 0 || (n_moves[i] && !actions)) {
+            set_error("sgo_session_setup: a move list is negative in length or longer than SGO_SETUP_MAX_MOVES");
+            return SGO_ERR_ARG;
+        }
+        total += (size_t)n_moves[i];
+    }
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    const SetupLayout L = setup_layout(n, total);
+    const int rc = session_buffer(x, L.total);
     if (rc != SGO_OK) return rc;
-    k_session_arm<<<dim3(1), dim3(1024), 0, st>>>(c, n, L);
+    // the lists are packed back to back in the pinned block (the caller's offsets need not be), then ONE copy takes them over
+    uint8_t *h = x->h.sess_h;
+    memcpy(h + L.slots, slots, sizeof(int32_t) * n);
+    memcpy(h + L.n_moves, n_moves, sizeof(int32_t) * n);
+    int32_t *ho = reinterpret_cast<int32_t *>(h + L.off), *ha = reinterpret_cast<int32_t *>(h + L.actions),
+            *hc = reinterpret_cast<int32_t *>(h + L.colors);
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        ho[i] = (int32_t)at;
+        for (int j = 0; j < n_moves[i]; j++) {
+            ha[at + j] = actions[(size_t)moves_off[i] + j];
+            hc[at + j] = colors ? colors[(size_t)moves_off[i] + j] : 0;
+        }
+        at += (size_t)n_moves[i];
+    }
+    SGO_HIP(hipMemcpyAsync(x->h.sess_d + L.slots, h + L.slots, L.total - L.slots, hipMemcpyHostToDevice, st));
+    SGO_DISPATCH(c.S, k_session_setup<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, x->h.sess_d, L));
     SGO_HIP(hipGetLastError());
-    int32_t *hs = reinterpret_cast<int32_t *>(x->h.stage + L.first);
-    SGO_HIP(hipMemcpyAsync(hs, c.stage + L.first, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipMemcpyAsync(h, x->h.sess_d, L.slots, hipMemcpyDeviceToHost, st));      // status and fail_at, adjacent
     SGO_HIP(hipStreamSynchronize(st));
-    if (hs[0] != SGO_OK) { set_error("sgo_session_genmove: a listed slot is not a holding session; nothing was armed"); return hs[0]; }
+    memcpy(status, h + L.status, sizeof(int32_t) * n);
+    memcpy(fail_at, h + L.fail_at, sizeof(int32_t) * n);
+    return SGO_OK;
+}
+
+int sgo_session_report(sgo_ctx *x, int n, const int32_t *slots, int K, int D, int32_t *status, int32_t *to_play,
+                       int32_t *root_count, float *root_value, float *root_mean, int32_t *n_children, int32_t *N, float *Q,
+                       float *P, int32_t *top_action, int32_t *pv, void *stream) {
+    if (!x || n < 0 || (n && (!slots || !status)) || K < 0 || K > SGO_REPORT_MAX_TOP || D < 0 || D > SGO_REPORT_MAX_DEPTH) {
+        set_error("sgo_session_report: bad argument (K <= SGO_REPORT_MAX_TOP, D <= SGO_REPORT_MAX_DEPTH)");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    if (n > c.G) { set_error("sgo_session_report: more slots than the context has"); return SGO_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_report: slot out of range"); return SGO_ERR_ARG; }
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    const size_t rw = report_words(c.A, K, D), head = al8(sizeof(int32_t) * (size_t)n), body = sizeof(int32_t) * rw * n;
+    const int rc = session_buffer(x, head + body);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    memcpy(h, slots, sizeof(int32_t) * n);
+    SGO_HIP(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, st));
+    SGO_DISPATCH(c.S, k_session_report<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, reinterpret_cast<const int32_t *>(d),
+                                                                            reinterpret_cast<int32_t *>(d + head), K, D));
+    SGO_HIP(hipGetLastError());
+    SGO_HIP(hipMemcpyAsync(h + head, d + head, body, hipMemcpyDeviceToHost, st));       // the one copy back
+    SGO_HIP(hipStreamSynchronize(st));
+    const size_t A = (size_t)c.A;
+    for (int i = 0; i < n; i++) {
+        const int32_t *o = reinterpret_cast<const int32_t *>(h + head) + rw * i;
+        const float *of = reinterpret_cast<const float *>(o);
+        status[i] = o[0];
+        if (o[0] != SGO_OK) continue;                       // the rows of a refused slot stay as the caller filled them
+        if (to_play) to_play[i] = o[1];
+        if (root_count) root_count[i] = o[2];
+        if (root_value) root_value[i] = of[3];
+        if (root_mean) root_mean[i] = of[4];
+        if (n_children) n_children[i] = o[5];
+        if (N) memcpy(N + A * i, o + 8, sizeof(int32_t) * A);
+        if (Q) memcpy(Q + A * i, o + 8 + A, sizeof(float) * A);
+        if (P) memcpy(P + A * i, o + 8 + 2 * A, sizeof(float) * A);
+        if (top_action && K) memcpy(top_action + (size_t)K * i, o + 8 + 3 * A, sizeof(int32_t) * K);
+        if (pv && K && D) memcpy(pv + (size_t)K * D * i, o + 8 + 3 * A + K, sizeof(int32_t) * K * D);
+    }
     return SGO_OK;
 }
 

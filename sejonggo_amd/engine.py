@@ -616,12 +616,13 @@ class SessionEngine(SelfPlayEngine):
                                                  _lib.ptr(status), self._stream_ptr()), "sgo_session_play")
         return status
 
-    def genmove_step_bound(self, n_slots):
-        """Steps a genmove may take.  The step after the arming asks for the root evaluation; every later step consumes at
-        least one evaluation of the slot (a round that is blocked waits for a leaf it requested in that very step), a move
-        consumes 1 + sims of them at most, and one more step plays the move: sims + 3.  On top, one step per round
-        (sims // energy) and per listed slot as slack."""
-        return self.sims + 3 + self.sims // self.E + n_slots
+    def genmove_step_bound(self, n_slots, sims=None):
+        """Steps a genmove (or an analysis of `sims` simulations) may take.  The step after the arming asks for the root
+        evaluation; every later step consumes at least one evaluation of the slot (a round that is blocked waits for a leaf it
+        requested in that very step), a move consumes 1 + sims of them at most, and one more step plays the move: sims + 3.
+        On top, one step per round (sims // energy) and per listed slot as slack."""
+        sims = int(sims or self.sims)
+        return sims + 3 + sims // self.E + n_slots
 
     def arm(self, slots):
         """First half of genmove: the listed holding sessions start their move's search with the next step.  Raises SgoError
@@ -639,10 +640,11 @@ class SessionEngine(SelfPlayEngine):
         self.arm(slots)
         return self.wait(slots)
 
-    def wait(self, slots):
-        """Second half of genmove: steps until every listed (armed) slot has recorded its move; the moves as genmove returns them."""
+    def wait(self, slots, sims=None):
+        """Second half of genmove / analyze: steps until every listed (armed) slot has recorded its move; the moves as genmove
+        returns them.  sims: what the slots were armed with (arm_analysis), for the step bound; None = the context's."""
         got, pending = {}, [int(s) for s in slots]
-        bound = self.genmove_step_bound(len(slots))
+        bound = self.genmove_step_bound(len(slots), sims)
         for _ in range(bound):
             if self.step().n_records > 0:
                 self.drain()
@@ -653,7 +655,82 @@ class SessionEngine(SelfPlayEngine):
             if not pending:
                 return [(int(got[int(s)]['action']), got[int(s)]['value'], got[int(s)]['policy']) for s in slots]
         raise _lib.SgoError("genmove: slots %s recorded no move within %d steps (sims %d, energy %d)"
-                            % (pending, bound, self.sims, self.E))
+                            % (pending, bound, sims or self.sims, self.E))
+
+    # ------------------------------------------------------------------ set-up, search-only analysis, reports
+    def setup(self, slots, move_lists, color_lists=None):
+        """The listed holding sessions are set to positions: the empty board, then move_lists[i] (actions y * S + x, pass =
+        S * S) with color_lists[i] (0 / None = the side to move, +1 black, -1 white; an out-of-turn colour places set-up and
+        handicap stones) -- what `open` and one `play` per move leave, in ONE launch and one copy for all slots
+        (sgo_session_setup).  The tree is dropped, the resign threshold kept.  Returns (status, fail_at): per slot 0 and -1, or
+        the refusal (SGO_ERR_RANGE / SGO_ERR_OCCUPIED at move fail_at, SGO_ERR_STATE: no holding session); a refused slot is
+        unchanged.  Raises SgoError (nothing runs) for a slot listed twice or a list longer than 4 * S * S."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(slots)
+        if len(move_lists) != n or (color_lists is not None and len(color_lists) != n):
+            raise ValueError("setup: one move list (and one colour list) per slot")
+        n_moves = np.array([len(m) for m in move_lists], dtype=np.int32)
+        off = np.zeros(n, np.int32)
+        if n:
+            off[1:] = np.cumsum(n_moves)[:-1]
+        total = int(n_moves.sum())
+        actions, colors = np.zeros(max(1, total), np.int32), np.zeros(max(1, total), np.int32)
+        for i in range(n):
+            actions[off[i]:off[i] + n_moves[i]] = np.asarray(move_lists[i], dtype=np.int32)
+            if color_lists is not None and color_lists[i] is not None:
+                if len(color_lists[i]) != n_moves[i]:
+                    raise ValueError("setup: one colour per move")
+                colors[off[i]:off[i] + n_moves[i]] = [c or 0 for c in color_lists[i]]
+        status, fail_at = np.zeros(n, np.int32), np.full(n, -1, np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_setup(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(n_moves), _lib.ptr(off),
+                                                  _lib.ptr(actions), _lib.ptr(colors), _lib.ptr(status), _lib.ptr(fail_at),
+                                                  self._stream_ptr()), "sgo_session_setup")
+        self._reset_records(slots[status == 0], None)
+        return status, fail_at
+
+    def arm_analysis(self, slots, sims=None):
+        """First half of analyze: the listed holding sessions start a search-only search of `sims` simulations (None: the
+        context's) with the next step.  Raises SgoError (and arms nothing) when a listed slot is no holding session or sims is
+        below the energy."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_analyze(self.ctx, C.c_int(len(slots)), _lib.ptr(slots), C.c_int(int(sims or 0)),
+                                                    self._stream_ptr()), "sgo_session_analyze")
+
+    def analyze(self, slots, sims=None):
+        """Searches the listed holding sessions without moving (sgo_session_analyze): root evaluation, no resign test, new_tree
+        when the root is unexpanded, sims // energy rounds.  Boards, move numbers and trees stay; the searched tree is kept, so
+        a second analyze deepens it, a genmove searches on top of it and a play follows into it.  Returns, per slot,
+        (SGO_ACTION_ANALYSIS, value, prior_row) -- the record a genmove from this root would write, without a move; read the
+        result with `report`."""
+        self.arm_analysis(slots, sims)
+        return self.wait(slots, sims)
+
+    def report(self, slots, top=5, depth=8):
+        """The search results of the listed holding sessions in one launch and one copy back (sgo_session_report), as a dict of
+        arrays: status [n] (SGO_ERR_STATE: not a holding session; that slot's rows hold -1 / 0 / NaN fillers), to_play,
+        root_count, root_value, root_mean, n_children [n]; N [n][A] (-1: no child), Q, P [n][A] float32; top_action [n][top]:
+        the best children by (count, mean, higher index), -1 padded; pv [n][top][depth]: the principal variation below each."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n, A = len(slots), self.A
+        out = {"status": np.zeros(n, np.int32), "to_play": np.zeros(n, np.int32), "root_count": np.zeros(n, np.int32),
+               "root_value": np.full(n, np.nan, np.float32), "root_mean": np.full(n, np.nan, np.float32),
+               "n_children": np.zeros(n, np.int32), "N": np.full((n, A), -1, np.int32), "Q": np.zeros((n, A), np.float32),
+               "P": np.zeros((n, A), np.float32), "top_action": np.full((n, top), -1, np.int32),
+               "pv": np.full((n, top, depth), -1, np.int32)}
+        return self.report_into(slots, out)
+
+    def report_into(self, slots, out):
+        """`report` into caller-filled arrays (keys and shapes as `report` makes them): rows of refused slots are not written."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        top, depth = out["pv"].shape[1:]
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_report(
+                self.ctx, C.c_int(len(slots)), _lib.ptr(slots), C.c_int(top), C.c_int(depth), *(
+                    [_lib.ptr(out[k]) for k in ("status", "to_play", "root_count", "root_value", "root_mean", "n_children", "N", "Q",
+                                                "P", "top_action", "pv")] + [self._stream_ptr()])), "sgo_session_report")
+        return out
 
 
 class _SumStatus(object):

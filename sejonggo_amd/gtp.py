@@ -75,6 +75,22 @@ class SejongGoEngine(object):
         self.board, self.player = self.play(color, x, y)
         return x, y, policy_target, value, self.board, self.player
 
+    def analyze(self, sims=None):
+        """Search without moving, the comparator of the device engine's sgo_session_analyze: genmove's root prediction
+        (:60), no resign test, new_tree when there is no tree (:63-64), select_play's simulation loop for `sims` simulations
+        (None: mcts_simulations) with the chosen move discarded.  Board and move stay; the searched tree is kept.  Returns
+        (policy, value) of the root prediction."""
+        policy, value = put_predict_request(self.model_indicator, self.board, response_now=True)
+        if not self.mcts_tree or not self.mcts_tree['subtree']:
+            self.mcts_tree = new_tree(policy, self.board, add_noise=self.add_noise)
+        keep = conf['MCTS_SIMULATIONS']
+        conf['MCTS_SIMULATIONS'] = sims or self.mcts_simulations
+        try:
+            select_play(self.board, conf['ENERGY'], self.mcts_tree, 0, self.model_indicator, self.process_id)
+        finally:
+            conf['MCTS_SIMULATIONS'] = keep
+        return policy, value
+
 
 class DeviceSejongGoEngine(object):
     """SejongGoEngine on the device engine: the game is a session slot of an engine.SessionEngine (tree, rules and search on
@@ -82,7 +98,9 @@ class DeviceSejongGoEngine(object):
     it), move, mcts_tree, model, close.
     `engine` / `slot` put it on a slot of an existing SessionEngine (many games in one context); otherwise it owns a context
     of one game (engine_kw go to SessionEngine).  Temperature 0 and no noise only: the host engine remains for the rest.
-    One deviation from the reference: a `play` with an out-of-turn colour drops the tree (include/sgo.h)."""
+    One deviation from the reference: a `play` with an out-of-turn colour drops the tree (include/sgo.h).
+    `moves` is the list of (action, colour) since clear_board -- external plays and generated moves, not resigns -- from which
+    `undo` and `load` set the slot up again in one launch (engine.SessionEngine.setup); `analyze` searches without moving."""
 
     def __init__(self, mcts_simulations, board=None, resign=None, temperature=0, add_noise=False, net=None, engine=None, slot=0,
                  **engine_kw):
@@ -109,6 +127,8 @@ class DeviceSejongGoEngine(object):
             engine = SessionEngine(net, sims=mcts_simulations, **engine_kw)
         self.engine = engine
         self.size = engine.S
+        self.moves = []
+        self.n_setup = 0                    # leading entries of `moves` that are set-up stones of a loaded record: undo stops there
         self.engine.open([self.slot], resign=resign)
 
     @property
@@ -126,6 +146,7 @@ class DeviceSejongGoEngine(object):
             raise ValueError("a session starts from the empty board")
         self.engine.open([self.slot], resign=self.resign)
         self.player = 1
+        self.moves, self.n_setup = [], 0
 
     @property
     def mcts_tree(self):
@@ -155,6 +176,7 @@ class DeviceSejongGoEngine(object):
             raise ValueError("play %s at (%d, %d) refused: %d (%s)" % (color, x, y, status, {
                 -101: "the point is occupied", -102: "outside the board", -203: "the slot is not a holding session"}.get(status, "?")))
         self.move += 1
+        self.moves.append((index, int(color or 0)))
         board = self.board
         self.player = -int(board[0, 0, 0, -1])           # make_play returns the player who moved (play.py:226-242)
         return board, self.player
@@ -168,8 +190,45 @@ class DeviceSejongGoEngine(object):
             return 0, self.size + 1, policy, value, board, self.player
         x, y = index2coord(action, self.size)
         self.move += 1
+        self.moves.append((int(action), 0))
         self.player = int(board[0, 0, 0, -1])
         return x, y, policy, value, self.board, self.player
+
+    def load(self, moves, colors=None, n_setup=0):
+        """The slot is set to the empty board followed by `moves` (actions y * S + x, pass = S * S; colors: 0 / None = the side to
+        move, +1 / -1 explicit -- an out-of-turn colour places set-up and handicap stones) in one launch; the tree is dropped.
+        A refused list (an occupied point, an action off the board) raises ValueError and leaves the game as it was.
+        n_setup: the first n_setup entries are set-up stones (AB / AW of a record), which `undo` does not take back."""
+        moves = [int(a) for a in moves]
+        colors = [0] * len(moves) if colors is None else [int(c or 0) for c in colors]
+        status, fail_at = self.engine.setup([self.slot], [moves], [colors])
+        if int(status[0]):
+            raise ValueError("move list refused at index %d: %d" % (int(fail_at[0]), int(status[0])))
+        self.moves, self.n_setup = list(zip(moves, colors)), int(n_setup)
+        self.move = 1 + len(moves)
+        board = self.board
+        self.player = -int(board[0, 0, 0, -1]) if moves else 1
+        return board, self.player
+
+    def undo(self):
+        """GTP undo: a set-up of the move list without its last entry (a resign is no entry).  ValueError when the list is empty."""
+        if len(self.moves) <= self.n_setup:
+            raise ValueError("cannot undo")
+        return self.load([a for a, _ in self.moves[:-1]], [c for _, c in self.moves[:-1]], n_setup=self.n_setup)
+
+    def analyze(self, sims=None):
+        """Search without moving (engine.SessionEngine.analyze): the tree is kept, a second call deepens it.  Returns (policy,
+        value): the root's prior row as a genmove would record it and the net's value; `report` reads the search."""
+        _, value, policy = self.engine.analyze([self.slot], sims)[0]
+        return policy, value
+
+    def report(self, top=5, depth=8):
+        """engine.SessionEngine.report for this game: a dict of arrays with one row."""
+        return self.engine.report([self.slot], top=top, depth=depth)
+
+
+class GTPFailure(Exception):
+    """A command that GTP answers with `? message` (undo on an empty game, a command the engine behind cannot serve)."""
 
 
 class GTPEngine(object):
@@ -189,8 +248,12 @@ class GTPEngine(object):
         return "2"
 
     def list_commands(self):
-        return "\n".join(["name", "version", "protocol_version", "list_commands", "boardsize", "komi", "play", "genmove",
-                          "clear_board", "quit"])
+        return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
+                          "genmove", "undo", "loadsgf", "clear_board", "sgo-analyze", "quit"])
+
+    def known_command(self, name=""):
+        # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
+        return "true" if name in self.list_commands().split("\n") or name in self.ALIASES.values() else "false"
 
     def boardsize(self, size):
         if int(size) != self.size:
@@ -235,17 +298,83 @@ class GTPEngine(object):
         self.sejong_engine.move = 1
         return ""
 
+    def _engine_method(self, name):
+        """undo / load / analyze / report exist on the device engine only"""
+        method = getattr(self.sejong_engine, name, None)
+        if method is None or not hasattr(self.sejong_engine, "load"):
+            raise GTPFailure("not supported")
+        return method
+
+    def undo(self):
+        undo = self._engine_method("undo")
+        try:
+            self.board, self.player = undo()
+        except ValueError:
+            raise GTPFailure("cannot undo")
+        return ""
+
+    def loadsgf(self, filename, move_number=None):
+        """GTP loadsgf: the main line of the record up to, not including, move `move_number` (all of it when absent); set-up
+        stones (AB / AW) are placed first and count as no move."""
+        load = self._engine_method("load")
+        from .sgfload import load_file
+        try:
+            game = load_file(filename)
+            last = None if move_number is None else int(move_number)
+        except (IOError, OSError, ValueError) as e:
+            raise GTPFailure("cannot load file" + (": %s" % e if isinstance(e, ValueError) else ""))
+        if game.size != self.size:
+            raise GTPFailure("cannot load file: the record is {0}x{0}, the configuration {1}x{1}".format(game.size, self.size))
+        moves = game.prefix(last - 1) if last is not None else game.moves
+        try:
+            n_setup = 0
+            while n_setup < len(moves) and game.setup[n_setup]:
+                n_setup += 1                          # the leading AB / AW stones: `undo` leaves them on the board
+            self.board, self.player = load([a for a, _ in moves], [c for _, c in moves], n_setup=n_setup)
+        except ValueError as e:
+            raise GTPFailure("cannot load file: %s" % e)
+        if game.komi is not None:
+            self._komi = game.komi
+        return ""
+
+    def _vertex(self, action):
+        return self.print_move(action % self.size, action // self.size)
+
+    def sgo_analyze(self, sims=None, top=5, depth=8):
+        """Private extension `sgo-analyze [sims]`: searches the position without moving and replies one line per top child --
+        vertex, visits, mean, prior, pv vertices."""
+        analyze, report = self._engine_method("analyze"), self._engine_method("report")
+        try:
+            analyze(int(sims) if sims is not None else None)
+        except ValueError:
+            raise GTPFailure("syntax error")
+        r = report(top=int(top), depth=int(depth))
+        lines = []
+        for k, a in enumerate(r["top_action"][0]):
+            if a < 0:
+                break
+            pv = " ".join(self._vertex(int(m)) for m in r["pv"][0][k] if m >= 0)
+            lines.append("%s visits %d mean %.4f prior %.4f pv %s" % (self._vertex(int(a)), int(r["N"][0][a]), float(r["Q"][0][a]),
+                                                                      float(r["P"][0][a]), pv))
+        return "\n".join(lines)
+
     def quit(self):
         return ""
+
+    ALIASES = {"sgo-analyze": "sgo_analyze"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")
         if not tokens or not tokens[0]:
             return ""
-        method = getattr(self, tokens[0], None)
-        if method is None or tokens[0].startswith("_"):
+        name = self.ALIASES.get(tokens[0], tokens[0])
+        method = getattr(self, name, None)
+        if method is None or name.startswith("_"):
             return "? unknown command\n\n"
-        result = method(*tokens[1:])
+        try:
+            result = method(*tokens[1:])
+        except GTPFailure as e:
+            return "? %s\n\n" % e
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 

@@ -1,0 +1,170 @@
+"""Batch review of a game record on the device engine: every reviewed position of an SGF file is one session slot, all of
+them set up in one launch (engine.SessionEngine.setup), searched together without moving (analyze: one net call per round for
+all positions) and read back in one launch (report).
+
+    python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
+                                           [--energy E] [--games n] [--json FILE]
+
+One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
+engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
+stones placed); with --every k the positions before moves 1, 1 + k, 1 + 2k, ... are reviewed.  Means are the search's own
+(the root player's view).  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+import argparse
+import json
+import string
+import sys
+
+import numpy as np
+
+from .conf import conf
+
+
+def vertex(action, size):
+    """GTP vertex of an action (letters skip 'I', rows count from the bottom), as gtp.GTPEngine.print_move."""
+    if action < 0:
+        return "none"
+    if action >= size * size:
+        return "pass"
+    x, y = action % size, action // size
+    return string.ascii_uppercase[x + 1 if x >= 8 else x] + str(size - y)
+
+
+def positions_of(game, every=1):
+    """[(move number m, the (action, colour) list in front of move m, move m itself)] for m = 1, 1 + every, ..."""
+    out = []
+    for m in range(1, game.n_moves + 1, max(1, int(every))):
+        before = game.prefix(m - 1)
+        out.append((m, before, game.prefix(m)[-1]))
+    return out
+
+
+def review(engine, game, sims=None, every=1, top=3, depth=8):
+    """Reviews `game` (sgfload.SgfGame) on `engine` (engine.SessionEngine; its board size must be the record's).  Returns one
+    dict per reviewed position: move_number, colour, played, played_visits, played_share, played_mean, best, best_visits,
+    best_mean, root_value, visits, top [{move, visits, mean, prior, pv}] -- or, for a position whose set-up was refused or whose
+    search failed, move_number, colour, played, error (the SGO_ERR_* code) and fail_at (the refused entry; -1: the search)."""
+    S = engine.S
+    if game.size != S:
+        raise ValueError("the record is {0}x{0}, the engine plays {1}x{1}".format(game.size, S))
+    todo, rows = positions_of(game, every), []
+    engine.open(np.arange(min(engine.G, len(todo)), dtype=np.int32))       # the slots become sessions once; setup re-uses them
+    for c0 in range(0, len(todo), engine.G):
+        chunk = todo[c0:c0 + engine.G]
+        slots = np.arange(len(chunk), dtype=np.int32)
+        status, fail_at = engine.setup(slots, [[a for a, _ in before] for _, before, _ in chunk],
+                                       [[c for _, c in before] for _, before, _ in chunk])
+        good = [int(s) for s in slots[status == 0]]
+        if good:
+            _search(engine, good, sims)
+        r = engine.report(slots, top=top, depth=depth)
+        failed = [int(s) for s in good if r["status"][s] != 0]
+        codes = dict(zip(failed, engine.results(failed)["done"])) if failed else {}
+        if failed:
+            engine.open(failed)                         # a failed slot takes no set-up: it serves the next chunk as a new session
+        for i, (m, _, (played, colour)) in enumerate(chunk):
+            if status[i] != 0 or r["status"][i] != 0:
+                # a refused set-up (fail_at = the entry) or a search that failed (fail_at -1; e.g. -201: out of tree blocks)
+                rows.append({"move_number": m, "colour": "B" if colour > 0 else "W", "played": vertex(played, S),
+                             "error": int(status[i] or codes.get(i) or r["status"][i]), "fail_at": int(fail_at[i])})
+                continue
+            N, Q, P = r["N"][i], r["Q"][i], r["P"][i]
+            visits = int(N[N > 0].sum())
+            best = int(r["top_action"][i][0]) if top > 0 else -1
+            # the mean of a move that is not the mover's to play (a record with two moves of one colour in a row) has no entry
+            in_tree = int(r["to_play"][i]) == colour and N[played] >= 0
+            rows.append({
+                "move_number": m, "colour": "B" if colour > 0 else "W", "played": vertex(played, S),
+                "played_visits": int(N[played]) if in_tree else 0,
+                "played_share": (float(N[played]) / visits) if in_tree and visits else 0.0,
+                "played_mean": float(Q[played]) if in_tree else 0.0,
+                "best": vertex(best, S), "best_visits": int(N[best]) if best >= 0 else 0,
+                "best_mean": float(Q[best]) if best >= 0 else 0.0,
+                "root_value": float(r["root_value"][i]), "visits": visits,
+                "top": [{"move": vertex(int(a), S), "visits": int(N[a]), "mean": float(Q[a]), "prior": float(P[a]),
+                         "pv": [vertex(int(v), S) for v in r["pv"][i][k] if v >= 0]}
+                        for k, a in enumerate(r["top_action"][i]) if a >= 0]})
+    return rows
+
+
+def _search(engine, slots, sims):
+    """analyze, except that a slot whose search fails (its tree outgrew its blocks) does not end the review: the other slots
+    search on to the end, the failed one does not hold afterwards and its report says so."""
+    from ._lib import SgoError
+    keep = getattr(engine, "raise_on_error", True)
+    engine.raise_on_error = False
+    try:
+        engine.analyze(slots, sims)
+    except SgoError:
+        pass                # the step bound ran out on the failed slots; the others have recorded and hold
+    finally:
+        engine.raise_on_error = keep
+
+
+def format_row(row):
+    if "error" in row and row["fail_at"] < 0:
+        return "%4d %s %-4s  search failed (%d)" % (row["move_number"], row["colour"], row["played"], row["error"])
+    if "error" in row:
+        return "%4d %s %-4s  set-up refused (%d at entry %d)" % (row["move_number"], row["colour"], row["played"], row["error"],
+                                                                 row["fail_at"])
+    pv = " ".join(row["top"][0]["pv"]) if row["top"] else ""
+    return "%4d %s %-4s share %5.1f%% mean %+.4f  best %-4s mean %+.4f  pv %s" % (
+        row["move_number"], row["colour"], row["played"], 100.0 * row["played_share"], row["played_mean"], row["best"],
+        row["best_mean"], pv)
+
+
+def document(game, rows, sims, energy, net_name):
+    """The review as one JSON-serialisable document."""
+    return {"size": game.size, "komi": game.komi, "moves": game.n_moves, "sims": sims, "energy": energy, "net": net_name,
+            "positions": rows}
+
+
+def _net(kind, size):
+    if kind == "best":
+        from .predicting_queue_worker import get_model, init_predicting_workers
+        init_predicting_workers(conf['GPUs'][:1])
+        return get_model("BEST")
+    from .stub_nets import make_stub
+    return make_stub(kind, size)
+
+
+def main(argv=None, out=sys.stdout):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("sgf")
+    ap.add_argument("--sims", type=int, default=None, help="simulations per position (default: conf['MCTS_SIMULATIONS'])")
+    ap.add_argument("--every", type=int, default=1, help="review every k-th position")
+    ap.add_argument("--top", type=int, default=3)
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--net", default="best", choices=["best", "hash", "uniform"],
+                    help="best: the model the configuration names; hash / uniform: the stub nets (no weights needed)")
+    ap.add_argument("--energy", type=int, default=None)
+    ap.add_argument("--games", type=int, default=None, help="session slots = positions per chunk (default: as many as reviewed, at most 1024)")
+    ap.add_argument("--symmetry", default="random1", choices=["random1", "avg8", "identity"])
+    ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
+    a = ap.parse_args(argv)
+    from .engine import SessionEngine
+    from .sgfload import load_file
+    game = load_file(a.sgf)
+    sims = a.sims or conf['MCTS_SIMULATIONS']
+    energy = a.energy or min(conf['ENERGY'], sims)
+    n_pos = len(positions_of(game, a.every))
+    net = _net(a.net, game.size)
+    eng = SessionEngine(net, size=game.size, n_games=a.games or max(1, min(1024, n_pos)), sims=sims, energy=energy,
+                        komi=game.komi if game.komi is not None else conf['KOMI'], symmetry=a.symmetry)
+    try:
+        rows = review(eng, game, sims=sims, every=a.every, top=a.top, depth=a.depth)
+    finally:
+        eng.close()
+        if a.net == "best":
+            from .predicting_queue_worker import destroy_predicting_workers
+            destroy_predicting_workers(conf['GPUs'][:1])
+    for row in rows:
+        out.write(format_row(row) + "\n")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net)), f, indent=1, sort_keys=True)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
