@@ -48,7 +48,8 @@ extern "C" {
  * library it loaded and refuses a mismatch (sejonggo_amd/_lib.py load(); INTEGRATION.md §B does the same).
  *   1: round 1.   2: sgo_start_games(+stream), sgo_game_result.first_model (40 bytes), sgo_config.two_model,
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
- *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*). */
+ *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
+ *   the "policy rollouts" section (sgo_rollout_*). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -412,6 +413,65 @@ int sgo_session_analyze(sgo_ctx *ctx, int n, const int32_t *slots, int sims, voi
 int sgo_session_report(sgo_ctx *ctx, int n, const int32_t *slots, int K, int D, int32_t *status, int32_t *to_play,
                        int32_t *root_count, float *root_value, float *root_mean, int32_t *n_children, int32_t *N, float *Q,
                        float *P, int32_t *top_action, int32_t *pv, void *stream);
+
+/* ---- policy rollouts: ownership, final score and dead stones from many policy-sampled play-outs -------------------------- */
+/* How did the game end?  sgo_score_dev / get_winner (play.py:274-292) count every stone on the board as alive.  A ROLLOUT object
+ * plays a position out many times with the net's policy -- thousands of tree-less games, one sampled move per net call -- and
+ * counts who ends up holding each point (csrc/sgo_rollout.hip).  The caller's loop is
+ *     sgo_rollout_start*;  while (n_live) { sgo_rollout_list -> the net on those rows -> sgo_rollout_step; }  sgo_rollout_result
+ * (INTEGRATION.md shows it with sgo_net_predict_packed_dev).  One object per caller; not thread-safe.
+ *
+ * Semantics, all integer.  A rollout is a packed record, a ply counter, a consecutive-pass counter and a global id
+ * g = src * per_src + j (j < per_src).  One step does, for every live rollout: the legal set of its position (play.py:71-104
+ * legal_moves, ko approximation included).  No legal board point: it passes (pass counter + 1; its policy row is ignored).
+ * Otherwise every legal point a < S*S weighs w[a] = floor(clamp(p[a]) * 2^20) + 1, where clamp(p) = p for 0 < p <= 1, 1 for p > 1
+ * or +inf, 0 for anything not > 0 (NaN, negatives, +-0); illegal points weigh 0 and the row's pass entry is never used (while a
+ * board move exists a rollout does not pass); total = sum of w (< 2^29); t = (uint64(r) * total) >> 32 with r = draw(seed, g,
+ * ply); the move is the smallest a with w[0] + ... + w[a] > t, and the pass counter returns to 0.  The move is played with
+ * make_play's rules (play.py:226-242) and ply is incremented.  The rollout ENDS when the pass counter reaches 2 or ply ==
+ * max_plies (<= 0: 2*S*S, the reference's num_moves); passes in the starting position's history do not count; one that ends
+ * with fewer than two passes in a row is CAPPED.
+ *   mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32)
+ *   draw(seed, g, ply) = mix(mix(seed ^ (g * 0x9E3779B9)) + ply * 0x85EBCA6B)
+ * At its end a rollout is scored as play.py:244-292 does: a point is black's if it holds a black stone or is empty and reached
+ * by black only, the same for white; empty points reached by both or by neither are nobody's.  Its source receives +1 in
+ * black_own / white_own for each owned point and one entry of the sums (below), with integer atomics: results do not depend on
+ * the order in which rollouts are listed or finish.
+ * A policy row is what the net produced from the input transformed by sym_k, the convention of sgo_step; the step maps it back. */
+typedef struct sgo_rollout sgo_rollout;
+typedef struct sgo_rollout_status { int32_t n_live, n_done, steps, error; } sgo_rollout_status;
+
+/* Allocates everything once: 2 * max_rollouts records, the lists, the accumulators of max_sources sources, pinned host blocks.
+ * NULL + sgo_last_error() for an unsupported S, max_sources outside [1, max_rollouts] or when memory runs out. */
+sgo_rollout *sgo_rollout_create(int S, int max_rollouts, int max_sources, int device_id);
+void sgo_rollout_destroy(sgo_rollout *);
+/* Start n_src * per_src rollouts, per_src from each source record; counters and accumulators are zeroed; whatever ran before is
+ * abandoned.  One kernel (after one host-to-device copy for HOST records: sgo_rollout_start) queued on `stream`, no
+ * synchronisation.  sgo_rollout_start_dev: DEVICE records, source s = record d_index[s] (d_index NULL: record s), read when the
+ * stream reaches the kernel.  Afterwards n_live = n_src * per_src, and every live rollout is on the list every step.
+ * SGO_ERR_ARG (nothing runs, state and results untouched): n_src * per_src > max_rollouts, n_src > max_sources, n_src < 1 or
+ * per_src < 1. */
+int sgo_rollout_start(sgo_rollout *, int n_src, const uint32_t *records, int per_src, uint32_t seed, int max_plies, void *stream);
+int sgo_rollout_start_dev(sgo_rollout *, int n_src, const uint32_t *d_records, const int32_t *d_index, int per_src, uint32_t seed,
+                          int max_plies, void *stream);
+/* The sources are the root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), copied on the
+ * device; the context is only read.  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: the call then
+ * returns SGO_ERR_STATE and nothing starts.  Waits for `stream` once (the verdict comes back); use the stream the steps run on. */
+int sgo_rollout_start_sessions(sgo_rollout *, sgo_ctx *ctx, int n, const int32_t *slots, int per_src, uint32_t seed, int max_plies,
+                               int32_t *status, void *stream);
+/* What the net must evaluate now: *d_records = the object's record array, *d_index = the record index of every live rollout
+ * (n_live rows valid; row i of the policy handed to the next step belongs to entry i), for sgo_stem_packed_dev /
+ * sgo_net_predict_packed_dev / sgo_nn_pack_dev.  Records ping-pong and the step fills a second list: ask again after every
+ * step.  Returns the capacity of the list (max_rollouts). */
+int sgo_rollout_list(sgo_rollout *, const uint32_t **d_records, const int32_t **d_index);
+/* One ply of every live rollout from d_policy [n_live][S*S+1] float32 (device): ONE kernel, then the count of the next list goes
+ * to pinned host memory and `stream` is synchronised once to return *st.  No allocation, no device-wide synchronisation.
+ * SGO_ERR_STATE (nothing runs): before a start, or after n_live reached 0. */
+int sgo_rollout_step(sgo_rollout *, const float *d_policy, int sym_k, void *stream, sgo_rollout_status *st);
+/* HOST outputs of the first n_src sources, each may be NULL: black_own / white_own int32 [n_src][S*S]; sums int64 [n_src][8] =
+ * {black_wins, white_wins, draws (by the komi-free area counts), score_sum (sum of black - white), score_sq_sum, plies_sum,
+ * capped, rollouts}.  SGO_ERR_STATE while rollouts are live or before a start; SGO_ERR_ARG for more sources than were started. */
+int sgo_rollout_result(sgo_rollout *, int n_src, int32_t *black_own, int32_t *white_own, int64_t *sums);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

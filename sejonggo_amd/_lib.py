@@ -32,6 +32,8 @@ SYMBOLS = [
     "sgo_heads_packed_bytes", "sgo_heads_prepack_dev", "sgo_heads_dev", "sgo_net_create", "sgo_net_set_weights", "sgo_net_packed_tower",
     "sgo_net_predict_packed_dev", "sgo_net_destroy",
     "sgo_session_open", "sgo_session_play", "sgo_session_genmove", "sgo_session_setup", "sgo_session_analyze", "sgo_session_report",
+    "sgo_rollout_create", "sgo_rollout_destroy", "sgo_rollout_start", "sgo_rollout_start_dev", "sgo_rollout_start_sessions",
+    "sgo_rollout_list", "sgo_rollout_step", "sgo_rollout_result",
 ]
 
 
@@ -61,6 +63,10 @@ class GameResult(C.Structure):
     _fields_ = [("winner", C.c_int32), ("black", C.c_int32), ("white", C.c_double), ("end_reason", C.c_int32),
                 ("n_moves", C.c_int32), ("last_player", C.c_int32), ("done", C.c_int32), ("first_model", C.c_int32),
                 ("blocks_high_water", C.c_int32)]
+
+
+class RolloutStatus(C.Structure):
+    _fields_ = [("n_live", C.c_int32), ("n_done", C.c_int32), ("steps", C.c_int32), ("error", C.c_int32)]
 
 
 class NetWeights(C.Structure):
@@ -150,6 +156,17 @@ def load():
     lib.sgo_session_setup.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
     lib.sgo_session_analyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.sgo_session_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12
+    lib.sgo_rollout_create.argtypes = [C.c_int] * 4
+    lib.sgo_rollout_create.restype = C.c_void_p
+    lib.sgo_rollout_destroy.argtypes = [C.c_void_p]
+    lib.sgo_rollout_destroy.restype = None
+    lib.sgo_rollout_start.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p]
+    lib.sgo_rollout_start_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p]
+    lib.sgo_rollout_start_sessions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p,
+                                               C.c_void_p]
+    lib.sgo_rollout_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sgo_rollout_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RolloutStatus)]
+    lib.sgo_rollout_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

@@ -48,5 +48,6 @@ conf = {
     'COMPAT_LATEST_SYM': True,   # reproduce predicting_queue_worker.py:92: LATEST_SYM requests are answered by the BEST model
     'COMPAT_WINNER_MODEL': True, # reproduce nomodel_self_play.py:247: winner_model names the loser when model1 plays white
     'SELFPLAY_WORKER_ENGINE': 'sync',  # SelfPlayWorker: 'sync' = self_play.model_self_play like the reference, 'device' = device engine
+    'ROLLOUTS': 64,              # policy rollouts per position behind final_score / final_status_list / review --rollouts (rollout.py)
     'WRITE_NPZ_TWIN': True,      # without h5py: keep sample.npz beside the spec-written sample.h5
 }

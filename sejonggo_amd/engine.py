@@ -732,6 +732,31 @@ class SessionEngine(SelfPlayEngine):
                                                 "P", "top_action", "pv")] + [self._stream_ptr()])), "sgo_session_report")
         return out
 
+    # ------------------------------------------------------------------ policy rollouts: how the games ended
+    def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
+        """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's
+        policy (rollout.RolloutEngine over sgo_rollout_start_sessions) and returns the ownership counts and score sums, one row
+        per slot (rollout.result_row / point_owner / stone_status / final_score read them).  The slots are only read: boards,
+        trees and move numbers stay.  The rollout object is kept and grows with the largest request."""
+        from .rollout import RolloutEngine
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        per_src = int(per_src or conf.get('ROLLOUTS', 64))
+        need, r = len(slots) * per_src, getattr(self, "_rollout", None)
+        if r is None or r.max_rollouts < need or r.max_sources < len(slots) or r.symmetry != symmetry:
+            if r is not None:
+                r.close()
+            r = self._rollout = RolloutEngine(self.net, size=self.S, max_rollouts=max(need, 1), max_sources=max(len(slots), 1),
+                                              device=self.device.index or 0, symmetry=symmetry)
+        with self._on_stream():
+            return r.run(sessions=(self, slots), per_src=per_src, seed=seed, max_plies=max_plies)
+
+    def close(self):
+        r = getattr(self, "_rollout", None)
+        if r is not None:
+            r.close()
+            self._rollout = None
+        super(SessionEngine, self).close()
+
 
 class _SumStatus(object):
     """The status of a DualEngine step: counts summed over the halves, the first error with its slot in the whole population."""

@@ -226,6 +226,17 @@ class DeviceSejongGoEngine(object):
         """engine.SessionEngine.report for this game: a dict of arrays with one row."""
         return self.engine.report([self.slot], top=top, depth=depth)
 
+    def rollouts(self, per_src=None, seed=0):
+        """How the game ends from here: the position played out per_src times (None: conf['ROLLOUTS']) with the net's policy
+        (engine.SessionEngine.rollouts).  Returns this game's row of counts (rollout.result_row) and the stones on the board
+        (int8 [S, S], +1 black); board, tree and move number stay.  The answer is kept until the position changes."""
+        from .rollout import real_board, result_row
+        key = (tuple(self.moves), per_src, seed)
+        if getattr(self, "_rollout_cache", (None,))[0] != key:
+            row = result_row(self.engine.rollouts([self.slot], per_src=per_src, seed=seed), 0)
+            self._rollout_cache = (key, row, real_board(self.board))
+        return self._rollout_cache[1], self._rollout_cache[2]
+
 
 class GTPFailure(Exception):
     """A command that GTP answers with `? message` (undo on an empty game, a command the engine behind cannot serve)."""
@@ -249,7 +260,8 @@ class GTPEngine(object):
 
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
-                          "genmove", "undo", "loadsgf", "clear_board", "sgo-analyze", "quit"])
+                          "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
+                          "sgo-ownership", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -358,10 +370,34 @@ class GTPEngine(object):
                                                                       float(r["P"][0][a]), pv))
         return "\n".join(lines)
 
+    def final_score(self):
+        """GTP final_score from policy rollouts: the points two thirds of the rollouts give one colour, minus komi."""
+        from .rollout import final_score
+        row, _ = self._engine_method("rollouts")()
+        return final_score(row, float(self._komi))
+
+    def final_status_list(self, status=""):
+        """GTP final_status_list alive|dead|seki: the stones whose point the rollouts give to their own colour / to the
+        opponent / to neither."""
+        from .rollout import stone_status
+        rollouts = self._engine_method("rollouts")
+        if status not in ("alive", "dead", "seki"):
+            raise GTPFailure("syntax error")
+        row, stones = rollouts()
+        return " ".join(self._vertex(a) for a in sorted(stone_status(row, stones)[status]))
+
+    def sgo_ownership(self):
+        """Private extension `sgo-ownership`: S lines of S signed per-mille values from the top row down, black positive:
+        (black_own - white_own) * 1000 / rollouts, rounded towards zero."""
+        row, _ = self._engine_method("rollouts")()
+        R = max(1, int(row["rollouts"]))
+        d = (np.asarray(row["black_own"], dtype=np.int64) - np.asarray(row["white_own"], dtype=np.int64)).reshape(self.size, self.size)
+        return "\n".join(" ".join("%d" % (int(np.sign(v)) * (1000 * abs(int(v)) // R)) for v in line) for line in d)
+
     def quit(self):
         return ""
 
-    ALIASES = {"sgo-analyze": "sgo_analyze"}      # GTP private extensions carry a hyphen; methods cannot
+    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -3,12 +3,14 @@ them set up in one launch (engine.SessionEngine.setup), searched together withou
 all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
-                                           [--energy E] [--games n] [--json FILE]
+                                           [--energy E] [--games n] [--json FILE] [--rollouts R]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
 stones placed); with --every k the positions before moves 1, 1 + k, 1 + 2k, ... are reviewed.  Means are the search's own
-(the root player's view).  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+(the root player's view).  --rollouts R plays every reviewed position out R times with the net's policy (rollout.py; all
+positions of a chunk in one batch) and adds the score lead (mean of black - white over the rollouts, minus komi), black's share
+of the rollouts won on the board (komi aside) and the number of stones judged dead.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -38,11 +40,13 @@ def positions_of(game, every=1):
     return out
 
 
-def review(engine, game, sims=None, every=1, top=3, depth=8):
+def review(engine, game, sims=None, every=1, top=3, depth=8, rollouts=0, komi=None, rollout_seed=0):
     """Reviews `game` (sgfload.SgfGame) on `engine` (engine.SessionEngine; its board size must be the record's).  Returns one
     dict per reviewed position: move_number, colour, played, played_visits, played_share, played_mean, best, best_visits,
     best_mean, root_value, visits, top [{move, visits, mean, prior, pv}] -- or, for a position whose set-up was refused or whose
-    search failed, move_number, colour, played, error (the SGO_ERR_* code) and fail_at (the refused entry; -1: the search)."""
+    search failed, move_number, colour, played, error (the SGO_ERR_* code) and fail_at (the refused entry; -1: the search).
+    rollouts > 0 adds rollout_lead, rollout_black_wins and rollout_dead (the module's text; komi None: the record's, else the
+    configuration's)."""
     S = engine.S
     if game.size != S:
         raise ValueError("the record is {0}x{0}, the engine plays {1}x{1}".format(game.size, S))
@@ -54,6 +58,7 @@ def review(engine, game, sims=None, every=1, top=3, depth=8):
         status, fail_at = engine.setup(slots, [[a for a, _ in before] for _, before, _ in chunk],
                                        [[c for _, c in before] for _, before, _ in chunk])
         good = [int(s) for s in slots[status == 0]]
+        played_out = _rollouts(engine, good, rollouts, komi, rollout_seed) if good and rollouts > 0 else {}
         if good:
             _search(engine, good, sims)
         r = engine.report(slots, top=top, depth=depth)
@@ -83,7 +88,25 @@ def review(engine, game, sims=None, every=1, top=3, depth=8):
                 "top": [{"move": vertex(int(a), S), "visits": int(N[a]), "mean": float(Q[a]), "prior": float(P[a]),
                          "pv": [vertex(int(v), S) for v in r["pv"][i][k] if v >= 0]}
                         for k, a in enumerate(r["top_action"][i]) if a >= 0]})
+            rows[-1].update(played_out.get(i, {}))
     return rows
+
+
+def _rollouts(engine, slots, per_src, komi, seed):
+    """{slot: the rollout fields of its row}: one batch over all listed slots (sgo_rollout_start_sessions); the slots are only
+    read, so the search that follows starts from what the set-up left."""
+    from .engine import unpack_positions
+    from .rollout import real_board, result_row, stone_status
+    res = engine.rollouts(slots, per_src=per_src, seed=seed)
+    boards = unpack_positions(res["records"], engine.S)
+    out = {}
+    for k, s in enumerate(slots):
+        row = result_row(res, k)
+        R = max(1, row["rollouts"])
+        out[s] = {"rollout_lead": row["score_sum"] / float(R) - float(komi),
+                  "rollout_black_wins": row["black_wins"] / float(R),
+                  "rollout_dead": len(stone_status(row, real_board(boards[k:k + 1]))["dead"])}
+    return out
 
 
 def _search(engine, slots, sims):
@@ -107,15 +130,21 @@ def format_row(row):
         return "%4d %s %-4s  set-up refused (%d at entry %d)" % (row["move_number"], row["colour"], row["played"], row["error"],
                                                                  row["fail_at"])
     pv = " ".join(row["top"][0]["pv"]) if row["top"] else ""
-    return "%4d %s %-4s share %5.1f%% mean %+.4f  best %-4s mean %+.4f  pv %s" % (
+    text = "%4d %s %-4s share %5.1f%% mean %+.4f  best %-4s mean %+.4f  pv %s" % (
         row["move_number"], row["colour"], row["played"], 100.0 * row["played_share"], row["played_mean"], row["best"],
         row["best_mean"], pv)
+    if "rollout_lead" in row:
+        text += "  | lead %+.1f black wins %5.1f%% dead %d" % (row["rollout_lead"], 100.0 * row["rollout_black_wins"], row["rollout_dead"])
+    return text
 
 
-def document(game, rows, sims, energy, net_name):
+def document(game, rows, sims, energy, net_name, rollouts=0):
     """The review as one JSON-serialisable document."""
-    return {"size": game.size, "komi": game.komi, "moves": game.n_moves, "sims": sims, "energy": energy, "net": net_name,
-            "positions": rows}
+    doc = {"size": game.size, "komi": game.komi, "moves": game.n_moves, "sims": sims, "energy": energy, "net": net_name,
+           "positions": rows}
+    if rollouts:
+        doc["rollouts"] = rollouts
+    return doc
 
 
 def _net(kind, size):
@@ -139,6 +168,7 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--energy", type=int, default=None)
     ap.add_argument("--games", type=int, default=None, help="session slots = positions per chunk (default: as many as reviewed, at most 1024)")
     ap.add_argument("--symmetry", default="random1", choices=["random1", "avg8", "identity"])
+    ap.add_argument("--rollouts", type=int, default=0, help="policy rollouts per position: score lead, black's win share, dead stones")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
@@ -151,7 +181,7 @@ def main(argv=None, out=sys.stdout):
     eng = SessionEngine(net, size=game.size, n_games=a.games or max(1, min(1024, n_pos)), sims=sims, energy=energy,
                         komi=game.komi if game.komi is not None else conf['KOMI'], symmetry=a.symmetry)
     try:
-        rows = review(eng, game, sims=sims, every=a.every, top=a.top, depth=a.depth)
+        rows = review(eng, game, sims=sims, every=a.every, top=a.top, depth=a.depth, rollouts=a.rollouts, komi=eng.komi)
     finally:
         eng.close()
         if a.net == "best":
@@ -161,7 +191,7 @@ def main(argv=None, out=sys.stdout):
         out.write(format_row(row) + "\n")
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net)), f, indent=1, sort_keys=True)
+            json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net), a.rollouts), f, indent=1, sort_keys=True)
             f.write("\n")
     return 0
 
