@@ -49,7 +49,7 @@ extern "C" {
  *   1: round 1.   2: sgo_start_games(+stream), sgo_game_result.first_model (40 bytes), sgo_config.two_model,
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
- *   the "policy rollouts" section (sgo_rollout_*). */
+ *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -472,6 +472,61 @@ int sgo_rollout_step(sgo_rollout *, const float *d_policy, int sym_k, void *stre
  * {black_wins, white_wins, draws (by the komi-free area counts), score_sum (sum of black - white), score_sq_sum, plies_sum,
  * capped, rollouts}.  SGO_ERR_STATE while rollouts are live or before a start; SGO_ERR_ARG for more sources than were started. */
 int sgo_rollout_result(sgo_rollout *, int n_src, int32_t *black_own, int32_t *white_own, int64_t *sums);
+
+/* ---- game records: whole move lists replayed into one packed record per ply, and a net scored on the recorded moves ---------- */
+/* A RECORDS object turns a collection of game records into device data without an engine context (csrc/sgo_records.hip).  The
+ * caller's loop is
+ *     sgo_records_replay;  for slices of its list of record indices { sgo_net_predict_packed_dev -> sgo_records_score_dev; }
+ * (INTEGRATION.md shows it).  One object per caller; not thread-safe.
+ *
+ * Replay.  Game g is a list of n_entries[g] entries, actions / colors [off[g], off[g] + n_entries[g]): action = y * S + x, S * S =
+ * pass; colors 0 = the side to move, +1 black / -1 white explicit (colors NULL: all 0), exactly what sgo_session_setup takes and
+ * played as it plays them: from the empty board with black to move, make_play's rules (play.py:226-242: suicide executed, passes
+ * are moves; a recorded move is PLAYED, not filtered by the legal set, so a ko recapture goes through), an out-of-turn colour is
+ * how set-up and handicap stones are placed.  The lists lie BACK TO BACK: off[g] = n_entries[0] + ... + n_entries[g-1].
+ * Game g owns the records base_g .. base_g + n_entries[g] with base_g = off[g] + g: record base_g + j is the position BEFORE
+ * entry j (record base_g is the empty board), record base_g + n_entries[g] is the final position.  Every record has its legal
+ * bitset (play.py:71-104, sgo_plane_words(S) words, bit a = action a is legal, the pass bit always set) at the same index of a
+ * parallel array.  The records are what sgo_stem_packed_dev / sgo_net_predict_packed_dev / sgo_nn_pack_dev / sgo_unpack_dev read.
+ * REFUSAL: entry j off the board (outside [0, S*S]) gives status[g] = SGO_ERR_RANGE, on a stone SGO_ERR_OCCUPIED, with fail_at[g]
+ * = j; game g ends there: records base_g .. base_g + j are valid, nothing after them is written, and every other game of the call
+ * goes through.  Otherwise status[g] = SGO_OK and fail_at[g] = -1.
+ *
+ * Score.  Per listed row i: the record index d_index[i], the recorded action t = d_target[i], z = d_z[i] in {+1, -1, 0} (the
+ * result seen from the mover; 0 = unknown), a bucket d_bucket[i] in [0, n_buckets), row i of d_policy [n][S*S+1] and d_value [n]
+ * as the net produced them from the record transformed by sym_k (sgo_step's convention; the row is mapped back as
+ * sgo_sym_invert_policy does: p[a] = d_policy[i][SWAP_k[a]]).  With key(a) = p[a], a NaN taken as -inf, and the candidates = the
+ * legal set of the record (pass included) united with {t}:
+ *     rank     = #{candidates a != t : key(a) > key(t) or (key(a) == key(t) and a < t)}
+ *     best     = the legal action with the largest key, the lowest index among equals
+ *     p_target = p[t], the float copied
+ *     flags    bit 0: t is in the legal set
+ * and the int64 counters [n_buckets][8] of the row's bucket grow (integer atomics) by {1, rank == 0, rank < 5, t not legal,
+ * z != 0, z != 0 and the value agrees (v > 0 and z > 0, or v < 0 and z < 0), 0, 0}.  A row whose record index, target or bucket is
+ * out of range is SKIPPED: rank = best = -1, p_target = 0, flags = 2, no counter moves.  Nothing depends on the order of the rows;
+ * sums of floats (cross-entropy, squared error) are the caller's, from p_target and the values. */
+typedef struct sgo_records sgo_records;
+/* Allocates everything once: max_entries + max_games records and legal bitsets, the staging block of the move lists and its
+ * pinned host twin (verdicts included).  NULL + sgo_last_error() for an unsupported S, max_games < 1, max_entries < 0 or when
+ * memory runs out. */
+sgo_records *sgo_records_create(int S, int max_games, int max_entries, int device_id);
+void sgo_records_destroy(sgo_records *);
+/* ONE host-to-device copy of all lists and ONE launch (one half-wavefront per game), then `stream` is waited for once to return
+ * status[n_games] and fail_at[n_games] (HOST).  Whatever an earlier call left in the records is overwritten from record 0 on.
+ * SGO_ERR_ARG (nothing runs, records and legal bitsets untouched): a negative length, a list longer than
+ * SGO_SETUP_MAX_MOVES(S), offsets that are not back to back, more games than max_games or more entries than max_entries.
+ * n_games == 0 is a no-op. */
+int sgo_records_replay(sgo_records *, int n_games, const int32_t *n_entries, const int32_t *off, const int32_t *actions,
+                       const int32_t *colors, int32_t *status, int32_t *fail_at, void *stream);
+/* *d_records = the record array (sgo_packed_words(S) words each), *d_legal = the legal bitsets (sgo_plane_words(S) words each);
+ * either may be NULL.  Returns the capacity in records (max_entries + max_games). */
+int sgo_records_list(sgo_records *, const uint32_t **d_records, const uint32_t **d_legal);
+/* ONE launch on `stream` (one half-wavefront per row), no allocation, no synchronisation; every pointer is DEVICE memory, outputs
+ * [n] each, d_counters int64 [n_buckets][8], zeroed by the caller (launches accumulate).  n == 0 is a no-op.  SGO_ERR_ARG: sym_k
+ * outside [0, 7], n < 0, n_buckets < 1, a NULL pointer. */
+int sgo_records_score_dev(sgo_records *, int n, const int32_t *d_index, const int32_t *d_target, const int32_t *d_z,
+                          const int32_t *d_bucket, int n_buckets, const float *d_policy, const float *d_value, int sym_k,
+                          int32_t *d_rank, int32_t *d_best, float *d_p_target, int32_t *d_flags, int64_t *d_counters, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

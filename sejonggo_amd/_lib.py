@@ -34,6 +34,7 @@ SYMBOLS = [
     "sgo_session_open", "sgo_session_play", "sgo_session_genmove", "sgo_session_setup", "sgo_session_analyze", "sgo_session_report",
     "sgo_rollout_create", "sgo_rollout_destroy", "sgo_rollout_start", "sgo_rollout_start_dev", "sgo_rollout_start_sessions",
     "sgo_rollout_list", "sgo_rollout_step", "sgo_rollout_result",
+    "sgo_records_create", "sgo_records_destroy", "sgo_records_replay", "sgo_records_list", "sgo_records_score_dev",
 ]
 
 
@@ -167,6 +168,14 @@ def load():
     lib.sgo_rollout_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sgo_rollout_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RolloutStatus)]
     lib.sgo_rollout_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sgo_records_create.argtypes = [C.c_int] * 4
+    lib.sgo_records_create.restype = C.c_void_p
+    lib.sgo_records_destroy.argtypes = [C.c_void_p]
+    lib.sgo_records_destroy.restype = None
+    lib.sgo_records_replay.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.sgo_records_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sgo_records_score_dev.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + \
+        [C.c_void_p] * 6
     _lib = lib
     return lib
 

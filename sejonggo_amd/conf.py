@@ -4,6 +4,7 @@ conf = {
     'MODEL_DIR': 'sp_models',
     'EVAL_DIR': 'sp_eval_games',
     'SELF_PLAY_DIR': 'sp_self_play_data',
+    'KGS_DATA_DIR': 'kgs_data',  # game records read by records.py (the reference's KGSSelfPlayWorker reads the same key)
     'LOG_DIR': 'logs',
     'TMP_DIR': 'temp',
     'GAMES_DIR': 'sp_eval_games',

@@ -1,0 +1,471 @@
+"""Game records as data (include/sgo.h "game records", csrc/sgo_records.hip): SGF collections replayed on the device into one
+packed record per ply, written out as supervised samples, and a net scored on the recorded moves.
+
+    python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
+                                        [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
+
+PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
+kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
+it, a one-hot policy target (the pass is the last entry) and the value target `+1 if winner == player else -1`, written as
+OUT/KGS/<game>/move_%03d/sample.h5 where the number is the index of the move's node on the main line (root = 0), the reference's
+`move_n`.  A game directory that exists is left alone, as the reference leaves it.
+
+--score is the strength measure that needs no games: how often the net's policy puts the recorded move first or among the top
+five of the candidates (the legal moves and the recorded one), the cross-entropy of the recorded moves, how often the sign of the
+value head agrees with the result, per bucket of `--bucket` moves (default 20) and in total.  The net reads the packed records
+the replay wrote (net.predict_packed); no input tensor is built for a net that can.
+
+ORIENTATION.  The project's own is kept, as review.py has it: x = the column letter, y = the row letter counted from the top.
+The reference feeds sgfmill's (row from the bottom, column) pairs into make_play(x, y): the same game under one fixed symmetry of
+the board.  That is not reproduced.
+
+RESULT.  The winner is read from RE ("B+..." / "W+..."); anything else is unknown.  The reference labels every move of such a
+record -1.  Here such records give no samples by default and their rows enter the score with z = 0, outside the value figures;
+--compat-unknown-result writes the reference's -1.
+
+ONE DEVIATION in the positions: the reference places only the root's AB stones (as black plays) and ignores AW.  Every AB / AW
+stone sgfload lists is placed here, in the node it stands in.
+
+A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
+skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
+(device memory, stream, the net)."""
+import argparse
+import collections
+import ctypes as C
+import json
+import os
+import random as pyrandom
+import sys
+
+import numpy as np
+
+from . import sgfload
+from .conf import conf
+
+Record = collections.namedtuple("Record", "name size entries setup nodes winner")
+COUNTERS = ("rows", "top1", "top5", "illegal", "value_rows", "value_agree")
+P_FLOOR = 2.0 ** -149          # the smallest float32 above zero: what a target probability that is not positive counts as
+
+
+def parse_record(text, name="game"):
+    """Record of one SGF text: entries [(action, colour)] as sgfload.loads gives them, setup [bool], nodes [int] (main-line
+    node index per entry), winner +1 / -1 / None."""
+    game = sgfload.loads(text)
+    nodes = sgfload.node_indices(text)
+    assert len(nodes) == len(game.moves)
+    return Record(name, game.size, list(game.moves), list(game.setup), nodes, sgfload.result_winner(sgfload.root_properties(text)))
+
+
+def max_entries_of(size):
+    return 4 * size * size           # SGO_SETUP_MAX_MOVES
+
+
+def read_path(path, size):
+    """(records, skipped) of a file or a directory (its *.sgf files, sorted).  skipped: {"unreadable": [names], "wrong_size":
+    [names], "too_long": [names]}."""
+    if os.path.isdir(path):
+        files = [os.path.join(path, f) for f in sorted(os.listdir(path)) if f.lower().endswith(".sgf")]
+    else:
+        files = [path]
+    records, skipped = [], {"unreadable": [], "wrong_size": [], "too_long": []}
+    for f in files:
+        name = os.path.basename(f).split(".")[0]       # KGSSelfPlayWorker.py:30
+        try:
+            with open(f, "r", errors="replace") as fh:
+                rec = parse_record(fh.read(), name)
+        except (ValueError, OSError, AssertionError):
+            skipped["unreadable"].append(name)
+            continue
+        if rec.size != size:
+            skipped["wrong_size"].append(name)
+        elif len(rec.entries) > max_entries_of(size):
+            skipped["too_long"].append(name)
+        else:
+            records.append(rec)
+    return records, skipped
+
+
+def value_targets(winner, colours, compat_unknown=False):
+    """(z int32 [n], has_sample bool [n]) for moves of the given colours in a record won by `winner` (+1 / -1 / None).
+    z = +1 if winner == colour else -1 (KGSSelfPlayWorker.py:97-99); an unknown result gives z = 0 and no sample, or with
+    `compat_unknown` the reference's -1 and a sample."""
+    colours = np.asarray(colours, dtype=np.int32)
+    if winner is None:
+        if compat_unknown:
+            return np.full(len(colours), -1, np.int32), np.ones(len(colours), bool)
+        return np.zeros(len(colours), np.int32), np.zeros(len(colours), bool)
+    return np.where(colours == winner, 1, -1).astype(np.int32), np.ones(len(colours), bool)
+
+
+def float_sums(p_target, value, z, bucket, n_buckets):
+    """(ce_sum, se_sum) float64 [n_buckets]: per bucket, row after row in the order given, -log(p) of the float32 target
+    probabilities taken to float64 (a p that is not positive counts as 2^-149, a p above 1 as 1) and (v - z)^2 over the rows with
+    z != 0."""
+    p = np.asarray(p_target, dtype=np.float32).astype(np.float64)
+    q = np.where(p > 0.0, np.minimum(p, 1.0), P_FLOOR)
+    ce_terms = -np.log(q)
+    v = np.asarray(value, dtype=np.float32).astype(np.float64)
+    zf = np.asarray(z, dtype=np.int32).astype(np.float64)
+    se_terms = np.where(zf != 0.0, (v - zf) * (v - zf), 0.0)
+    ce, se = np.zeros(n_buckets, np.float64), np.zeros(n_buckets, np.float64)
+    b = np.asarray(bucket, dtype=np.int64)
+    np.add.at(ce, b, ce_terms)                 # unbuffered: one addition per row, in row order
+    np.add.at(se, b[zf != 0.0], se_terms[zf != 0.0])
+    return ce, se
+
+
+def tables(counters, ce_sum, se_sum, width):
+    """(per-bucket rows, total row) as dicts from the int64 counters [n_buckets][8] and the float sums."""
+    counters = np.asarray(counters, dtype=np.int64)
+
+    def row(c, ce, se):
+        d = {name: int(c[i]) for i, name in enumerate(COUNTERS)}
+        d["ce_sum"], d["se_sum"] = float(ce), float(se)
+        d["cross_entropy"] = float(ce) / d["rows"] if d["rows"] else None
+        d["value_mse"] = float(se) / d["value_rows"] if d["value_rows"] else None
+        return d
+    buckets = []
+    for b in range(len(counters)):
+        d = row(counters[b], ce_sum[b], se_sum[b])
+        d["bucket"], d["first_move"] = b, b * width
+        buckets.append(d)
+    tce = tse = 0.0
+    for b in range(len(counters)):             # bucket after bucket: the order is part of the figure
+        tce += float(ce_sum[b])
+        tse += float(se_sum[b])
+    return buckets, row(counters.sum(axis=0), tce, tse)
+
+
+class DeviceRecords(object):
+    """The sgo_records object of the library: replay, the record arrays as tensors, boards, the score launch."""
+
+    def __init__(self, size, max_games, max_entries, device=0):
+        import torch
+        from . import _lib
+        self.torch, self._lib = torch, _lib
+        self.lib = _lib.require_gpu()
+        self.S, self.N, self.A = size, size * size, size * size + 1
+        self.max_games, self.max_entries = int(max_games), int(max_entries)
+        self.device = torch.device("cuda", device)
+        torch.cuda.set_device(self.device)
+        self.RW, self.NW = self.lib.sgo_packed_words(size), self.lib.sgo_plane_words(size)
+        self.h = C.c_void_p(self.lib.sgo_records_create(size, self.max_games, self.max_entries, device))
+        if not self.h:
+            raise _lib.SgoError("sgo_records_create failed: %s" % self.lib.sgo_last_error().decode())
+        rec, leg = C.c_void_p(), C.c_void_p()
+        self.cap = _lib.check(self.lib.sgo_records_list(self.h, C.byref(rec), C.byref(leg)), "sgo_records_list")
+        self.rec_ptr, self.legal_ptr = rec.value, leg.value
+        self.records = self._view(rec.value, (self.cap, self.RW))
+        self.legal = self._view(leg.value, (self.cap, self.NW))
+
+    def _view(self, address, shape):
+        class _Mem(object):
+            pass
+        m = _Mem()
+        m.__cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (address, False), "version": 2}
+        return self.torch.as_tensor(m, device=self.device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.records = self.legal = None
+            self.lib.sgo_records_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def replay(self, n_entries, off, actions, colors):
+        n_entries, off = np.ascontiguousarray(n_entries, np.int32), np.ascontiguousarray(off, np.int32)
+        actions, colors = np.ascontiguousarray(actions, np.int32), np.ascontiguousarray(colors, np.int32)
+        status, fail_at = np.zeros(len(n_entries), np.int32), np.full(len(n_entries), -1, np.int32)
+        self._lib.check(self.lib.sgo_records_replay(self.h, len(n_entries), self._lib.ptr(n_entries), self._lib.ptr(off),
+                                                    self._lib.ptr(actions), self._lib.ptr(colors), self._lib.ptr(status),
+                                                    self._lib.ptr(fail_at), self._lib.stream_ptr()), "sgo_records_replay")
+        return status, fail_at
+
+    def boards(self, index, chunk=2048):
+        """Board tensors int32 [n, S, S, 17] (host) of the listed records, through sgo_unpack_dev."""
+        torch = self.torch
+        index = np.asarray(index, dtype=np.int64)
+        out = np.zeros((len(index), self.S, self.S, 17), np.int32)
+        for lo in range(0, len(index), chunk):
+            idx = torch.from_numpy(index[lo:lo + chunk]).to(self.device)
+            packed = self.records.index_select(0, idx).contiguous()
+            b17 = torch.empty((len(idx), self.S, self.S, 17), dtype=torch.int32, device=self.device)
+            self._lib.check(self.lib.sgo_unpack_dev(C.c_int(self.S), C.c_int(len(idx)), self._lib.ptr(packed), self._lib.ptr(b17),
+                                                    self._lib.stream_ptr()), "sgo_unpack_dev")
+            out[lo:lo + chunk] = b17.cpu().numpy()
+        return out
+
+    def forward(self, net, index_dev, n, k, scratch):
+        """(policy float32 [n, A], value float32 [n]) of the net on the records index_dev lists, evaluated under symmetry k."""
+        torch = self.torch
+        if getattr(net, "packed_ok", False):
+            p, v = net.predict_packed(self.rec_ptr, index_dev.data_ptr(), n, k)
+        else:                                   # a net that reads board tensors: the route of rollout.RolloutEngine._forward
+            layout = 2 if getattr(net, "in_channels", 17) == 32 else 0
+            if scratch.get("nn_in") is None or scratch["nn_in"].shape[0] < n:
+                scratch["nn_in"] = torch.zeros((n, self.S, self.S, 32 if layout == 2 else 17), dtype=torch.float16, device=self.device)
+            x = scratch["nn_in"]
+            self._lib.check(self.lib.sgo_nn_pack_dev(C.c_int(self.S), C.c_int(n), C.c_void_p(self.rec_ptr), self._lib.ptr(index_dev),
+                                                     C.c_int(k), C.c_int(layout), C.c_int(0), self._lib.ptr(x), self._lib.stream_ptr()),
+                            "sgo_nn_pack_dev")
+            p, v = net.predict_on_batch(x[:n])
+        return p.to(torch.float32).contiguous(), v.to(torch.float32).reshape(n).contiguous()
+
+    def score(self, n, index, target, z, bucket, n_buckets, policy, value, k, rank, best, p_target, flags, counters):
+        P = self._lib.ptr
+        self._lib.check(self.lib.sgo_records_score_dev(self.h, int(n), P(index), P(target), P(z), P(bucket), int(n_buckets), P(policy),
+                                                       P(value), int(k), P(rank), P(best), P(p_target), P(flags), P(counters),
+                                                       self._lib.stream_ptr()), "sgo_records_score_dev")
+
+
+class Chunk(object):
+    """What one replay call left on the device, one row per ENTRY of its games (set-up stones included): index (the record
+    holding the position before the entry), game (index into RecordSet.records), node, action, colour, z, setup, valid (the entry
+    was played: its game was not refused at or before it), sample (a move that gives a sample), plus status / fail_at per game."""
+    FIELDS = ("index", "game", "node", "action", "colour", "z", "setup", "valid", "sample")
+
+    def rows(self, mask):
+        return {k: getattr(self, k)[mask] for k in self.FIELDS}
+
+
+class RecordSet(object):
+    """Records of one board size on a replay backend (DeviceRecords, or anything with its replay / boards surface)."""
+
+    def __init__(self, records, size=None, device=0, max_games=None, max_entries=None, compat_unknown_result=False, backend=None):
+        self.records = list(records)
+        self.S = size or conf['SIZE']
+        self.N, self.A = self.S * self.S, self.S * self.S + 1
+        self.compat_unknown_result = bool(compat_unknown_result)
+        for r in self.records:
+            if r.size != self.S or len(r.entries) > max_entries_of(self.S):
+                raise ValueError("record %s does not fit a %dx%d replay" % (r.name, self.S, self.S))
+            if any(c not in (1, -1) for _, c in r.entries):
+                raise ValueError("record %s: every entry needs an explicit colour" % r.name)
+        longest = max([len(r.entries) for r in self.records] + [1])
+        total = sum(len(r.entries) for r in self.records)
+        self.max_games = int(max_games or max(1, min(len(self.records), 4096)))
+        self.max_entries = max(longest, int(max_entries or min(max(total, 1), 1 << 18)))
+        self.backend = backend if backend is not None else DeviceRecords(self.S, self.max_games, self.max_entries, device)
+        self.refused = []                      # (record name, status, fail_at) of the games a replay cut short
+
+    def close(self):
+        if self.backend is not None and hasattr(self.backend, "close"):
+            self.backend.close()
+        self.backend = None
+
+    def _partition(self):
+        out, cur, used = [], [], 0
+        for g, r in enumerate(self.records):
+            if cur and (len(cur) >= self.max_games or used + len(r.entries) > self.max_entries):
+                out.append(cur)
+                cur, used = [], 0
+            cur.append(g)
+            used += len(r.entries)
+        if cur:
+            out.append(cur)
+        return out
+
+    def replay(self):
+        """Generator of Chunks: as many games per replay call as the object holds.  The device records of a chunk are valid until
+        the next one is asked for."""
+        self.refused = []
+        for games in self._partition():
+            n_entries = np.array([len(self.records[g].entries) for g in games], np.int32)
+            off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
+            total = int(n_entries.sum())
+            ch = Chunk()
+            ch.games = games
+            ch.action, ch.colour = np.zeros(total, np.int32), np.zeros(total, np.int32)
+            ch.node, ch.game = np.zeros(total, np.int32), np.zeros(total, np.int32)
+            ch.setup, ch.z, has = np.zeros(total, bool), np.zeros(total, np.int32), np.zeros(total, bool)
+            for i, g in enumerate(games):
+                r = self.records[g]
+                lo, hi = int(off[i]), int(off[i]) + len(r.entries)
+                if hi > lo:
+                    ch.action[lo:hi] = [a for a, _ in r.entries]
+                    ch.colour[lo:hi] = [c for _, c in r.entries]
+                    ch.node[lo:hi] = r.nodes
+                    ch.setup[lo:hi] = r.setup
+                    ch.z[lo:hi], has[lo:hi] = value_targets(r.winner, ch.colour[lo:hi], self.compat_unknown_result)
+                ch.game[lo:hi] = g
+            ch.status, ch.fail_at = self.backend.replay(n_entries, off, ch.action, ch.colour)
+            ch.index = (np.arange(total) + np.repeat(np.arange(len(games)), n_entries)).astype(np.int32)    # base_g + j
+            ch.valid = np.ones(total, bool)
+            for i, g in enumerate(games):
+                if ch.status[i] != 0:
+                    ch.valid[int(off[i]) + int(ch.fail_at[i]):int(off[i]) + int(n_entries[i])] = False
+                    self.refused.append((self.records[g].name, int(ch.status[i]), int(ch.fail_at[i])))
+            ch.sample = ch.valid & ~ch.setup & has
+            yield ch
+
+    # ------------------------------------------------------------------ the strength measure
+    def score(self, net, batch=4096, symmetry="identity", bucket=20, seed=0, keep_policy=False):
+        """Runs the net on every recorded move's position (slices of `batch` rows of the sample index list) and scores it.
+        Returns {"buckets": [dict per bucket], "total": dict, "rows": {per-row numpy arrays}, "bucket_width", "net_calls"}.
+        Rows: every played B / W move (set-up stones are no rows); z = 0 where the result is unknown."""
+        import torch
+        be = self.backend
+        assert symmetry in ("identity", "random1") or symmetry in range(8)
+        width = int(bucket)
+        top = max([max([n for n, s in zip(r.nodes, r.setup) if not s] + [0]) for r in self.records] + [0])
+        n_buckets = top // width + 1
+        counters = torch.zeros((n_buckets, 8), dtype=torch.int64, device=be.device)
+        rng = pyrandom.Random(seed)
+        keep = {k: [] for k in ("index", "game", "node", "action", "z", "bucket", "rank", "best", "p_target", "flags", "value", "sym_k")}
+        if keep_policy:
+            keep["policy"] = []
+        scratch, calls = {}, 0
+        for ch in self.replay():
+            m = ch.valid & ~ch.setup
+            n = int(m.sum())
+            if n == 0:
+                continue
+            z = ch.z[m].astype(np.int32)
+            if self.compat_unknown_result:     # the compat label is a sample's, not a result: the rows of an unknown result stay z = 0
+                unknown = np.array([self.records[g].winner is None for g in ch.game[m]], bool)
+                z[unknown] = 0
+            bk = (ch.node[m] // width).astype(np.int32)
+            d_index, d_target = torch.from_numpy(ch.index[m]).to(be.device), torch.from_numpy(ch.action[m]).to(be.device)
+            d_z, d_bucket = torch.from_numpy(z).to(be.device), torch.from_numpy(bk).to(be.device)
+            d_rank, d_best = torch.empty(n, dtype=torch.int32, device=be.device), torch.empty(n, dtype=torch.int32, device=be.device)
+            d_pt, d_flags = torch.empty(n, dtype=torch.float32, device=be.device), torch.empty(n, dtype=torch.int32, device=be.device)
+            d_value = torch.empty(n, dtype=torch.float32, device=be.device)
+            ks = np.zeros(n, np.int32)
+            for lo in range(0, n, int(batch)):
+                hi = min(n, lo + int(batch))
+                k = 0 if symmetry == "identity" else (rng.randrange(8) if symmetry == "random1" else int(symmetry))
+                p, v = be.forward(net, d_index[lo:hi], hi - lo, k, scratch)
+                assert tuple(p.shape) == (hi - lo, self.A)
+                d_value[lo:hi] = v
+                be.score(hi - lo, d_index[lo:hi], d_target[lo:hi], d_z[lo:hi], d_bucket[lo:hi], n_buckets, p, v, k, d_rank[lo:hi],
+                         d_best[lo:hi], d_pt[lo:hi], d_flags[lo:hi], counters)
+                ks[lo:hi] = k
+                calls += 1
+                if keep_policy:
+                    keep["policy"].append(p.cpu().numpy())
+            for name, arr in (("index", ch.index[m]), ("game", ch.game[m]), ("node", ch.node[m]), ("action", ch.action[m]), ("z", z), ("bucket", bk),
+                              ("rank", d_rank.cpu().numpy()), ("best", d_best.cpu().numpy()), ("p_target", d_pt.cpu().numpy()),
+                              ("flags", d_flags.cpu().numpy()), ("value", d_value.cpu().numpy()), ("sym_k", ks)):
+                keep[name].append(arr)
+        empty = {"policy": np.zeros((0, self.A), np.float32), "p_target": np.zeros(0, np.float32), "value": np.zeros(0, np.float32)}
+        rows = {k: (np.concatenate(v) if v else empty.get(k, np.zeros(0, np.int32))) for k, v in keep.items()}
+        ce, se = float_sums(rows["p_target"], rows["value"], rows["z"], rows["bucket"], n_buckets)
+        buckets, total = tables(counters.cpu().numpy(), ce, se, width)
+        return {"buckets": buckets, "total": total, "rows": rows, "bucket_width": width, "net_calls": calls,
+                "net": getattr(net, "name", str(net)), "refused": list(self.refused)}
+
+    # ------------------------------------------------------------------ supervised samples
+    def write_samples(self, root):
+        """root/KGS/<game>/move_%03d/sample.h5 for every move that gives a sample.  Returns {"games", "samples", "existing":
+        [names left alone], "empty": [names without a sample]}."""
+        from .sgfsave import _write_sample_arrays
+        out = {"games": 0, "samples": 0, "existing": [], "empty": []}
+        for ch in self.replay():
+            todo = []
+            for g in ch.games:
+                name = self.records[g].name
+                rows = np.flatnonzero(ch.sample & (ch.game == g))
+                if os.path.isdir(os.path.join(root, "KGS", name)):          # KGSSelfPlayWorker.py:32-33
+                    out["existing"].append(name)
+                elif len(rows) == 0:
+                    out["empty"].append(name)
+                else:
+                    todo.append((name, rows))
+            if not todo:
+                continue
+            allrows = np.concatenate([rows for _, rows in todo])
+            boards = self.backend.boards(ch.index[allrows])
+            at = 0
+            for name, rows in todo:
+                for r in rows:
+                    directory = os.path.join(root, "KGS", name, "move_%03d" % int(ch.node[r]))
+                    os.makedirs(directory, exist_ok=True)
+                    pol = np.zeros(self.A, np.float32)
+                    pol[int(ch.action[r])] = 1.0                             # the pass is the last entry
+                    _write_sample_arrays(directory, boards[at:at + 1].astype(np.float32), pol, np.array(ch.z[r], dtype=np.float32))
+                    at += 1
+                out["games"] += 1
+                out["samples"] += len(rows)
+        return out
+
+
+def format_bucket(d, label):
+    def pct(a, b):
+        return "%5.1f%%" % (100.0 * a / b) if b else "    - "
+    ce = "%7.4f" % d["cross_entropy"] if d["cross_entropy"] is not None else "    -  "
+    mse = "%6.4f" % d["value_mse"] if d["value_mse"] is not None else "   -  "
+    return "%-9s rows %7d  top1 %s  top5 %s  illegal %5d  ce %s  value %s of %7d  mse %s" % (
+        label, d["rows"], pct(d["top1"], d["rows"]), pct(d["top5"], d["rows"]), d["illegal"], ce,
+        pct(d["value_agree"], d["value_rows"]), d["value_rows"], mse)
+
+
+def _net(kind, size):
+    if kind == "best":
+        from .predicting_queue_worker import get_model, init_predicting_workers
+        init_predicting_workers(conf['GPUs'][:1])
+        return get_model("BEST")
+    from .stub_nets import make_stub
+    return make_stub(kind, size)
+
+
+def main(argv=None, out=sys.stdout):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("path", nargs="?", default=None, help="an .sgf file or a directory of them (default: conf['KGS_DATA_DIR'])")
+    ap.add_argument("--size", type=int, default=None, help="board size (default: conf['SIZE']); other records are skipped")
+    ap.add_argument("--samples", default=None, help="write OUT/KGS/<game>/move_%%03d/sample.h5")
+    ap.add_argument("--score", action="store_true", help="score the net on the recorded moves")
+    ap.add_argument("--net", default="best", choices=["best", "hash", "uniform", "table"],
+                    help="best: the model the configuration names; hash / uniform / table: the stub nets (no weights needed)")
+    ap.add_argument("--symmetry", default="identity", help="identity, random1 (one of the eight per net call) or 0..7")
+    ap.add_argument("--bucket", type=int, default=20, help="moves per bucket of the score table")
+    ap.add_argument("--batch", type=int, default=4096, help="positions per net call")
+    ap.add_argument("--json", default=None, help="write the counts and figures as one JSON document to this file")
+    ap.add_argument("--compat-unknown-result", action="store_true",
+                    help="label the moves of a record without a decided result -1, as the reference does, instead of leaving them out")
+    a = ap.parse_args(argv)
+    size = a.size or conf['SIZE']
+    symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
+    records, skipped = read_path(a.path or conf['KGS_DATA_DIR'], size)
+    out.write("records %d  skipped: unreadable %d, wrong size %d, too long %d\n" % (
+        len(records), len(skipped["unreadable"]), len(skipped["wrong_size"]), len(skipped["too_long"])))
+    doc = {"size": size, "records": len(records), "skipped": skipped}
+    if not records:
+        return 0
+    rs = RecordSet(records, size, compat_unknown_result=a.compat_unknown_result)
+    try:
+        if a.samples:
+            w = rs.write_samples(a.samples)
+            out.write("samples %d of %d games  (%d game directories existed, %d games without a sample)\n" % (
+                w["samples"], w["games"], len(w["existing"]), len(w["empty"])))
+            doc["samples"] = w
+        if a.score:
+            net = _net(a.net, size)
+            try:
+                res = rs.score(net, batch=a.batch, symmetry=symmetry, bucket=a.bucket)
+            finally:
+                if a.net == "best":
+                    from .predicting_queue_worker import destroy_predicting_workers
+                    destroy_predicting_workers(conf['GPUs'][:1])
+            for d in res["buckets"]:
+                out.write(format_bucket(d, "%d-%d" % (d["first_move"], d["first_move"] + a.bucket - 1)) + "\n")
+            out.write(format_bucket(res["total"], "total") + "\n")
+            doc["score"] = {"net": res["net"], "bucket_width": a.bucket, "buckets": res["buckets"], "total": res["total"]}
+        doc["refused"] = [list(t) for t in rs.refused]
+        for name, status, at in rs.refused:
+            out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))
+    finally:
+        rs.close()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(doc, f, indent=1, sort_keys=True)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

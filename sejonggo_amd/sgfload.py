@@ -15,7 +15,11 @@ board, which is how engines that keep (x, y = size) for the pass have written it
     game.setup              # [bool] per entry: True for an AB / AW stone, False for a B / W move
     game.prefix(k)          # the entries up to and including the k-th B / W move (set-up stones count as no move)
 
-The (action, colour) list is what engine.SessionEngine.setup takes: set-up stones are played as stones of an explicit colour."""
+The (action, colour) list is what engine.SessionEngine.setup takes: set-up stones are played as stones of an explicit colour.
+
+For collections of records (records.py): root_properties(text) gives the root node's properties ({ident: [values]}: RE, PB, ...),
+node_indices(text) the index on the main line (root = 0) of the node every entry of loads(text).moves comes from, and
+result_winner(values) reads RE."""
 import collections
 
 
@@ -174,6 +178,38 @@ def loads(text):
                 moves.append((size * size if is_pass else _point(v, size), colour))
                 setup.append(False)
     return SgfGame(size, komi, moves, setup)
+
+
+def root_properties(text):
+    """{ident: [values]} of the root node of the record's main line."""
+    return dict(_main_line(text)[0])
+
+
+def node_indices(text):
+    """One int per entry of loads(text).moves, in its order: the index of the entry's node on the main line, root = 0.  For a
+    B / W move this is the position of its node in the main sequence, whether or not the root carries a move itself."""
+    out = []
+    for i, node in enumerate(_main_line(text)):
+        for ident in ("AB", "AW"):
+            for v in node.get(ident, []):
+                if ":" in v:
+                    a, b = v.split(":", 1)
+                    out.extend([i] * ((ord(b[0]) - ord(a[0]) + 1) * (ord(b[1]) - ord(a[1]) + 1)))
+                else:
+                    out.append(i)
+        out.extend([i] * (len(node.get("B", [])) + len(node.get("W", []))))
+    return out
+
+
+def result_winner(root):
+    """+1 / -1 from the RE of root_properties: "B+..." / "W+..." (any case, leading blanks skipped); None for everything else
+    ("0", "Draw", "Void", "?", no RE at all)."""
+    re = (root.get("RE") or [""])[0].strip().upper()
+    if re.startswith("B+"):
+        return 1
+    if re.startswith("W+"):
+        return -1
+    return None
 
 
 def load_file(path):
