@@ -49,7 +49,8 @@ extern "C" {
  *   1: round 1.   2: sgo_start_games(+stream), sgo_game_result.first_model (40 bytes), sgo_config.two_model,
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
- *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*). */
+ *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
+ *   (sgo_keys*, sgo_session_keys). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -527,6 +528,46 @@ int sgo_records_list(sgo_records *, const uint32_t **d_records, const uint32_t *
 int sgo_records_score_dev(sgo_records *, int n, const int32_t *d_index, const int32_t *d_target, const int32_t *d_z,
                           const int32_t *d_bucket, int n_buckets, const float *d_policy, const float *d_value, int sym_k,
                           int32_t *d_rank, int32_t *d_best, float *d_p_target, int32_t *d_flags, int64_t *d_counters, void *stream);
+
+/* ---- position keys: which position does a record hold?  A 64-bit key that rotations and reflections do not change ------------- */
+/* What an opening book, duplicate detection and every later "have I seen this position" stand on (csrc/sgo_keys.hip).  All
+ * arithmetic is unsigned 64-bit and wraps.
+ *   sm(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  x ^= x >> 31                                      (uint64)
+ *   z(S, c, a) = sm((uint64(S) << 24) | (uint64(c) << 16) | a)      c: 0 black, 1 white, 2 = "white to play" (a = 0)
+ * Inputs of a record, N = S * S: black = the bits a < N of plane 0, white = the bits a < N of plane 1 (ABSOLUTE colours, the
+ * current position only), w = the to-play flag, the top bit of the last word of plane 0.  The flag is NOT a stone (at S = 5 it
+ * shares the plane's only word with the stones); bits a >= N other than the flag and planes 2..15 are never read as stones.
+ * L_k is the table sgo_sym_lut(S, k) writes, k = 0..7: together the whole symmetry group of the square.  For k = 4 and k = 6 the
+ * table is the INVERSE of where sgo_sym_apply moves a stone, which is why the definition goes through the tables:
+ *   key_k  = XOR over a in black of z(S, 0, L_k[a])  ^  XOR over a in white of z(S, 1, L_k[a])  ^  (w ? z(S, 2, 0) : 0)
+ *   key0   = key_0
+ *   canon  = the unsigned minimum of key_0 .. key_7
+ *   mask   = bit k set  <=>  key_k == canon            (the empty board: 255; never 0 for a valid row)
+ *   canon_action(t) = min over k in mask of L_k[t]     for t in [0, N]  (L_k[N] = N: a pass stays a pass);  -1 for any other t
+ * INVARIANCE: for every g among the eight tables, the record of the position moved by g with the target moved by g has the same
+ * (canon, canon_action).
+ * LEFT OUT: ko status and history are no part of the key, so two positions that differ only in what the ko approximation
+ * (play.py:78-80) forbids share a key; so do positions reached by different move orders.  Colours are not swapped.
+ *
+ * sgo_keys_dev: row i keys record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], read in place;
+ * d_target[i] is the action to map (d_target NULL: no targets; d_canon_action is then not written and may be NULL, and only
+ * then).  Outputs [n] each.  A row whose record index is outside [0, n_records) gives key0 = canon = 0, mask = 0, canon_action
+ * = -1.  ONE launch on `stream` (one half-wavefront per row), no allocation, no synchronisation, capturable; n == 0 is a no-op;
+ * rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, a NULL d_records or output. */
+int sgo_keys_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
+                 uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_canon_action, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests. */
+int sgo_keys(int S, int n, const uint32_t *records, const int32_t *target, uint64_t *key0, uint64_t *canon, int32_t *mask,
+             int32_t *canon_action);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), keyed in place: one launch and one
+ * copy back; waits for `stream`.  HOST arrays of n entries.  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding
+ * session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be listed repeatedly. */
+int sgo_session_keys(sgo_ctx *ctx, int n, const int32_t *slots, int32_t *status, uint64_t *key0, uint64_t *canon, int32_t *mask,
+                     void *stream);
+/* Where sgo_keys_dev / sgo_keys take z from: 0 = a table z[2][N] in LDS, written once per workgroup (default), 1 = computed where
+ * it is used (for A/B timing).  Same bits.  Returns the previous mode; other values only query. */
+int sgo_keys_mode(int mode);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

@@ -35,6 +35,7 @@ SYMBOLS = [
     "sgo_rollout_create", "sgo_rollout_destroy", "sgo_rollout_start", "sgo_rollout_start_dev", "sgo_rollout_start_sessions",
     "sgo_rollout_list", "sgo_rollout_step", "sgo_rollout_result",
     "sgo_records_create", "sgo_records_destroy", "sgo_records_replay", "sgo_records_list", "sgo_records_score_dev",
+    "sgo_keys_dev", "sgo_keys", "sgo_session_keys", "sgo_keys_mode",
 ]
 
 
@@ -176,6 +177,10 @@ def load():
     lib.sgo_records_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sgo_records_score_dev.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + \
         [C.c_void_p] * 6
+    lib.sgo_keys_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.sgo_keys.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
+    lib.sgo_session_keys.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    lib.sgo_keys_mode.argtypes = [C.c_int]
     _lib = lib
     return lib
 

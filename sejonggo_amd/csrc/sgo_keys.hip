@@ -1,0 +1,265 @@
+// sgo_keys.hip -- position keys on the device (include/sgo.h "position keys"): per packed record a 64-bit Zobrist-style key, its
+// minimum over the eight symmetries of the square (the canonical key), the mask of the symmetries that reach the minimum, and a
+// recorded action mapped into the canonical frame.  What an opening book and duplicate detection stand on.  A translation unit
+// of its own: tests/test_engine_isa.py pins the kernel set of sgo_engine.hip, and nothing here touches k_search.
+//
+//   k_keys<S, INLINE>     per listed record: key0, canon, mask, canon_action
+//   k_session_keys<S>     the same for the root records of holding session slots (sgo_session_keys)
+//
+// Kernel form: one 32-lane HALF of a wavefront per record, one board row per lane (sgo_rows.hpp load_row), as k_records_score.
+// A record gives 2 of its 16 planes; they are read in place through the index list, no record is copied.  Each lane walks the
+// set bits of its black and its white row and XORs z(S, c, L_k[a]) into eight 64-bit accumulators; L_k of a point is plain
+// arithmetic on (x, y) -- per lane a base and a step per symmetry -- so no symmetry table is read.  Five butterfly steps XOR
+// the 32 lanes together; lane 0 adds the to-play word, takes the minimum and writes the outputs with plain stores.
+//
+// z comes from a table z[2][N] in LDS (5.8 KB at 19x19), written once per 256-thread workgroup, which then strides over the
+// records (INLINE = false, the product), or is computed where it is needed (INLINE = true: eight splitmix rounds per stone;
+// sgo_keys_mode selects it for A/B timing, and the few rows of k_session_keys use it: no table to fill).  Same bits either way.
+//
+// Nothing branches around a shuffle on a per-record condition: a half whose row is out of range or does not exist reads no
+// stones and only its final stores differ.
+#include <string.h>
+
+#include "sgo_engine_state.hpp"
+#include "sgo_rows.hpp"
+
+namespace sgo {
+
+static inline int cdiv_k(long a, long b) { return (int)((a + b - 1) / b); }
+
+__host__ __device__ __forceinline__ uint64_t sm64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// c: 0 black, 1 white, 2 = "white to play" (a = 0)
+__host__ __device__ __forceinline__ uint64_t zkey(int S, int c, int a) {
+    return sm64(((uint64_t)S << 24) | ((uint64_t)c << 16) | (uint64_t)a);
+}
+
+// L_k[y * S + x], the table sgo_sym_lut(S, k) writes (build_sym_lut's rotations and reflections, in integers)
+template <int S>
+SGO_DEV int sym_point(int k, int x, int y) {
+    constexpr int m = S - 1;
+    switch (k) {
+    case 0: return y * S + x;
+    case 1: return x * S + y;                  // left diagonal
+    case 2: return y * S + (m - x);            // vertical axis
+    case 3: return (m - y) * S + x;            // horizontal axis
+    case 4: return x * S + (m - y);            // rotation 90
+    case 5: return (m - y) * S + (m - x);      // rotation 180
+    case 6: return (m - x) * S + y;            // rotation 270
+    default: return (m - x) * S + (m - y);     // right diagonal
+    }
+}
+
+// The eight keys of one record WITHOUT the to-play word, XOR-reduced over the half: every lane of the half returns them all.
+// rec == nullptr (uniform over the half): no stones.
+template <int S, bool INLINE>
+SGO_DEV void stone_keys(const uint32_t *rec, const uint64_t *zt, int y, uint64_t (&key)[8]) {
+    using G = Geo<S>;
+    constexpr int m = S - 1;
+    uint32_t row[2] = {0u, 0u};
+    if (rec) { row[0] = rows::load_row<S>(rec, y); row[1] = rows::load_row<S>(rec + G::NW, y); }
+    // L_k[y * S + x] = base[k] + x * step[k]
+    const int base[8] = {y * S, y, y * S + m, (m - y) * S, m - y, (m - y) * S + m, m * S + y, m * S + (m - y)};
+    constexpr int step[8] = {1, S, -1, 1, S, -1, -S, -S};
+#pragma unroll
+    for (int k = 0; k < 8; k++) key[k] = 0ull;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        uint32_t bits = row[c];
+        while (bits) {
+            const int x = __builtin_ctz(bits);
+            bits &= bits - 1u;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int a = base[k] + x * step[k];
+                key[k] ^= INLINE ? zkey(S, c, a) : zt[c * G::N + a];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) key[k] ^= (uint64_t)__shfl_xor((unsigned long long)key[k], o, 32);
+    }
+}
+
+// canon, mask and canon_action(t) from the eight keys (to-play word included)
+template <int S>
+SGO_DEV void canonical(const uint64_t (&key)[8], int t, uint64_t &canon, int &mask, int &action) {
+    using G = Geo<S>;
+    canon = key[0];
+#pragma unroll
+    for (int k = 1; k < 8; k++) canon = key[k] < canon ? key[k] : canon;
+    mask = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) mask |= (key[k] == canon) ? (1 << k) : 0;
+    action = -1;
+    if (t == G::N) action = G::N;                          // a pass stays a pass
+    else if (t >= 0 && t < G::N) {
+        const int x = t % S, y = t / S;
+        action = G::N;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int a = sym_point<S>(k, x, y);
+            if (((mask >> k) & 1) && a < action) action = a;
+        }
+    }
+}
+
+template <int S, bool INLINE>
+__global__ __launch_bounds__(256) void k_keys(int n, const uint32_t *records, int n_records, const int32_t *index, const int32_t *target,
+                                              uint64_t *key0, uint64_t *canon_out, int32_t *mask_out, int32_t *action_out) {
+    using G = Geo<S>;
+    __shared__ uint64_t zt[INLINE ? 1 : 2 * G::N];
+    if (!INLINE) {
+        for (int i = threadIdx.x; i < 2 * G::N; i += 256) zt[i] = zkey(S, i >= G::N ? 1 : 0, i >= G::N ? i - G::N : i);
+        __syncthreads();
+    }
+    const int hw = threadIdx.x >> 5, y = threadIdx.x & 31;
+    // the trip count is the workgroup's: every half of a wave runs every shuffle
+    for (long i0 = (long)blockIdx.x * 8; i0 < n; i0 += (long)gridDim.x * 8) {
+        const long i = i0 + hw;
+        const bool valid = i < n;
+        const int r = valid ? (index ? index[i] : (int)i) : -1;
+        const bool ok = r >= 0 && r < n_records;                         // uniform over the half
+        const uint32_t *rec = ok ? records + (size_t)r * G::RW : nullptr;
+        uint64_t key[8];
+        stone_keys<S, INLINE>(rec, zt, y, key);
+        if (valid && y == 0) {
+            uint64_t canon = 0ull;
+            int mask = 0, action = -1;
+            if (ok) {
+                if (rec[G::META_WORD] & G::META_BIT) {
+                    const uint64_t zw = zkey(S, 2, 0);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) key[k] ^= zw;
+                }
+                canonical<S>(key, target ? target[i] : -1, canon, mask, action);
+            }
+            key0[i] = ok ? key[0] : 0ull;
+            canon_out[i] = canon;
+            mask_out[i] = mask;
+            if (target) action_out[i] = action;
+        }
+    }
+}
+
+// One half of a wavefront per listed slot: the root record of a holding session (what sgo_game_board shows) is keyed in place;
+// anything else gets SGO_ERR_STATE and no other output.  The context is only read.
+template <int S>
+__global__ __launch_bounds__(64) void k_session_keys(Ctx c, int n, const int32_t *slots, int32_t *status, uint64_t *key0,
+                                                     uint64_t *canon_out, int32_t *mask_out) {
+    using G = Geo<S>;
+    const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
+    const int i = blockIdx.x * 2 + half;
+    const bool valid = i < n;
+    const uint32_t *rec = nullptr;
+    if (valid) {
+        const int g = slots[i];
+        const GameState &s = c.gs[g];
+        if (s.session && s.phase == PH_HOLD && !s.error) {
+            const int blk = s.root_blk;
+            const size_t ph = blk < c.cap ? (size_t)g * c.cap + blk
+                                          : (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
+            rec = c.pos + ph * G::RW;
+        }
+    }
+    uint64_t key[8];
+    stone_keys<S, true>(rec, nullptr, y, key);
+    if (valid && y == 0) {
+        status[i] = rec ? SGO_OK : SGO_ERR_STATE;
+        if (rec) {
+            if (rec[G::META_WORD] & G::META_BIT) {
+                const uint64_t zw = zkey(S, 2, 0);
+#pragma unroll
+                for (int k = 0; k < 8; k++) key[k] ^= zw;
+            }
+            uint64_t canon;
+            int mask, action;
+            canonical<S>(key, -1, canon, mask, action);
+            key0[i] = key[0];
+            canon_out[i] = canon;
+            mask_out[i] = mask;
+        }
+    }
+}
+
+static int g_keys_mode = 0;       // 0: the LDS table, 1: splitmix inline
+
+static int launch_keys(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
+                       uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_action, hipStream_t st) {
+    const int blocks = cdiv_k(n, 8) < 4096 ? cdiv_k(n, 8) : 4096;
+    if (g_keys_mode == 1) {
+        SGO_DISPATCH(S, k_keys<kS, true><<<dim3(blocks), dim3(256), 0, st>>>(n, d_records, n_records, d_index, d_target, d_key0, d_canon,
+                                                                              d_mask, d_action));
+    } else {
+        SGO_DISPATCH(S, k_keys<kS, false><<<dim3(blocks), dim3(256), 0, st>>>(n, d_records, n_records, d_index, d_target, d_key0, d_canon,
+                                                                               d_mask, d_action));
+    }
+    SGO_HIP(hipGetLastError());
+    return SGO_OK;
+}
+
+// sgo_session_keys' launch (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
+int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, uint64_t *d_key0, uint64_t *d_canon,
+                        int32_t *d_mask, hipStream_t st) {
+    SGO_DISPATCH(c.S, k_session_keys<kS><<<dim3(cdiv_k(n, 2)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_key0, d_canon, d_mask));
+    SGO_HIP(hipGetLastError());
+    return SGO_OK;
+}
+
+}  // namespace sgo
+
+using namespace sgo;
+
+extern "C" {
+
+int sgo_keys_mode(int mode) {
+    const int prev = g_keys_mode;
+    if (mode == 0 || mode == 1) g_keys_mode = mode;
+    return prev;
+}
+
+int sgo_keys_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
+                 uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_canon_action, void *stream) {
+    if (!size_ok(S) || n < 0 || n_records < 0 || !d_records || !d_key0 || !d_canon || !d_mask || (d_target && !d_canon_action)) {
+        set_error("sgo_keys_dev: bad argument (unsupported size, n < 0, a NULL record array or output, targets without d_canon_action)");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    return launch_keys(S, n, d_records, n_records, d_index, d_target, d_key0, d_canon, d_mask, d_canon_action, (hipStream_t)stream);
+}
+
+int sgo_keys(int S, int n, const uint32_t *records, const int32_t *target, uint64_t *key0, uint64_t *canon, int32_t *mask,
+             int32_t *canon_action) {
+    if (!size_ok(S) || n < 0 || !records || !key0 || !canon || !mask || (target && !canon_action)) {
+        set_error("sgo_keys: bad argument (unsupported size, n < 0, a NULL record array or output, targets without canon_action)");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    // one block: records | key0 | canon | mask | target | action
+    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), kb = (size_t)n * sizeof(uint64_t), ib = (size_t)n * sizeof(int32_t);
+    uint8_t *d = nullptr;
+    SGO_HIP(hipMalloc((void **)&d, rb + 2 * kb + 3 * ib));
+    uint64_t *d_key0 = reinterpret_cast<uint64_t *>(d + rb), *d_canon = d_key0 + n;
+    int32_t *d_mask = reinterpret_cast<int32_t *>(d + rb + 2 * kb), *d_target = d_mask + n, *d_action = d_target + n;
+    int rc = SGO_OK;
+    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && target) e = hipMemcpy(d_target, target, ib, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        rc = launch_keys(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, target ? d_target : nullptr, d_key0, d_canon, d_mask,
+                         d_action, nullptr);
+    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(key0, d_key0, kb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(canon, d_canon, kb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(mask, d_mask, ib, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == SGO_OK && target) e = hipMemcpy(canon_action, d_action, ib, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(e, "sgo_keys", __FILE__, __LINE__);
+    return rc;
+}
+
+}  // extern "C"

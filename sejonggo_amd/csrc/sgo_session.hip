@@ -1,7 +1,8 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
-// "interactive games" section of include/sgo.h.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip;
-// the kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
-// SejongGoEngine a GTP front-end drives.
+// "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
+// sgo_keys.hip).  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the kernels are in
+// sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the SejongGoEngine a GTP
+// front-end drives.
 #include <string.h>
 #include <vector>
 
@@ -9,6 +10,12 @@
 #include "sgo_session.hpp"
 
 using namespace sgo;
+
+namespace sgo {
+// csrc/sgo_keys.hip: k_session_keys on device pointers
+int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, uint64_t *d_key0, uint64_t *d_canon,
+                        int32_t *d_mask, hipStream_t st);
+}
 
 // Stage n slots (+ optional actions / colours) in the context's staging area, as sgo_start_games does: wait until the previous
 // batch has left the pinned block, fill it, one host-to-device copy on the caller's stream.
@@ -202,6 +209,41 @@ int sgo_session_report(sgo_ctx *x, int n, const int32_t *slots, int K, int D, in
         if (P) memcpy(P + A * i, o + 8 + 2 * A, sizeof(float) * A);
         if (top_action && K) memcpy(top_action + (size_t)K * i, o + 8 + 3 * A, sizeof(int32_t) * K);
         if (pv && K && D) memcpy(pv + (size_t)K * D * i, o + 8 + 3 * A + K, sizeof(int32_t) * K * D);
+    }
+    return SGO_OK;
+}
+
+int sgo_session_keys(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, uint64_t *key0, uint64_t *canon, int32_t *mask,
+                     void *stream) {
+    if (!x || n < 0 || (n && (!slots || !status || !key0 || !canon || !mask))) { set_error("sgo_session_keys: bad argument"); return SGO_ERR_ARG; }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    if (n > c.G) { set_error("sgo_session_keys: more slots than the context has"); return SGO_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_keys: slot out of range"); return SGO_ERR_ARG; }
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    // slots | status | mask | key0 | canon; everything behind the slots comes back in one copy
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), kb = sizeof(uint64_t) * (size_t)n;
+    const int rc = session_buffer(x, 3 * ib + 2 * kb);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    memcpy(h, slots, sizeof(int32_t) * n);
+    SGO_HIP(hipMemcpyAsync(d, h, ib, hipMemcpyHostToDevice, st));
+    const int lrc = launch_session_keys(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + ib),
+                                        reinterpret_cast<uint64_t *>(d + 3 * ib), reinterpret_cast<uint64_t *>(d + 3 * ib + kb),
+                                        reinterpret_cast<int32_t *>(d + 2 * ib), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + ib, d + ib, 2 * ib + 2 * kb, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + ib), *hm = reinterpret_cast<const int32_t *>(h + 2 * ib);
+    const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + 3 * ib), *hc = hk + n;
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        key0[i] = hk[i];
+        canon[i] = hc[i];
+        mask[i] = hm[i];
     }
     return SGO_OK;
 }

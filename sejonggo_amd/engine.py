@@ -732,6 +732,19 @@ class SessionEngine(SelfPlayEngine):
                                                 "P", "top_action", "pv")] + [self._stream_ptr()])), "sgo_session_report")
         return out
 
+    def keys(self, slots):
+        """The position keys of the root positions of the listed holding sessions (sgo_session_keys; include/sgo.h "position
+        keys"), one launch: {"status" int32 [n] (SGO_ERR_STATE: not a holding session; that row stays 0), "key0", "canon" uint64
+        [n], "mask" int32 [n]}.  Boards and trees are only read."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(slots)
+        out = {"status": np.zeros(n, np.int32), "key0": np.zeros(n, np.uint64), "canon": np.zeros(n, np.uint64),
+               "mask": np.zeros(n, np.int32)}
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_keys(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(out["status"]), _lib.ptr(out["key0"]),
+                                                 _lib.ptr(out["canon"]), _lib.ptr(out["mask"]), self._stream_ptr()), "sgo_session_keys")
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

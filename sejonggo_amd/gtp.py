@@ -226,6 +226,18 @@ class DeviceSejongGoEngine(object):
         """engine.SessionEngine.report for this game: a dict of arrays with one row."""
         return self.engine.report([self.slot], top=top, depth=depth)
 
+    def keys(self):
+        """(canon, mask) of the position on the board (engine.SessionEngine.keys): what records.Book.moves takes."""
+        k = self.engine.keys([self.slot])
+        if int(k["status"][0]):
+            raise ValueError("the slot is not a holding session")
+        return int(k["canon"][0]), int(k["mask"][0])
+
+    def legal(self):
+        """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
+        from .play import legal_moves
+        return np.asarray(legal_moves(self.board)).reshape(-1) == 0
+
     def rollouts(self, per_src=None, seed=0):
         """How the game ends from here: the position played out per_src times (None: conf['ROLLOUTS']) with the net's policy
         (engine.SessionEngine.rollouts).  Returns this game's row of counts (rollout.result_row) and the stones on the board
@@ -243,8 +255,18 @@ class GTPFailure(Exception):
 
 
 class GTPEngine(object):
-    def __init__(self, engine=None):
+    def __init__(self, engine=None, book=None, book_min=1):
+        """book: a records.Book (or the path of its .npz) genmove answers from while it holds a legal move played at least
+        book_min times; it needs the device engine (position keys come from the session slot)."""
         self._komi = 0
+        self.book, self.book_min = None, int(book_min)
+        if book is not None:
+            if engine is None or not hasattr(engine, "keys"):
+                raise ValueError("an opening book needs the device engine (gtp --device)")
+            from .records import Book
+            self.book = book if isinstance(book, Book) else Book.load(book)
+            if self.book.size != conf['SIZE']:
+                raise ValueError("the book is {0}x{0}, the configuration {1}x{1}".format(self.book.size, conf['SIZE']))
         self.size = conf['SIZE']
         self.board, self.player = game_init(self.size)
         self.sejong_engine = engine or SejongGoEngine(conf['MCTS_SIMULATIONS'], self.board)
@@ -261,7 +283,7 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "quit"])
+                          "sgo-ownership", "sgo-book", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -299,9 +321,31 @@ class GTPEngine(object):
         self.board, self.player = self.sejong_engine.play(COLOR_TO_PLAYER[color], x, y)
         return ""
 
+    def _book_moves(self):
+        """[(action, count, wins, losses)] of the book for the position on the board, most played first; [] without a book"""
+        if self.book is None:
+            return []
+        return self.book.moves(*self.sejong_engine.keys())
+
     def genmove(self, color):
-        x, y, _, _, self.board, self.player = self.sejong_engine.genmove(COLOR_TO_PLAYER[color])
+        player = COLOR_TO_PLAYER[color]
+        if self.book is not None and player == int(np.asarray(self.sejong_engine.board)[0, 0, 0, -1]):
+            rows = [r for r in self._book_moves() if r[1] >= self.book_min]
+            legal = self.sejong_engine.legal() if rows else None
+            for a, _, _, _ in rows:
+                if legal[a]:
+                    # an external move as far as the session is concerned: its tree follows as for any play
+                    x, y = (a % self.size, a // self.size) if a < self.size * self.size else (0, self.size)
+                    self.board, self.player = self.sejong_engine.play(player, x, y)
+                    return self.print_move(x, y)
+        x, y, _, _, self.board, self.player = self.sejong_engine.genmove(player)
         return self.print_move(x, y)
+
+    def sgo_book(self):
+        """Private extension `sgo-book`: the book's moves for the position on the board, one line `vertex count wins losses`
+        each, most played first; empty when there are none (or no book)."""
+        self._engine_method("keys")
+        return "\n".join("%s %d %d %d" % (self._vertex(a), c, w, l) for a, c, w, l in self._book_moves())
 
     def clear_board(self):
         self.board, self.player = game_init(self.size)
@@ -397,7 +441,7 @@ class GTPEngine(object):
     def quit(self):
         return ""
 
-    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership"}      # GTP private extensions carry a hyphen; methods cannot
+    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")
@@ -414,9 +458,14 @@ class GTPEngine(object):
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 
-def main(inp=sys.stdin, out=sys.stdout, device=False):
-    """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine)."""
-    engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None)
+def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1):
+    """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine).
+    book (`--book FILE [--book-min N]`, device only): genmove plays from the opening book records.py wrote while it has a move."""
+    if book is not None and not device:
+        sys.stderr.write("--book needs the device engine: run with --device\n")
+        return 2
+    engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None, book=book,
+                       book_min=book_min)
     for line in inp:
         for cmd in line.split("\n"):
             res = engine.parse_command(cmd)
@@ -428,5 +477,15 @@ def main(inp=sys.stdin, out=sys.stdout, device=False):
                 return
 
 
+def _cli(argv):
+    import argparse
+    ap = argparse.ArgumentParser(description="GTP on stdin / stdout")
+    ap.add_argument("--device", action="store_true", help="the game lives on the device engine")
+    ap.add_argument("--book", default=None, help="an opening book (.npz of `python -m sejonggo_amd.records --book`); needs --device")
+    ap.add_argument("--book-min", type=int, default=1, help="play a book move only when it was played at least N times (default 1)")
+    a = ap.parse_args(argv)
+    return main(device=a.device, book=a.book, book_min=a.book_min)
+
+
 if __name__ == "__main__":
-    main(device="--device" in sys.argv[1:])
+    sys.exit(_cli(sys.argv[1:]))

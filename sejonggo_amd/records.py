@@ -3,6 +3,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
 
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
+                                        [--book OUT.npz] [--book-plies N] [--duplicates]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -25,6 +26,12 @@ record -1.  Here such records give no samples by default and their rows enter th
 
 ONE DEVIATION in the positions: the reference places only the root's AB stones (as black plays) and ignores AW.  Every AB / AW
 stone sgfload lists is placed here, in the node it stands in.
+
+POSITION KEYS (include/sgo.h "position keys", csrc/sgo_keys.hip).  Every record of a replay has a 64-bit key that rotations and
+reflections of the board do not change.  --book groups the recorded moves of the first --book-plies nodes (default 30) by
+(canonical key, move in the canonical frame) and writes count / wins / losses per group as one .npz (Book); `gtp --device --book`
+plays from it.  --duplicates lists the records whose key sequences are equal ply for ply: the same game, in any orientation.
+Ko status and history are no part of a key.
 
 A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
 skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
@@ -136,6 +143,87 @@ def tables(counters, ce_sum, se_sum, width):
     return buckets, row(counters.sum(axis=0), tce, tse)
 
 
+def sym_luts(size):
+    """int32 [8, A]: the tables sgo_sym_lut(size, k) writes, k = 0..7 (symmetry.py:12-42), in integers."""
+    m = size - 1
+    y, x = np.divmod(np.arange(size * size), size)
+    pts = [(x, y), (y, x), (m - x, y), (x, m - y), (m - y, x), (m - x, m - y), (y, m - x), (m - y, m - x)]     # (new x, new y)
+    out = np.full((8, size * size + 1), size * size, np.int32)
+    for k, (nx, ny) in enumerate(pts):
+        out[k, :size * size] = nx + size * ny
+    return out
+
+
+def sm64(x):
+    """sm of include/sgo.h "position keys" on uint64 arrays (wrapping)."""
+    with np.errstate(over="ignore"):
+        x = np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def _host(a, dtype=None):
+    """numpy array of a backend's output (a torch tensor or an array); int64 key tensors come back as uint64"""
+    a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    return a.view(dtype) if dtype is not None and a.dtype != dtype else a
+
+
+def _tensor(a):
+    """torch tensor of a backend's output; uint64 keys travel as the int64 of the same bits (torch has no unsigned sort)"""
+    import torch
+    if torch.is_tensor(a):
+        return a
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+
+
+class Book(object):
+    """An opening book: per (canonical key, action in the canonical frame) how often the move was played and how it ended for the
+    mover.  Entries are sorted by (key unsigned, action).  One .npz: size, key uint64, action int32, count / wins / losses int64."""
+
+    def __init__(self, size, key, action, count, wins, losses):
+        self.size = int(size)
+        self.key, self.action = np.asarray(key, np.uint64), np.asarray(action, np.int32)
+        self.count, self.wins, self.losses = (np.asarray(v, np.int64) for v in (count, wins, losses))
+        order = np.lexsort((self.action, self.key))
+        for name in ("key", "action", "count", "wins", "losses"):
+            setattr(self, name, getattr(self, name)[order])
+        self._luts = sym_luts(self.size)
+
+    def __len__(self):
+        return len(self.key)
+
+    def __eq__(self, other):
+        return isinstance(other, Book) and self.size == other.size and all(
+            np.array_equal(getattr(self, n), getattr(other, n)) for n in ("key", "action", "count", "wins", "losses"))
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, size=np.int32(self.size), key=self.key, action=self.action, count=self.count, wins=self.wins,
+                     losses=self.losses)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(int(z["size"]), z["key"], z["action"], z["count"], z["wins"], z["losses"])
+
+    def moves(self, canon, mask):
+        """[(a, count, wins, losses)] in the BOARD frame of a position with the given canonical key and symmetry mask
+        (sgo_keys_dev / sgo_session_keys): for the smallest k of the mask, the a with L_k[a] == the entry's canonical action.
+        Ordered by count descending, then a ascending."""
+        mask = int(mask) & 255
+        if not mask:
+            return []
+        k = (mask & -mask).bit_length() - 1
+        canon = np.uint64(int(canon) & ((1 << 64) - 1))
+        lo, hi = np.searchsorted(self.key, canon, "left"), np.searchsorted(self.key, canon, "right")
+        back = np.empty(self.size * self.size + 1, np.int64)
+        back[self._luts[k]] = np.arange(self.size * self.size + 1)
+        rows = [(int(back[self.action[i]]), int(self.count[i]), int(self.wins[i]), int(self.losses[i])) for i in range(lo, hi)]
+        return sorted(rows, key=lambda r: (-r[1], r[0]))
+
+
 class DeviceRecords(object):
     """The sgo_records object of the library: replay, the record arrays as tensors, boards, the score launch."""
 
@@ -222,6 +310,27 @@ class DeviceRecords(object):
                                                        P(value), int(k), P(rank), P(best), P(p_target), P(flags), P(counters),
                                                        self._lib.stream_ptr()), "sgo_records_score_dev")
 
+    def keys(self, index, target=None):
+        """(key0, canon, mask, canon_action) device tensors of the listed records (sgo_keys_dev, one launch): the keys int64
+        holding the uint64 bit patterns, mask / canon_action int32; canon_action is None without targets.  An index outside the
+        object gives the zero row."""
+        torch = self.torch
+        def dev(a):
+            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))).to(self.device, torch.int32)
+        index = dev(index).contiguous()
+        n = int(index.shape[0])
+        target = dev(target).contiguous() if target is not None else None
+        assert target is None or int(target.shape[0]) == n
+        key0, canon = torch.zeros(n, dtype=torch.int64, device=self.device), torch.zeros(n, dtype=torch.int64, device=self.device)
+        mask = torch.zeros(n, dtype=torch.int32, device=self.device)
+        action = torch.full((n,), -1, dtype=torch.int32, device=self.device) if target is not None else None
+        if n:
+            P = self._lib.ptr
+            self._lib.check(self.lib.sgo_keys_dev(C.c_int(self.S), C.c_int(n), C.c_void_p(self.rec_ptr), C.c_int(self.cap), P(index),
+                                                  P(target), P(key0), P(canon), P(mask), P(action), self._lib.stream_ptr()),
+                            "sgo_keys_dev")
+        return key0, canon, mask, action
+
 
 class Chunk(object):
     """What one replay call left on the device, one row per ENTRY of its games (set-up stones included): index (the record
@@ -302,6 +411,89 @@ class RecordSet(object):
                     self.refused.append((self.records[g].name, int(ch.status[i]), int(ch.fail_at[i])))
             ch.sample = ch.valid & ~ch.setup & has
             yield ch
+
+    # ------------------------------------------------------------------ position keys, the opening book, duplicates
+    def _keyed(self):
+        """Generator of (chunk, (key0, canon, mask, canon_action)) as the backend gives them (device tensors on the device), one
+        row per entry: the record before the entry, the entry's action as the target.  Rows that were not played key nothing."""
+        for ch in self.replay():
+            yield ch, self.backend.keys(np.where(ch.valid, ch.index, -1).astype(np.int32), ch.action)
+
+    def keys(self):
+        """Generator of Chunks as `replay` gives them, each with key0 / canon uint64 [rows], mask / canon_action int32 [rows]
+        beside its fields: the position BEFORE each entry and the entry's action in the canonical frame (rows that were not
+        played: 0, 0, 0, -1)."""
+        for ch, (key0, canon, mask, action) in self._keyed():
+            ch.key0, ch.canon = _host(key0, np.uint64), _host(canon, np.uint64)
+            ch.mask, ch.canon_action = _host(mask), _host(action)
+            yield ch
+
+    def book(self, plies=30, min_count=1):
+        """Book of the played B / W moves whose node index (the reference's move_n) is below `plies`, grouped by (canon,
+        canon_action): count, wins (z = +1 for the mover), losses (z = -1); a record without a decided result counts in count
+        only.  Groups with fewer than min_count rows are left out.  Grouped per chunk where the keys are (torch sort / unique),
+        merged on the host: the result does not depend on how the set was chunked."""
+        import torch
+        parts = []
+        for ch, (_, canon, _, action) in self._keyed():
+            m = ch.valid & ~ch.setup & (ch.node < int(plies))
+            if not m.any():
+                continue
+            winner = np.array([self.records[g].winner or 0 for g in ch.game], np.int32)
+            z = np.where(winner == 0, 0, np.where(winner == ch.colour, 1, -1))
+            canon, action = _tensor(canon), _tensor(action)
+            sel = torch.from_numpy(np.flatnonzero(m)).to(canon.device)
+            pair = torch.stack([canon.index_select(0, sel), action.index_select(0, sel).to(torch.int64)], dim=1)
+            uniq, inv = torch.unique(pair, dim=0, return_inverse=True)
+            tally = torch.from_numpy(np.stack([np.ones(int(m.sum()), np.int64), z[m] > 0, z[m] < 0], axis=1).astype(np.int64)).to(canon.device)
+            sums = torch.zeros((uniq.shape[0], 3), dtype=torch.int64, device=canon.device).index_add_(0, inv.reshape(-1), tally)
+            parts.append((uniq.cpu().numpy(), sums.cpu().numpy()))
+        if not parts:
+            return Book(self.S, [], [], [], [], [])
+        pairs, sums = np.concatenate([p for p, _ in parts]), np.concatenate([t for _, t in parts])
+        key, action = pairs[:, 0].copy().view(np.uint64), pairs[:, 1].astype(np.int32)
+        order = np.lexsort((action, key))
+        key, action, sums = key[order], action[order], sums[order]
+        first = np.ones(len(key), bool)
+        first[1:] = (key[1:] != key[:-1]) | (action[1:] != action[:-1])
+        at = np.flatnonzero(first)
+        sums = np.add.reduceat(sums, at, axis=0)
+        keep = sums[:, 0] >= int(min_count)
+        return Book(self.S, key[at][keep], action[at][keep], sums[keep, 0], sums[keep, 1], sums[keep, 2])
+
+    def duplicates(self):
+        """Groups (lists of record names, in the set's order) of records whose sequences of canonical keys are equal ply for ply:
+        one key per record of the replay -- the empty board, the position after every entry, set-up entries included -- the
+        same length and the same key everywhere.  A record that was cut short counts with the records it has.  Candidates are
+        found by a signature folded on the host, sig = sm(sig ^ canon_j) from sig = 0, and confirmed on the sequences."""
+        seqs = {}
+        for ch in self.replay():
+            n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
+            base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]) + np.arange(len(ch.games))
+            have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1       # records base .. base + have - 1
+            index = np.concatenate([b + np.arange(h) for b, h in zip(base, have)]).astype(np.int32)
+            canon = _host(self.backend.keys(index, None)[1], np.uint64)
+            at = 0
+            for g, h in zip(ch.games, have):
+                seqs[g] = canon[at:at + int(h)].copy()
+                at += int(h)
+        games = sorted(seqs)
+        sig = np.zeros(len(games), np.uint64)
+        length = np.array([len(seqs[g]) for g in games], np.int64)
+        for j in range(int(length.max()) if len(games) else 0):
+            live = np.flatnonzero(length > j)
+            sig[live] = sm64(sig[live] ^ np.array([seqs[games[i]][j] for i in live], np.uint64))
+        buckets = collections.OrderedDict()
+        for i, g in enumerate(games):
+            buckets.setdefault((int(length[i]), int(sig[i])), []).append(g)
+        out = []
+        for cand in buckets.values():
+            while len(cand) > 1:                       # confirmed against the first; what differs waits for its own turn
+                same = [g for g in cand if np.array_equal(seqs[g], seqs[cand[0]])]
+                if len(same) > 1:
+                    out.append(same)
+                cand = [g for g in cand if g not in same]
+        return [[self.records[g].name for g in group] for group in sorted(out)]
 
     # ------------------------------------------------------------------ the strength measure
     def score(self, net, batch=4096, symmetry="identity", bucket=20, seed=0, keep_policy=False):
@@ -427,6 +619,9 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--json", default=None, help="write the counts and figures as one JSON document to this file")
     ap.add_argument("--compat-unknown-result", action="store_true",
                     help="label the moves of a record without a decided result -1, as the reference does, instead of leaving them out")
+    ap.add_argument("--book", default=None, help="write the opening book of the records to this .npz")
+    ap.add_argument("--book-plies", type=int, default=30, help="moves whose node index is below N enter the book (default 30)")
+    ap.add_argument("--duplicates", action="store_true", help="list the records that are one game, in any orientation")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -455,6 +650,19 @@ def main(argv=None, out=sys.stdout):
                 out.write(format_bucket(d, "%d-%d" % (d["first_move"], d["first_move"] + a.bucket - 1)) + "\n")
             out.write(format_bucket(res["total"], "total") + "\n")
             doc["score"] = {"net": res["net"], "bucket_width": a.bucket, "buckets": res["buckets"], "total": res["total"]}
+        if a.book:
+            book = rs.book(plies=a.book_plies)
+            book.save(a.book)
+            out.write("book %d entries in %d positions from %d moves (plies < %d) -> %s\n" % (
+                len(book), len(np.unique(book.key)), int(book.count.sum()), a.book_plies, a.book))
+            doc["book"] = {"file": a.book, "plies": a.book_plies, "entries": len(book), "positions": int(len(np.unique(book.key))),
+                           "moves": int(book.count.sum())}
+        if a.duplicates:
+            groups = rs.duplicates()
+            for names in groups:
+                out.write("duplicates: %s\n" % " ".join(names))
+            out.write("duplicate groups %d\n" % len(groups))
+            doc["duplicates"] = groups
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))
