@@ -324,7 +324,7 @@ __global__ __launch_bounds__(512) void k_conv8w(const char *__restrict__ xb, con
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         const float f = v[j] + (float)__builtin_bit_cast(half4, bvi[qn][nt])[j];
-                        o[j] = (_Float16)(f > 0.f ? f : 0.f);
+                        o[j] = (_Float16)__builtin_elementwise_maximum(f, 0.f);   // v_maximum3_f32: NaN passes (epilogue contract)
                     }
                     const intx2 oi = __builtin_bit_cast(intx2, o);
                     if (nt == 0) SGT_DS_WRITE64(a0, oi, mt * 8192 + qn * 256);

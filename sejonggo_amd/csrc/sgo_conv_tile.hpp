@@ -236,7 +236,7 @@ static inline dim3 grid_pairs(const launch_geom &g) { return dim3(8 * 2 * (g.xcd
                 half4 o;                                                                                              \
                 _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                       \
                     const float f = v[j] + (float)__builtin_bit_cast(half4, bvi[qn][nt])[j];                          \
-                    o[j] = (_Float16)(f > 0.f ? f : 0.f);                                                             \
+                    o[j] = (_Float16)__builtin_elementwise_maximum(f, 0.f);  /* v_maximum3_f32: NaN passes */ \
                 }                                                                                                     \
                 const intx2 oi = __builtin_bit_cast(intx2, o);                                                        \
                 if (qn == 0 && nt == 0) SGT_DS_WRITE64(a00, oi, mt * 4096);                                           \

@@ -151,7 +151,8 @@ __global__ __launch_bounds__(THREADS) void k_heads(const char *__restrict__ y, c
             c += __shfl_xor(c, 1);
             if ((lane & 7) == 0 && pix < P) {
                 const int pos = pix / G::T2, px = pix - pos * G::T2;
-                const float h = fmaxf(c + hb, 0.f);
+                const float hs = c + hb;
+                const float h = __builtin_elementwise_maximum(hs, 0.f);   // IEEE maximum: passes NaN on (fmaxf would return the 0)
                 // flatten order k = pixel * 2 + channel; outputs 0, 1 -> policy rows, 2, 3 -> value rows
                 *reinterpret_cast<_Float16 *>(smem + (o_lane >> 1) * G::H_BYTES + (pos * G::ROWH + px * 2 + (o_lane & 1)) * 2) = (_Float16)h;
             }
@@ -198,7 +199,8 @@ __global__ __launch_bounds__(THREADS) void k_heads(const char *__restrict__ y, c
             const int out0 = (nt - G::NPT) * 16 + q * 4;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const float v1 = fmaxf(acc[i][r] + (float)v_fc1_b[out0 + r], 0.f);
+                const float vs = acc[i][r] + (float)v_fc1_b[out0 + r];
+                const float v1 = __builtin_elementwise_maximum(vs, 0.f);  // NaN passes, as above
                 vp += v1 * (float)v_fc2_w[out0 + r];
             }
         }

@@ -465,7 +465,8 @@ __global__ __launch_bounds__(256) void k_bias_act(long n8, int C8, const half8_t
     for (; i < n8; i += stride) {
         half8_t r = x[i] + bias[i % C8];
         if (skip) r = r + skip[i];
-        out[i] = __builtin_elementwise_max(r, zero);
+        // IEEE maximum (v_pk_maximum3_f16), not maxNum: a NaN passes, -0 becomes +0
+        out[i] = __builtin_elementwise_maximum(r, zero);
     }
 }
 

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(512) void k_stem(const char *__restrict__ xb, const
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                     const float f = acc[mt][2 * j + (e >> 2)][e & 3] + (float)bv[j][e];
-                    o[e] = (_Float16)(f > 0.f ? f : 0.f);
+                    o[e] = (_Float16)__builtin_elementwise_maximum(f, 0.f);   // v_maximum3_f32: NaN passes (epilogue contract)
                 }
                 if (p < M) *reinterpret_cast<half8 *>(yb + (unsigned)(p * YROW + (wc * 64 + j * 32 + (lane >> 4) * 8) * 2)) = o;
             }

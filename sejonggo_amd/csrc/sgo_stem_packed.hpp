@@ -179,7 +179,7 @@ __global__ __launch_bounds__(512) void k_stem_packed(const uint32_t *__restrict_
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                     const float f = acc[mt][2 * j + (e >> 2)][e & 3] + (float)bv[e] + col * (e < 4 ? c0[e & 3] : c1[e & 3]);
-                    o[e] = (_Float16)(f > 0.f ? f : 0.f);
+                    o[e] = (_Float16)__builtin_elementwise_maximum(f, 0.f);   // v_maximum3_f32: NaN passes (epilogue contract)
                 }
                 if (p < M) *reinterpret_cast<half8 *>(yb + (size_t)p * YROW + (eo + j * 32) * 2) = o;
             }

@@ -105,11 +105,18 @@ class _IntCase(object):
 _INT = {}
 
 
+def int_case(L, S):
+    """the integer case of board size S, built once per session (also used by tests/test_gpu_conv_epilogue.py)"""
+    if S not in _INT:
+        _INT[S] = _IntCase(L, S)
+    return _INT[S]
+
+
 @pytest.mark.parametrize("n", BATCHES)
 @pytest.mark.parametrize("S", SIZES)
 def test_exact_on_integers(L, S, n):
     import torch
-    c = _INT.get(S) or _INT.setdefault(S, _IntCase(L, S))
+    c = int_case(L, S)
     pol, val = run_heads(L, S, n, c.y, c.head_w, c.head_b, c.bank, c.p_fc_b, c.v_fc1_b, c.v_fc2_w, c.v_fc2_b)
     assert bool((pol[n:] == SENTINEL).all()) and bool((val[n:] == SENTINEL).all()), "rows >= n were written"
     p, v = pol[:n].double().cpu(), val[:n].double().cpu()

@@ -73,13 +73,19 @@ class _Case(object):
 _CASES = {}
 
 
-@pytest.fixture(scope="module", params=CONFIGS, ids=["19x19_20block", "9x9_4block"])
-def case(request, L):
-    S, blocks, plies = request.param
+def shared_case(L, S, blocks):
+    """the case of configuration (S, blocks) of CONFIGS, built once and shared (also by tests/test_gpu_conv_epilogue.py)"""
+    plies = {(s, b): p for s, b, p in CONFIGS}[(S, blocks)]
     if (S, blocks) not in _CASES:
         _CASES.clear()                      # one 20-block net + its references at a time
         _CASES[(S, blocks)] = _Case(L, S, blocks, plies)
     return _CASES[(S, blocks)]
+
+
+@pytest.fixture(scope="module", params=CONFIGS, ids=["19x19_20block", "9x9_4block"])
+def case(request, L):
+    S, blocks, plies = request.param
+    return shared_case(L, S, blocks)
 
 
 class _Tower(object):
