@@ -50,7 +50,7 @@ extern "C" {
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
  *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
- *   (sgo_keys*, sgo_session_keys). */
+ *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -568,6 +568,71 @@ int sgo_session_keys(sgo_ctx *ctx, int n, const int32_t *slots, int32_t *status,
 /* Where sgo_keys_dev / sgo_keys take z from: 0 = a table z[2][N] in LDS, written once per workgroup (default), 1 = computed where
  * it is used (for A/B timing).  Same bits.  Returns the previous mode; other values only query. */
 int sgo_keys_mode(int mode);
+
+/* ---- chains and ladders: which stones are short of liberties, and can they be caught? ------------------------------------------- */
+/* Per packed record: the liberty count of the chain on every point, the table of the chains with one or two liberties, and for
+ * each of them the verdict of a small exhaustive reader (csrc/sgo_tactics.hip).  Everything is integer.
+ * Inputs of a record, N = S * S: black / white = the bits a < N of planes 0 / 1; the to-play flag is read as sgo_keys_dev reads
+ * it (the top bit of the last word of plane 0; NOT a stone); planes 2 / 3 = black / white one ply ago, bits a < N, used only for
+ * the ko test at the root; padding bits and planes 4..15 are never read.
+ * RULES: the project's.  A move is one ply of sgo_make_play (captures first, then suicide is executed).  A move of a side is
+ * ALLOWED iff sgo_legal_moves allows it in the position with that side to move and `prev` = that side's stones one ply ago: a
+ * point without an empty neighbour only if it captures, and the one-stone ko approximation (play.py:78-80) on `prev`.
+ * LIBERTY MAP: libs[a] = min(255, liberties of the chain on a); 0 on an empty point.
+ * CHAIN TABLE: the chains of either colour with 1 or 2 liberties in ascending order of their ANCHOR, the lowest point index of
+ * the chain.  n_chains = their true number; the first max_chains (1..SGO_TACTICS_MAX_CHAINS) get a row
+ *   int32[8] = {anchor, colour (+1 black, -1 white), size, liberties, status, attack_move, defend_move, nodes}.
+ * THE READER: read(pos, t, attacker_to_move, prev, depth) -> captured | escaped.  t = the anchor, the DEFENDER is the colour on t,
+ * the ATTACKER the other colour; the root has depth 0, a child depth + 1.  On entry: nodes += 1; if nodes >
+ * SGO_TACTICS_MAX_NODES or depth > SGO_TACTICS_MAX_DEPTH the WHOLE QUERY ends unknown at once, whatever the branches above had
+ * found.  L = the liberties of the chain on t.
+ *   Attacker to move:  L >= 3: escaped.  L == 1: captured iff that liberty is allowed for the attacker.  L == 2: for each liberty
+ *     a in ascending index order that is allowed: play it; the chain on t is gone: captured; else the stone just played was
+ *     removed (suicide): next liberty; else recurse with the defender to move: captured if that returns captured.  No liberty
+ *     gives captured: escaped.
+ *   Defender to move:  candidates = the liberties of the chain on t, plus the single liberty of every attacker chain that touches
+ *     it and has exactly one liberty; merged, ascending, duplicates dropped.  For each candidate that is allowed: play it; the
+ *     chain on t is gone or has <= 1 liberty: next candidate; >= 3 liberties: escaped; exactly 2: recurse with the attacker to
+ *     move: escaped if that returns escaped.  No candidate escapes: captured.
+ *   A pass is never considered.  `prev` of a child = the child's mover's stones BEFORE the parent's move.  `prev` at the root =
+ *   plane 2 (black) / 3 (white) of the record when the root's mover is the record's side to move; otherwise there is no ko
+ *   restriction at the root.
+ * QUERIES per chain row:  A = the attacker moves first, always run;  D = the defender moves first, run when L == 1, or L == 2 and
+ * A returned captured.  status bits: 1 = A captured, 2 = D ran and returned captured, 4 = A unknown, 8 = D unknown, 16 = D ran.
+ * attack_move = the first liberty by which A captures (L == 1: that liberty), -1 otherwise and when A is unknown; defend_move =
+ * the first candidate by which D escapes, -1 otherwise.  nodes = the sum of the node counts of the queries that ran; the counter
+ * restarts per query, and a query that ends unknown contributes its count at the moment it ended.  The traversal order is fixed,
+ * so `nodes` pins it.
+ *
+ * sgo_tactics_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_libs uint8 [n][N], d_n_chains int32 [n], d_chains int32 [n][max_chains][8]; of a row's chain rows only the first
+ * min(n_chains, max_chains) are written.  A row whose record index is outside [0, n_records) gives zero libs, n_chains = 0 and
+ * untouched chain rows.  TWO launches on `stream` (k_tactics_chains, k_tactics_read), no allocation, no synchronisation,
+ * capturable; n == 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, max_chains
+ * outside [1, SGO_TACTICS_MAX_CHAINS], a NULL d_records or output. */
+#define SGO_TACTICS_MAX_CHAINS 128
+#define SGO_TACTICS_MAX_NODES 512
+#define SGO_TACTICS_MAX_DEPTH 80
+#define SGO_TACTICS_A_CAPTURED 1
+#define SGO_TACTICS_D_CAPTURED 2
+#define SGO_TACTICS_A_UNKNOWN 4
+#define SGO_TACTICS_D_UNKNOWN 8
+#define SGO_TACTICS_D_RAN 16
+int sgo_tactics_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int max_chains, uint8_t *d_libs,
+                    int32_t *d_n_chains, int32_t *d_chains, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity
+ * tests.  Chain rows beyond min(n_chains, max_chains) come back as the caller filled them. */
+int sgo_tactics(int S, int n, const uint32_t *records, int max_chains, uint8_t *libs, int32_t *n_chains, int32_t *chains);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], libs [n][N], n_chains [n], chains [n][max_chains][8].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot
+ * that is not a holding session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be
+ * listed repeatedly. */
+int sgo_session_tactics(sgo_ctx *ctx, int n, const int32_t *slots, int max_chains, int32_t *status, uint8_t *libs, int32_t *n_chains,
+                        int32_t *chains, void *stream);
+/* Which of the two launches the calls above make: 0 = both (default), 1 = k_tactics_chains only (chain rows listed, not read
+ * out), 2 = k_tactics_read only, on the table an earlier call left in the same buffers (for timing the kernels apart).  Returns
+ * the previous stage; other values only query. */
+int sgo_tactics_stage(int stage);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

@@ -20,6 +20,7 @@ SGO_ERR_ARG = -1
 SGO_ERR_CAPACITY = -201
 SGO_ACTION_ANALYSIS = -2     # sgo_move_record.action of a search-only record (sgo_session_analyze)
 REPORT_MAX_TOP, REPORT_MAX_DEPTH = 16, 32
+TACTICS_MAX_CHAINS, TACTICS_MAX_NODES, TACTICS_MAX_DEPTH = 128, 512, 80
 
 # every symbol include/sgo.h declares (tests/test_abi.py checks the built library exports them all)
 SYMBOLS = [
@@ -36,6 +37,7 @@ SYMBOLS = [
     "sgo_rollout_list", "sgo_rollout_step", "sgo_rollout_result",
     "sgo_records_create", "sgo_records_destroy", "sgo_records_replay", "sgo_records_list", "sgo_records_score_dev",
     "sgo_keys_dev", "sgo_keys", "sgo_session_keys", "sgo_keys_mode",
+    "sgo_tactics_dev", "sgo_tactics", "sgo_session_tactics", "sgo_tactics_stage",
 ]
 
 
@@ -181,6 +183,10 @@ def load():
     lib.sgo_keys.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
     lib.sgo_session_keys.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
     lib.sgo_keys_mode.argtypes = [C.c_int]
+    lib.sgo_tactics_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_tactics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_tactics_stage.argtypes = [C.c_int]
+    lib.sgo_session_tactics.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     _lib = lib
     return lib
 

@@ -1,6 +1,6 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
-// sgo_keys.hip).  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the kernels are in
+// sgo_keys.hip) and of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip).  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the kernels are in
 // sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the SejongGoEngine a GTP
 // front-end drives.
 #include <string.h>
@@ -15,6 +15,9 @@ namespace sgo {
 // csrc/sgo_keys.hip: k_session_keys on device pointers
 int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, uint64_t *d_key0, uint64_t *d_canon,
                         int32_t *d_mask, hipStream_t st);
+// csrc/sgo_tactics.hip: k_session_roots, k_tactics_chains and k_tactics_read on device pointers
+int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
+                           int32_t *d_n_chains, int32_t *d_chains, hipStream_t st);
 }
 
 // Stage n slots (+ optional actions / colours) in the context's staging area, as sgo_start_games does: wait until the previous
@@ -244,6 +247,47 @@ int sgo_session_keys(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, u
         key0[i] = hk[i];
         canon[i] = hc[i];
         mask[i] = hm[i];
+    }
+    return SGO_OK;
+}
+
+int sgo_session_tactics(sgo_ctx *x, int n, const int32_t *slots, int max_chains, int32_t *status, uint8_t *libs, int32_t *n_chains,
+                        int32_t *chains, void *stream) {
+    if (!x || n < 0 || max_chains < 1 || max_chains > SGO_TACTICS_MAX_CHAINS || (n && (!slots || !status || !libs || !n_chains || !chains))) {
+        set_error("sgo_session_tactics: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    if (n > c.G) { set_error("sgo_session_tactics: more slots than the context has"); return SGO_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_tactics: slot out of range"); return SGO_ERR_ARG; }
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    // slots | record index | status | n_chains | chains | libs; everything behind the index comes back in one copy
+    const int N = c.S * c.S;
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)max_chains * n, lb = al8((size_t)n * N);
+    const int rc = session_buffer(x, 4 * ib + cb + lb);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    memcpy(h, slots, sizeof(int32_t) * n);
+    SGO_HIP(hipMemcpyAsync(d, h, ib, hipMemcpyHostToDevice, st));
+    const int lrc = launch_session_tactics(c, n, reinterpret_cast<const int32_t *>(d), max_chains, reinterpret_cast<int32_t *>(d + 2 * ib),
+                                           reinterpret_cast<int32_t *>(d + ib), d + 4 * ib + cb, reinterpret_cast<int32_t *>(d + 3 * ib),
+                                           reinterpret_cast<int32_t *>(d + 4 * ib), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, 2 * ib + cb + lb, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hn = reinterpret_cast<const int32_t *>(h + 3 * ib);
+    const int32_t *hc = reinterpret_cast<const int32_t *>(h + 4 * ib);
+    const uint8_t *hl = h + 4 * ib + cb;
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        n_chains[i] = hn[i];
+        memcpy(libs + (size_t)i * N, hl + (size_t)i * N, N);
+        const int stored = hn[i] < max_chains ? hn[i] : max_chains;   // the chain rows behind them were not written
+        memcpy(chains + (size_t)i * max_chains * 8, hc + (size_t)i * max_chains * 8, sizeof(int32_t) * 8 * (size_t)stored);
     }
     return SGO_OK;
 }

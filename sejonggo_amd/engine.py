@@ -745,6 +745,21 @@ class SessionEngine(SelfPlayEngine):
                                                  _lib.ptr(out["canon"]), _lib.ptr(out["mask"]), self._stream_ptr()), "sgo_session_keys")
         return out
 
+    def tactics(self, slots, max_chains=None):
+        """Chains, liberties and ladders of the root positions of the listed holding sessions (sgo_session_tactics; include/sgo.h
+        "chains and ladders"): a tactics.Tactics with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session;
+        that row stays zero).  Boards and trees are only read."""
+        from .tactics import Tactics
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n, mc = len(slots), int(max_chains or _lib.TACTICS_MAX_CHAINS)
+        out = Tactics(self.S, np.zeros((n, self.S * self.S), np.uint8), np.zeros(n, np.int32), np.zeros((n, mc, 8), np.int32))
+        out.status = np.zeros(n, np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_tactics(self.ctx, C.c_int(n), _lib.ptr(slots), C.c_int(mc), _lib.ptr(out.status),
+                                                    _lib.ptr(out.libs), _lib.ptr(out.n_chains), _lib.ptr(out.chains),
+                                                    self._stream_ptr()), "sgo_session_tactics")
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

@@ -233,6 +233,14 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the slot is not a holding session")
         return int(k["canon"][0]), int(k["mask"][0])
 
+    def tactics(self):
+        """The chains with one or two liberties of the position on the board, read out (engine.SessionEngine.tactics): a list of
+        tactics.Chain in ascending anchor order."""
+        t = self.engine.tactics([self.slot])
+        if int(t.status[0]):
+            raise ValueError("the slot is not a holding session")
+        return t.chains_of(0)
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -283,7 +291,7 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "sgo-book", "quit"])
+                          "sgo-ownership", "sgo-book", "sgo-ladders", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -441,7 +449,15 @@ class GTPEngine(object):
     def quit(self):
         return ""
 
-    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book"}      # GTP private extensions carry a hyphen; methods cannot
+    def sgo_ladders(self):
+        """Private extension `sgo-ladders`: one line per chain with one or two liberties that the reader catches (include/sgo.h
+        "chains and ladders") -- the anchor vertex, colour, size, liberties, `capturable` (caught when the attacker moves first) or
+        `dead` (caught even when the defender moves first), then `attack V` and `defend V` (none: no such move)."""
+        from .tactics import format_chain
+        chains = self._engine_method("tactics")()
+        return "\n".join(format_chain(c, self._vertex) for c in chains if c.capturable or c.dead)
+
+    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -331,6 +331,33 @@ class DeviceRecords(object):
                             "sgo_keys_dev")
         return key0, canon, mask, action
 
+    def tactics(self, index, max_chains=128):
+        """(libs uint8 [n, N], n_chains int32 [n], chains int32 [n, max_chains, 8]) device tensors of the listed records
+        (sgo_tactics_dev, two launches; include/sgo.h "chains and ladders").  Chain rows behind min(n_chains, max_chains) are zero;
+        an index outside the object gives the zero row."""
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        index = index.contiguous()
+        n, mc = int(index.shape[0]), int(max_chains)
+        libs = torch.zeros((n, self.N), dtype=torch.uint8, device=self.device)
+        n_chains = torch.zeros(n, dtype=torch.int32, device=self.device)
+        chains = torch.zeros((n, mc, 8), dtype=torch.int32, device=self.device)
+        if n:
+            P = self._lib.ptr
+            self._lib.check(self.lib.sgo_tactics_dev(C.c_int(self.S), C.c_int(n), C.c_void_p(self.rec_ptr), C.c_int(self.cap), P(index),
+                                                     C.c_int(mc), P(libs), P(n_chains), P(chains), self._lib.stream_ptr()),
+                            "sgo_tactics_dev")
+        return libs, n_chains, chains
+
+    def stones(self, index):
+        """int8 [n, N] (host): +1 black, -1 white on the listed records; an index outside the object gives the empty board."""
+        from .tactics import stones_of
+        index = np.asarray(index, dtype=np.int64)
+        ok = (index >= 0) & (index < self.cap)
+        idx = self.torch.from_numpy(np.where(ok, index, 0)).to(self.device)
+        planes = self.records.index_select(0, idx)[:, :2 * self.NW].contiguous().cpu().numpy()
+        return stones_of(self.S, planes) * ok[:, None].astype(np.int8)
+
 
 class Chunk(object):
     """What one replay call left on the device, one row per ENTRY of its games (set-up stones included): index (the record
@@ -426,6 +453,27 @@ class RecordSet(object):
         for ch, (key0, canon, mask, action) in self._keyed():
             ch.key0, ch.canon = _host(key0, np.uint64), _host(canon, np.uint64)
             ch.mask, ch.canon_action = _host(mask), _host(action)
+            yield ch
+
+    # ------------------------------------------------------------------ chains and ladders
+    def tactics(self, max_chains=128, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `tactics`, a tactics.Tactics with one row per RECORD of the
+        chunk (one backend call per chunk): row ch.index[e] is the position before entry e, row ch.index[e] + 1 the position
+        after it.  Records that were not written (behind a refused entry) give the zero row.  stones=True adds ch.stones, int8
+        [records, N] (+1 black, -1 white), rows as in `tactics`.  The chain table takes 32 * max_chains bytes per record: for a
+        large collection give the set a smaller max_entries (the chunk size) or a smaller max_chains."""
+        from .tactics import Tactics
+        for ch in self.replay():
+            n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
+            base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int64) + np.arange(len(ch.games))
+            have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1
+            index = np.full(int(n_entries.sum()) + len(ch.games), -1, np.int32)
+            for b, h in zip(base, have):
+                index[int(b):int(b + h)] = np.arange(int(b), int(b + h))
+            libs, n_chains, chains = self.backend.tactics(index, max_chains)
+            ch.tactics = Tactics(self.S, _host(libs, np.uint8), _host(n_chains), _host(chains))
+            if stones:
+                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
             yield ch
 
     def book(self, plies=30, min_count=1):

@@ -3,14 +3,17 @@ them set up in one launch (engine.SessionEngine.setup), searched together withou
 all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
-                                           [--energy E] [--games n] [--json FILE] [--rollouts R]
+                                           [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
 stones placed); with --every k the positions before moves 1, 1 + k, 1 + 2k, ... are reviewed.  Means are the search's own
 (the root player's view).  --rollouts R plays every reviewed position out R times with the net's policy (rollout.py; all
 positions of a chunk in one batch) and adds the score lead (mean of black - white over the rollouts, minus komi), black's share
-of the rollouts won on the board (komi aside) and the number of stones judged dead.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+of the rollouts won on the board (komi aside) and the number of stones judged dead.  --tactics reads the chains and ladders of
+every position of the record in one call (records.RecordSet.tactics) and flags a move `ladder` when it runs out a chain that was
+dead even with its owner to move and is still capturable afterwards, `missed` when it leaves an opponent chain of three or more
+stones standing that could have been caught.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -123,7 +126,50 @@ def _search(engine, slots, sims):
         engine.raise_on_error = keep
 
 
+def move_flags(game, record_set):
+    """{move number: ["ladder", "missed"]} of the B / W moves of `game` (tactics.review_flags) from one RecordSet.tactics pass over
+    a set that holds the game as its only record."""
+    from .tactics import review_flags
+    out = {}
+    for ch in record_set.tactics(stones=True):
+        t, m = ch.tactics, 0
+        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+            if is_setup:
+                continue
+            m += 1
+            if not ch.valid[e]:
+                continue
+            r = int(ch.index[e])
+            out[m] = review_flags(game.size, int(action), int(colour), ch.stones[r], t.chains_of(r), ch.stones[r + 1], t.chains_of(r + 1),
+                                  t.libs[r + 1])
+    return out
+
+
+def add_tactics(rows, game, record_set=None):
+    """Adds `tactics` (the flag list of move_flags) to every row of a review.  record_set None: a device RecordSet of the game."""
+    from .records import Record, RecordSet
+    own = record_set is None
+    if own:
+        entries = [(int(a), int(c)) for a, c in game.moves]
+        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    try:
+        flags = move_flags(game, record_set)
+    finally:
+        if own:
+            record_set.close()
+    for row in rows:
+        row["tactics"] = flags.get(row["move_number"], [])
+    return rows
+
+
 def format_row(row):
+    text = _format_row(row)
+    if row.get("tactics"):
+        text += "  | " + " ".join(row["tactics"])
+    return text
+
+
+def _format_row(row):
     if "error" in row and row["fail_at"] < 0:
         return "%4d %s %-4s  search failed (%d)" % (row["move_number"], row["colour"], row["played"], row["error"])
     if "error" in row:
@@ -169,6 +215,7 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--games", type=int, default=None, help="session slots = positions per chunk (default: as many as reviewed, at most 1024)")
     ap.add_argument("--symmetry", default="random1", choices=["random1", "avg8", "identity"])
     ap.add_argument("--rollouts", type=int, default=0, help="policy rollouts per position: score lead, black's win share, dead stones")
+    ap.add_argument("--tactics", action="store_true", help="flag moves that run out a dead ladder or miss a capturable chain")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
@@ -187,6 +234,8 @@ def main(argv=None, out=sys.stdout):
         if a.net == "best":
             from .predicting_queue_worker import destroy_predicting_workers
             destroy_predicting_workers(conf['GPUs'][:1])
+    if a.tactics:
+        add_tactics(rows, game)
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.json:
