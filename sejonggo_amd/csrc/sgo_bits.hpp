@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/sgo.h"
+
 namespace sgo {
 
 template <int S>
@@ -420,6 +422,29 @@ SGO_DEV void store_plane(uint32_t *rec, int plane, const uint32_t (&w)[Geo<S>::N
 
 template <int S>
 SGO_DEV bool white_to_play(const uint32_t *rec) { return (rec[Geo<S>::META_WORD] & Geo<S>::META_BIT) != 0; }
+
+// ---- external moves (sgo_session_play, sgo_session_setup, sgo_records_replay) ---------------------------
+// An external move a on a record: SGO_OK, SGO_ERR_RANGE (a outside [0, A)) or SGO_ERR_OCCUPIED (a stone on the point).
+template <int S>
+SGO_DEV int external_move_status(const uint32_t *rec, int a) {
+    using G = Geo<S>;
+    int rc = SGO_OK;
+    if (a < 0 || a >= G::A) rc = SGO_ERR_RANGE;
+    else if (a < G::N && (((rec[a >> 5] | rec[G::NW + (a >> 5)]) >> (a & 31)) & 1u)) rc = SGO_ERR_OCCUPIED;
+    return rc;
+}
+// Who is to play on the record (+1 black, -1 white), and whether colour col (0 = the side to move) moves in turn.
+template <int S>
+SGO_DEV bool moves_in_turn(const uint32_t *rec, int col, int &to_play) {
+    to_play = white_to_play<S>(rec) ? -1 : 1;
+    return col == 0 || col == to_play;
+}
+// Word i of the legal set of the empty board: every point and the pass.
+template <int S>
+SGO_DEV uint32_t empty_legal_word(int i) {
+    constexpr int bits = Geo<S>::A - 32 * (Geo<S>::NW - 1);
+    return (i == Geo<S>::NW - 1 && bits < 32) ? ((1u << bits) - 1u) : 0xffffffffu;
+}
 
 // Core of one ply on the current pair.  p0/p1 are filled with planes 0,1 (black, white) of `in`, and on return hold
 // the new pair (meta bit set for the new side to move); optionally the legal set of the new position is produced.

@@ -31,8 +31,21 @@ inline bool size_ok(int S) { return S == 5 || S == 7 || S == 9 || S == 13 || S =
     default: ::sgo::set_error("unsupported board size"); return SGO_ERR_ARG; \
     }
 
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+struct DeviceGuard {       // the calling thread's current device is left as it was
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 // symmetry.py:12-42 -- SWAP tables by float rotation + round, as the reference builds them
 void build_sym_lut(int S, int k, int32_t *lut);
+// the eight tables [8][S * S + 1] built and copied to device memory (a blocking copy)
+hipError_t upload_sym_luts(int S, int32_t *d_lut);
 
 // kernels launched from more than one translation unit
 int launch_advance_legal(int S, int n, const uint32_t *d_in, const int32_t *d_in_idx, const int32_t *d_moves,

@@ -174,14 +174,7 @@ __global__ __launch_bounds__(64) void k_start(Ctx c, int n, StageLayout L, int h
     if (c.max_moves == 0) st.phase = PH_DONE;
     if (session) { st.session = 1; st.phase = PH_HOLD; st.temperature = 0; }
     for (int i = lane; i < G::RW; i += 64) c.pos[gb0 * G::RW + i] = 0;
-    for (int i = lane; i < G::NW; i += 64) {
-        uint32_t w = 0xffffffffu;
-        if (i == G::NW - 1) {
-            int bits = G::A - 32 * (G::NW - 1);
-            w = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
-        }
-        c.legal[gb0 * G::NW + i] = w;
-    }
+    for (int i = lane; i < G::NW; i += 64) c.legal[gb0 * G::NW + i] = empty_legal_word<S>(i);
     // whatever the slot's previous game still holds of the shared pool goes back to it
     for (int j = lane; j < c.ovf_cap; j += 64) pool_release(c, (size_t)g * c.ovf_cap + j);
     for (int b = lane; b < c.L - 1; b += 64) c.freeList[(size_t)g * c.L + b] = c.L - 1 - b;  // pops give 1,2,3,...: private ids first
@@ -269,9 +262,7 @@ static int ctx_alloc(Ctx &c) {
     }
     SGO_HIP(hipHostMalloc((void **)&c.hstatus, sizeof(DevStatus), hipHostMallocDefault));
     memset(c.hstatus, 0, sizeof(DevStatus));
-    std::vector<int32_t> lut((size_t)8 * c.A);
-    for (int k = 0; k < 8; k++) build_sym_lut(c.S, k, lut.data() + (size_t)k * c.A);
-    SGO_HIP(hipMemcpy(c.symLut, lut.data(), sizeof(int32_t) * lut.size(), hipMemcpyHostToDevice));
+    SGO_HIP(upload_sym_luts(c.S, c.symLut));
     return SGO_OK;
 }
 

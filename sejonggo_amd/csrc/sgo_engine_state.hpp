@@ -124,6 +124,25 @@ static StageLayout stage_layout(int n, int APAD, int nu, bool has_noise) {
     return L;
 }
 
+// a session slot between two commands: the state every sgo_session_* call and every reader of a session's root asks for
+__device__ __forceinline__ bool holding(const GameState &s) { return s.session && s.phase == PH_HOLD && !s.error; }
+
+// physical block behind local id `blk` of game g: the private region, or one dependent load for an overflow id.  gb0 = g * cap is
+// passed in by Eng<S>, which keeps it: recomputed here, k_search's listing changes
+__device__ __forceinline__ size_t phys_block(const Ctx &c, int g, size_t gb0, int blk) {
+    if (blk < c.cap) return gb0 + blk;
+    return (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
+}
+__device__ __forceinline__ size_t phys_block(const Ctx &c, int g, int blk) { return phys_block(c, g, (size_t)g * c.cap, blk); }
+
+// csrc/sgo_session.hip: k_session_roots on device pointers -- per listed slot the record index (physical block) of a holding
+// session's root position and SGO_OK, or -1 and SGO_ERR_STATE.  The records are c.pos, G * cap + pool_blocks of them.
+int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st);
+static inline int ctx_records(const Ctx &c) {
+    const long blocks = (long)c.G * c.cap + c.pool_blocks;
+    return blocks < 0x7fffffffl ? (int)blocks : 0x7fffffff;
+}
+
 // Give the shared block behind one entry of the overflow map (index mi = g * ovf_cap + j: overflow id cap + j of game g) back
 // to the pool, if it is backed.  Releases go to poolRet; k_compact merges them into poolFree between two k_search launches, so
 // a pop never meets a push.

@@ -4,7 +4,8 @@
 // of its own: tests/test_engine_isa.py pins the kernel set of sgo_engine.hip, and nothing here touches k_search.
 //
 //   k_keys<S, INLINE>     per listed record: key0, canon, mask, canon_action
-//   k_session_keys<S>     the same for the root records of holding session slots (sgo_session_keys)
+//
+// sgo_session_keys runs the same kernel over the context's records, with the root index k_session_roots (sgo_session.hpp) writes.
 //
 // Kernel form: one 32-lane HALF of a wavefront per record, one board row per lane (sgo_rows.hpp load_row), as k_records_score.
 // A record gives 2 of its 16 planes; they are read in place through the index list, no record is copied.  Each lane walks the
@@ -14,7 +15,7 @@
 //
 // z comes from a table z[2][N] in LDS (5.8 KB at 19x19), written once per 256-thread workgroup, which then strides over the
 // records (INLINE = false, the product), or is computed where it is needed (INLINE = true: eight splitmix rounds per stone;
-// sgo_keys_mode selects it for A/B timing, and the few rows of k_session_keys use it: no table to fill).  Same bits either way.
+// sgo_keys_mode selects it for A/B timing, and the few rows of sgo_session_keys use it: no table to fill).  Same bits either way.
 //
 // Nothing branches around a shuffle on a per-record condition: a half whose row is out of range or does not exist reads no
 // stones and only its final stores differ.
@@ -24,8 +25,6 @@
 #include "sgo_rows.hpp"
 
 namespace sgo {
-
-static inline int cdiv_k(long a, long b) { return (int)((a + b - 1) / b); }
 
 __host__ __device__ __forceinline__ uint64_t sm64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -148,51 +147,11 @@ __global__ __launch_bounds__(256) void k_keys(int n, const uint32_t *records, in
     }
 }
 
-// One half of a wavefront per listed slot: the root record of a holding session (what sgo_game_board shows) is keyed in place;
-// anything else gets SGO_ERR_STATE and no other output.  The context is only read.
-template <int S>
-__global__ __launch_bounds__(64) void k_session_keys(Ctx c, int n, const int32_t *slots, int32_t *status, uint64_t *key0,
-                                                     uint64_t *canon_out, int32_t *mask_out) {
-    using G = Geo<S>;
-    const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
-    const int i = blockIdx.x * 2 + half;
-    const bool valid = i < n;
-    const uint32_t *rec = nullptr;
-    if (valid) {
-        const int g = slots[i];
-        const GameState &s = c.gs[g];
-        if (s.session && s.phase == PH_HOLD && !s.error) {
-            const int blk = s.root_blk;
-            const size_t ph = blk < c.cap ? (size_t)g * c.cap + blk
-                                          : (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
-            rec = c.pos + ph * G::RW;
-        }
-    }
-    uint64_t key[8];
-    stone_keys<S, true>(rec, nullptr, y, key);
-    if (valid && y == 0) {
-        status[i] = rec ? SGO_OK : SGO_ERR_STATE;
-        if (rec) {
-            if (rec[G::META_WORD] & G::META_BIT) {
-                const uint64_t zw = zkey(S, 2, 0);
-#pragma unroll
-                for (int k = 0; k < 8; k++) key[k] ^= zw;
-            }
-            uint64_t canon;
-            int mask, action;
-            canonical<S>(key, -1, canon, mask, action);
-            key0[i] = key[0];
-            canon_out[i] = canon;
-            mask_out[i] = mask;
-        }
-    }
-}
-
 static int g_keys_mode = 0;       // 0: the LDS table, 1: splitmix inline
 
 static int launch_keys(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
                        uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_action, hipStream_t st) {
-    const int blocks = cdiv_k(n, 8) < 4096 ? cdiv_k(n, 8) : 4096;
+    const int blocks = cdiv(n, 8) < 4096 ? cdiv(n, 8) : 4096;
     if (g_keys_mode == 1) {
         SGO_DISPATCH(S, k_keys<kS, true><<<dim3(blocks), dim3(256), 0, st>>>(n, d_records, n_records, d_index, d_target, d_key0, d_canon,
                                                                               d_mask, d_action));
@@ -204,10 +163,16 @@ static int launch_keys(int S, int n, const uint32_t *d_records, int n_records, c
     return SGO_OK;
 }
 
-// sgo_session_keys' launch (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
-int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, uint64_t *d_key0, uint64_t *d_canon,
-                        int32_t *d_mask, hipStream_t st) {
-    SGO_DISPATCH(c.S, k_session_keys<kS><<<dim3(cdiv_k(n, 2)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_key0, d_canon, d_mask));
+// sgo_session_keys' launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory.
+// k_session_roots names the root records, k_keys reads them in place from the context's blocks -- in the inline form whatever
+// sgo_keys_mode says: no table is worth filling for these few rows.  A refused slot (index -1) gets the zero row.
+int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint64_t *d_key0,
+                        uint64_t *d_canon, int32_t *d_mask, hipStream_t st) {
+    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
+    if (rc != SGO_OK) return rc;
+    const int blocks = cdiv(n, 8) < 4096 ? cdiv(n, 8) : 4096;
+    SGO_DISPATCH(c.S, k_keys<kS, true><<<dim3(blocks), dim3(256), 0, st>>>(n, c.pos, ctx_records(c), d_index, nullptr, d_key0, d_canon,
+                                                                           d_mask, nullptr));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
 }

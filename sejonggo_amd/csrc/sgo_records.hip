@@ -8,7 +8,8 @@
 // k_records_replay: one 32-lane HALF of a wavefront per game, one board row per lane (sgo_rows.hpp), as k_board_advance_rows and
 // k_rollout_step.  The two halves of a wave run in LOCKSTEP (the flood fills of sgo_rows.hpp vote over the whole wave): the loop
 // runs to the longer of the two lists, and a half whose game has ended, was refused or does not exist plays passes on the
-// position it holds and writes nothing outside its own LDS.
+// position it holds and writes nothing outside its own LDS.  A recorded move is tested and its turn decided as sgo_session_play and
+// sgo_session_setup do it (sgo_bits.hpp: external_move_status, moves_in_turn).
 //
 // The running record lives in LDS, two records per half (rows::advance_record_rows needs in != out), with a barrier between
 // plies; every finished record and its legal words are copied out from there, coalesced.  Global memory is WRITE-ONLY for this
@@ -18,14 +19,10 @@
 // verbatim copy.  Results do not depend on the order of the rows.
 #include <string.h>
 
-#include <vector>
-
 #include "sgo_common.hpp"
 #include "sgo_rows.hpp"
 
 namespace sgo {
-
-static inline int cdiv_g(long a, long b) { return (int)((a + b - 1) / b); }
 
 struct Recs {          // passed by value to the kernels
     int max_games, max_entries;
@@ -60,14 +57,7 @@ __global__ __launch_bounds__(64) void k_records_replay(Recs d, int n_games, int 
         uint32_t *both = &rec[half][0][0];                       // the two records of the half are contiguous
         for (int i = y; i < 2 * G::RW; i += 32) both[i] = 0u;
     }
-    if (y < G::NW) {
-        uint32_t w = 0xffffffffu;
-        if (y == G::NW - 1) {
-            constexpr int bits = G::A - 32 * (G::NW - 1);
-            w = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
-        }
-        lg[half][y] = w;
-    }
+    if (y < G::NW) lg[half][y] = empty_legal_word<S>(y);
     __syncthreads();
     if (has) {
         uint32_t *o = d.rec + base * G::RW;
@@ -85,12 +75,11 @@ __global__ __launch_bounds__(64) void k_records_replay(Recs d, int n_games, int 
         if (live) {
             const int idx = off + j;
             if (idx < n_total) { a = actions[idx]; col = colors[idx]; }
-            if (a < 0 || a >= G::A) rc = SGO_ERR_RANGE;
-            else if (a < G::N && (((in[a >> 5] | in[G::NW + (a >> 5)]) >> (a & 31)) & 1u)) rc = SGO_ERR_OCCUPIED;
+            rc = external_move_status<S>(in, a);
             if (rc) { fail = j; live = false; a = G::N; col = 0; }
         }
-        const int to_play = (in[G::META_WORD] & G::META_BIT) ? -1 : 1;
-        const bool in_turn = col == 0 || col == to_play;
+        int to_play;
+        const bool in_turn = moves_in_turn<S>(in, col, to_play);
         // an idle half passes on the position it holds: it takes part in every vote and touches its own LDS only
         (void)rows::advance_record_rows<S>(in, out, a, !in_turn, lg[half], half, y);
         __syncthreads();
@@ -174,15 +163,6 @@ struct sgo_records {
 };
 
 namespace {
-struct DeviceGuard {       // the calling thread's current device is left as it was
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 size_t stage_words(const sgo_records *r) { return 4 * (size_t)r->d.max_games + 2 * (size_t)r->d.max_entries; }
 
 void free_all(sgo_records *r) {
@@ -214,11 +194,7 @@ sgo_records *sgo_records_create(int S, int max_games, int max_entries, int devic
               hipMalloc((void **)&d.lut, (size_t)8 * r->A * sizeof(int32_t)) == hipSuccess &&
               hipMalloc((void **)&d.stage, sw) == hipSuccess &&
               hipHostMalloc((void **)&r->h_stage, sw, hipHostMallocDefault) == hipSuccess;
-    if (ok) {
-        std::vector<int32_t> lut((size_t)8 * r->A);
-        for (int k = 0; k < 8; k++) build_sym_lut(S, k, lut.data() + (size_t)k * r->A);
-        ok = hipMemcpy(d.lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    ok = ok && upload_sym_luts(S, d.lut) == hipSuccess;
     if (!ok) {
         set_error("sgo_records_create: out of memory (device or pinned host)");
         free_all(r);
@@ -268,7 +244,7 @@ int sgo_records_replay(sgo_records *r, int n_games, const int32_t *n_entries, co
     else memset(h + 4 * mg + me, 0, sizeof(int32_t) * total);
     // ONE copy takes lengths, offsets, (stale) verdicts and both lists over: everything up to the last colour used
     SGO_HIP(hipMemcpyAsync(d.stage, h, sizeof(int32_t) * (4 * mg + me + total), hipMemcpyHostToDevice, st));
-    SGO_DISPATCH(r->S, k_records_replay<kS><<<dim3(cdiv_g(n_games, 2)), dim3(64), 0, st>>>(d, n_games, (int)total));
+    SGO_DISPATCH(r->S, k_records_replay<kS><<<dim3(cdiv(n_games, 2)), dim3(64), 0, st>>>(d, n_games, (int)total));
     SGO_HIP(hipGetLastError());
     SGO_HIP(hipMemcpyAsync(h + 2 * mg, d.stage + 2 * mg, sizeof(int32_t) * 2 * mg, hipMemcpyDeviceToHost, st));   // status, fail_at
     SGO_HIP(hipStreamSynchronize(st));
@@ -295,7 +271,7 @@ int sgo_records_score_dev(sgo_records *r, int n, const int32_t *d_index, const i
     }
     if (n == 0) return SGO_OK;
     DeviceGuard guard(r->device);
-    SGO_DISPATCH(r->S, k_records_score<kS><<<dim3(cdiv_g(n, 2)), dim3(64), 0, (hipStream_t)stream>>>(
+    SGO_DISPATCH(r->S, k_records_score<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, (hipStream_t)stream>>>(
                            r->d, n, d_index, d_target, d_z, d_bucket, n_buckets, d_policy, d_value, sym_k, d_rank, d_best, d_p_target,
                            d_flags, reinterpret_cast<unsigned long long *>(d_counters)));
     SGO_HIP(hipGetLastError());

@@ -3,10 +3,12 @@
 // final_status_list and the review's dead-stone count are made of.  A translation unit of its own: tests/test_engine_isa.py
 // pins the kernel set of sgo_engine.hip, and nothing here touches k_search.
 //
-//   k_rollout_start     clones the source records into the rollout records, zeroes counters and accumulators
-//   k_rollout_sources   the root records of holding session slots -> the source staging array (sgo_rollout_start_sessions)
+//   k_rollout_start     clones the source records into the rollout records, zeroes counters and accumulators; the sources are
+//                       (records, index): host records staged once, device records, or the root records of holding session
+//                       slots in the context's blocks, named by k_session_roots (sgo_session.hpp)
 //   k_rollout_step<S>   one ply of every listed rollout: legal set, weights, pick, make_play, end test, score, accumulation,
-//                       append of the survivors to the next list
+//                       append of the survivors to the next list.  The ply is rows::load_ply / rows::store_ply, the two halves of
+//                       rows::advance_record_rows, around its own legal -> draw -> advance
 //
 // Kernel form: one 32-lane HALF of a wavefront per listed rollout, one board row per lane (sgo_rows.hpp), as
 // k_board_advance_rows.  A step's list is a few thousand rollouts at most, far too few for the lane-per-position form.
@@ -21,14 +23,10 @@
 // on the order of the list, which the survivors' appends (one atomicAdd each) leave unspecified.
 #include <string.h>
 
-#include <vector>
-
 #include "sgo_engine_state.hpp"
 #include "sgo_rows.hpp"
 
 namespace sgo {
-
-static inline int cdiv_r(long a, long b) { return (int)((a + b - 1) / b); }
 
 struct Roll {          // passed by value to the kernels
     int max_r, max_src;
@@ -39,8 +37,8 @@ struct Roll {          // passed by value to the kernels
     unsigned long long *sums;     // [max_src][8]
     int32_t *count;    // [0] entries of the list being filled
     int32_t *lut;      // [8][A] symmetry.py SWAP tables
-    uint32_t *src;     // [max_src][RW] staging of the source records (host records, session roots)
-    int32_t *slots, *sstat;       // [max_src] sgo_rollout_start_sessions: slot ids in, status out
+    uint32_t *src;     // [max_src][RW] staging of the source records of sgo_rollout_start (host records)
+    int32_t *slots, *sroot;       // sgo_rollout_start_sessions: slot ids in [max_src]; status and root record index out [2][max_src]
 };
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -81,24 +79,6 @@ __global__ __launch_bounds__(256) void k_rollout_start(Roll d, int n_src, const 
     }
 }
 
-// One block per listed slot: a holding session's root record (what sgo_game_board shows) goes to the staging array; anything
-// else gets SGO_ERR_STATE.  The context is only read.
-__global__ __launch_bounds__(64) void k_rollout_sources(Ctx c, Roll d, int n) {
-    const int k = blockIdx.x;
-    if (k >= n) return;
-    const int g = d.slots[k];
-    const GameState &s = c.gs[g];
-    if (!s.session || s.phase != PH_HOLD || s.error) {            // uniform over the block
-        if (threadIdx.x == 0) d.sstat[k] = SGO_ERR_STATE;
-        return;
-    }
-    const int blk = s.root_blk;
-    const size_t ph = blk < c.cap ? (size_t)g * c.cap + blk
-                                  : (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
-    for (int i = threadIdx.x; i < c.RW; i += 64) d.src[(size_t)k * c.RW + i] = c.pos[ph * c.RW + i];
-    if (threadIdx.x == 0) d.sstat[k] = SGO_OK;
-}
-
 template <int S>
 __global__ __launch_bounds__(64) void k_rollout_step(Roll d, int n, int cur, const float *policy, int sym_k, uint32_t seed,
                                                       int per_src, int max_plies) {
@@ -120,15 +100,10 @@ __global__ __launch_bounds__(64) void k_rollout_step(Roll d, int n, int cur, con
     for (int j = y; j < G::N; j += 32) sp[half][j] = prow[j];
     __syncthreads();
 
-    rows::Board<S> bd;
-    bd.half = half;
-    bd.y = y;
-    bd.M = (y < S) ? G::ROWMASK : 0u;
-    const bool mover_white = (in[G::META_WORD] & G::META_BIT) != 0;
-    const uint32_t black = rows::load_row<S>(in, y), white = rows::load_row<S>(in + G::NW, y);
-    const uint32_t prev = rows::load_row<S>(in + (mover_white ? 3 : 2) * G::NW, y);
-    uint32_t own = mover_white ? white : black, opp = mover_white ? black : white;
-    const uint32_t lg = bd.legal(own, opp, prev);
+    const rows::Board<S> bd(half, y);
+    rows::Ply p = rows::load_ply<S>(in, false, y);
+    const uint32_t prev = rows::load_row<S>(in + (p.mover_white ? 3 : 2) * G::NW, y);
+    const uint32_t lg = bd.legal(p.own, p.opp, prev);
 
     // weights of this row's points and their sum; an inclusive scan over the rows of the half
     const int32_t *lut = d.lut + (size_t)sym_k * G::A;
@@ -168,22 +143,9 @@ __global__ __launch_bounds__(64) void k_rollout_step(Roll d, int n, int cur, con
     const int a_pick = __shfl(a_loc, from, 32);
     const int a = total != 0 ? a_pick : G::N;                       // no legal board point: a pass
 
-    (void)bd.advance(own, opp, a);                                  // a legal point is never occupied
-    const uint32_t nb = mover_white ? opp : own, nw = mover_white ? own : opp;
-    uint32_t w0 = rows::gather_word<S>(nb, half, y), w1 = rows::gather_word<S>(nw, half, y);
-    if (valid) {
-        if (y < G::NW) {
-            if (y == G::META_WORD && !mover_white) w0 |= G::META_BIT;   // black moved => white to play
-            out[y] = w0;
-            out[G::NW + y] = w1;
-        }
-        // history: planes 0..13 of the record read become planes 2..15 of the record written
-#pragma unroll
-        for (int c0 = 0; c0 < 14 * G::NW; c0 += 32) {
-            const int c = c0 + y;
-            if (c < 14 * G::NW) out[2 * G::NW + c] = in[c];
-        }
-    }
+    (void)bd.advance(p.own, p.opp, a);                              // a legal point is never occupied
+    const uint32_t nb = p.black(), nw = p.white();
+    rows::store_ply<S>(in, out, p, 0u, nullptr, half, y, valid);    // an idle half writes nothing
 
     const int ply1 = ply + 1, passes1 = (a == G::N) ? passes + 1 : 0;
     const bool ended = passes1 >= 2 || ply1 >= max_plies;
@@ -237,18 +199,9 @@ struct sgo_rollout {
 };
 
 namespace {
-struct DeviceGuard {       // the calling thread's current device is left as it was
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 void free_all(sgo_rollout *r) {
     Roll &d = r->d;
-    void *dev[] = {d.rec, d.list[0], d.list[1], d.ply, d.passes, d.bown, d.wown, d.sums, d.count, d.lut, d.src, d.slots, d.sstat};
+    void *dev[] = {d.rec, d.list[0], d.list[1], d.ply, d.passes, d.bown, d.wown, d.sums, d.count, d.lut, d.src, d.slots, d.sroot};
     for (void *p : dev) if (p) (void)hipFree(p);
     if (r->h_stat) (void)hipHostFree(r->h_stat);
     if (r->h_src) (void)hipHostFree(r->h_src);
@@ -269,7 +222,7 @@ int check_start(const sgo_rollout *r, const char *what, int n_src, int per_src) 
 int launch_start(sgo_rollout *r, int n_src, const uint32_t *d_records, const int32_t *d_index, int per_src, uint32_t seed,
                  int max_plies, hipStream_t st) {
     const long words = (long)n_src * per_src * r->RW;
-    const int blocks = cdiv_r(words, 256) < 4096 ? cdiv_r(words, 256) : 4096;
+    const int blocks = cdiv(words, 256) < 4096 ? cdiv(words, 256) : 4096;
     SGO_DISPATCH(r->S, k_rollout_start<kS><<<dim3(blocks), dim3(256), 0, st>>>(r->d, n_src, d_records, d_index, per_src));
     SGO_HIP(hipGetLastError());
     r->n_src = n_src;
@@ -311,16 +264,12 @@ sgo_rollout *sgo_rollout_create(int S, int max_rollouts, int max_sources, int de
               hipMalloc((void **)&d.lut, (size_t)8 * r->A * sizeof(int32_t)) == hipSuccess &&
               hipMalloc((void **)&d.src, ms * r->RW * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc((void **)&d.slots, ms * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc((void **)&d.sstat, ms * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc((void **)&d.sroot, 2 * ms * sizeof(int32_t)) == hipSuccess &&
               hipHostMalloc((void **)&r->h_stat, 4 * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void **)&r->h_src, ms * r->RW * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void **)&r->h_slots, 2 * ms * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
               hipEventCreateWithFlags(&r->ev_src, hipEventDisableTiming) == hipSuccess;
-    if (ok) {
-        std::vector<int32_t> lut((size_t)8 * r->A);
-        for (int k = 0; k < 8; k++) build_sym_lut(S, k, lut.data() + (size_t)k * r->A);
-        ok = hipMemcpy(d.lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    ok = ok && upload_sym_luts(S, d.lut) == hipSuccess;
     if (!ok) {
         set_error("sgo_rollout_create: out of memory (device or pinned host)");
         free_all(r);
@@ -367,18 +316,19 @@ int sgo_rollout_start_sessions(sgo_rollout *r, sgo_ctx *x, int n, const int32_t 
     for (int i = 0; i < n; i++)
         if (slots[i] < 0 || slots[i] >= x->c.G) { set_error("sgo_rollout_start_sessions: slot outside the context"); return SGO_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    if (r->src_busy) { SGO_HIP(hipEventSynchronize(r->ev_src)); r->src_busy = false; }
-    int32_t *h_status = r->h_slots + r->d.max_src;
+    // the root records are read in place: k_session_roots names them, k_rollout_start clones them from the context's blocks
+    const size_t ms = (size_t)r->d.max_src;
+    int32_t *h_status = r->h_slots + ms, *d_status = r->d.sroot, *d_index = r->d.sroot + ms;
     memcpy(r->h_slots, slots, sizeof(int32_t) * (size_t)n);
     SGO_HIP(hipMemcpyAsync(r->d.slots, r->h_slots, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    k_rollout_sources<<<dim3(n), dim3(64), 0, st>>>(x->c, r->d, n);
-    SGO_HIP(hipGetLastError());
-    SGO_HIP(hipMemcpyAsync(h_status, r->d.sstat, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    const int lrc = launch_session_roots(x->c, n, r->d.slots, d_status, d_index, st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h_status, d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     SGO_HIP(hipStreamSynchronize(st));           // the verdict decides whether anything starts
     bool bad = false;
     for (int i = 0; i < n; i++) { status[i] = h_status[i]; bad = bad || h_status[i] != SGO_OK; }
     if (bad) { set_error("sgo_rollout_start_sessions: a listed slot is not a holding session; nothing started"); return SGO_ERR_STATE; }
-    return launch_start(r, n, r->d.src, nullptr, per_src, seed, max_plies, st);
+    return launch_start(r, n, x->c.pos, d_index, per_src, seed, max_plies, st);
 }
 
 int sgo_rollout_list(sgo_rollout *r, const uint32_t **d_records, const int32_t **d_index) {
@@ -394,7 +344,7 @@ int sgo_rollout_step(sgo_rollout *r, const float *d_policy, int sym_k, void *str
     hipStream_t st = (hipStream_t)stream;
     const int n = r->n_live;
     SGO_HIP(hipMemsetAsync(r->d.count, 0, sizeof(int32_t), st));
-    SGO_DISPATCH(r->S, k_rollout_step<kS><<<dim3(cdiv_r(n, 2)), dim3(64), 0, st>>>(r->d, n, r->cur, d_policy, sym_k, r->seed, r->per_src,
+    SGO_DISPATCH(r->S, k_rollout_step<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(r->d, n, r->cur, d_policy, sym_k, r->seed, r->per_src,
                                                                                      r->max_plies));
     SGO_HIP(hipGetLastError());
     SGO_HIP(hipMemcpyAsync(r->h_stat, r->d.count, sizeof(int32_t), hipMemcpyDeviceToHost, st));

@@ -40,6 +40,7 @@ template <int S>
 struct Board {
     int half, y;          // which half of the wave, row index inside the half
     uint32_t M;           // ROWMASK for rows < S, 0 for padding rows
+    SGO_DEV Board(int half_, int y_) : half(half_), y(y_), M((y_ < S) ? Geo<S>::ROWMASK : 0u) {}
 
     SGO_DEV uint32_t nbr4(uint32_t a) const { return (((a << 1) | (a >> 1)) | row_above(a) | row_below(a)) & M; }
 
@@ -155,29 +156,37 @@ SGO_DEV uint32_t gather_word(uint32_t row, int half, int j) {
     return w;
 }
 
-// Full ply of one packed record by one half-wave: new pair + legal set of the new position + history move.
-// in / out must not alias.  Every lane of the half returns the same status (0, -101 occupied, -102 bad move).
+// A ply of one packed record by one half-wave, in two halves around the rules calls of the Board.
+// The mover's row and the opponent's, as loaded and as Board::advance leaves them; colours are absolute in the record.
+struct Ply {
+    bool mover_white;
+    uint32_t own, opp;
+    SGO_DEV uint32_t black() const { return mover_white ? opp : own; }
+    SGO_DEV uint32_t white() const { return mover_white ? own : opp; }
+};
+// The load half: row y of planes 0 / 1 of `in`, the mover picked (swap_first: make_play's out-of-turn colour).
 template <int S>
-SGO_DEV int advance_record_rows(const uint32_t *in, uint32_t *out, int a, bool swap_first, uint32_t *legal_out, int half, int y) {
+SGO_DEV Ply load_ply(const uint32_t *in, bool swap_first, int y) {
     using G = Geo<S>;
-    if (a < 0 || a > G::N) return -102;
-    Board<S> bd;
-    bd.half = half;
-    bd.y = y;
-    bd.M = (y < S) ? G::ROWMASK : 0u;
-    const bool mover_white = ((in[G::META_WORD] & G::META_BIT) != 0) != swap_first;
+    Ply p;
+    p.mover_white = ((in[G::META_WORD] & G::META_BIT) != 0) != swap_first;
     const uint32_t black = load_row<S>(in, y), white = load_row<S>(in + G::NW, y);
-    uint32_t own = mover_white ? white : black, opp = mover_white ? black : white;
-    const uint32_t before_opp = opp;
-    const int st = bd.advance(own, opp, a);
-    if (st) return st;
-    // new side to move = old opponent; its stones one ply ago = the opponent plane as loaded
-    uint32_t lg = 0;
-    if (legal_out) lg = bd.legal(opp, own, before_opp);
-    const uint32_t nb = mover_white ? opp : own, nw = mover_white ? own : opp;
-    uint32_t w0 = gather_word<S>(nb, half, y), w1 = gather_word<S>(nw, half, y), wl = legal_out ? gather_word<S>(lg, half, y) : 0u;
+    p.own = p.mover_white ? white : black;
+    p.opp = p.mover_white ? black : white;
+    return p;
+}
+// The store half: the new pair (and, with legal_out, the legal rows lg) gathered into words, the to-play bit, and the history
+// move.  Every lane of the half takes part in the gathers; write == false (uniform over the half) stores nothing.
+// in / out must not alias.
+template <int S>
+SGO_DEV void store_ply(const uint32_t *in, uint32_t *out, const Ply &p, uint32_t lg, uint32_t *legal_out, int half, int y,
+                       bool write = true) {
+    using G = Geo<S>;
+    uint32_t w0 = gather_word<S>(p.black(), half, y), w1 = gather_word<S>(p.white(), half, y),
+             wl = legal_out ? gather_word<S>(lg, half, y) : 0u;
+    if (!write) return;
     if (y < G::NW) {
-        if (y == G::META_WORD && !mover_white) w0 |= G::META_BIT;   // black moved => white to play
+        if (y == G::META_WORD && !p.mover_white) w0 |= G::META_BIT;   // black moved => white to play
         out[y] = w0;
         out[G::NW + y] = w1;
         if (legal_out) {
@@ -187,6 +196,9 @@ SGO_DEV int advance_record_rows(const uint32_t *in, uint32_t *out, int a, bool s
     }
     // history: planes 0..13 of the parent become planes 2..15 (one contiguous run of 14*NW words)
     if constexpr (G::NW % 4 == 0) {
+        // record arrays are 16-byte aligned (hipMalloc, aligned LDS), and so is every record and its plane 2
+        static_assert((G::RW * sizeof(uint32_t)) % 16 == 0 && (2 * G::NW * sizeof(uint32_t)) % 16 == 0 && (14 * G::NW) % 4 == 0,
+                      "16-byte history move");
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 *s = reinterpret_cast<const u32x4 *>(in);
         u32x4 *d = reinterpret_cast<u32x4 *>(out + 2 * G::NW);
@@ -202,66 +214,25 @@ SGO_DEV int advance_record_rows(const uint32_t *in, uint32_t *out, int a, bool s
             if (c < 14 * G::NW) out[2 * G::NW + c] = in[c];
         }
     }
+}
+
+// Full ply of one packed record by one half-wave: new pair + legal set of the new position + history move.
+// in / out must not alias.  Every lane of the half returns the same status (0, -101 occupied, -102 bad move).
+template <int S>
+SGO_DEV int advance_record_rows(const uint32_t *in, uint32_t *out, int a, bool swap_first, uint32_t *legal_out, int half, int y) {
+    using G = Geo<S>;
+    if (a < 0 || a > G::N) return -102;
+    const Board<S> bd(half, y);
+    Ply p = load_ply<S>(in, swap_first, y);
+    const uint32_t before_opp = p.opp;
+    const int st = bd.advance(p.own, p.opp, a);
+    if (st) return st;
+    // new side to move = old opponent; its stones one ply ago = the opponent plane as loaded
+    uint32_t lg = 0;
+    if (legal_out) lg = bd.legal(p.opp, p.own, before_opp);
+    store_ply<S>(in, out, p, lg, legal_out, half, y);
     return 0;
 }
 
 }  // namespace rows
-
-// What the fused board_advance + nn_input_pack kernel keeps from the ply: word `lane` of the child's planes 0 / 1 (valid in
-// lanes 0..NW-1 of the half) and who is to move in the child.
-template <int S>
-struct Board_rows_result {
-    uint32_t w0, w1;      // word `lane` of the child's planes 0 / 1
-    uint32_t rb, rw;      // row `lane` of the child's black / white stones
-    bool child_white;
-};
-
-// advance_record_rows of a LEGAL move (the engine's leaves: the move comes from the legal set), keeping the new pair in
-// registers.  out / legal_out may be null for an idle half (nothing is written; the wave stays converged).
-template <int S>
-SGO_DEV void rows_advance_keep(const uint32_t *in, uint32_t *out, int a, uint32_t *legal_out, int half, int y,
-                               Board_rows_result<S> &res) {
-    using G = Geo<S>;
-    rows::Board<S> bd;
-    bd.half = half;
-    bd.y = y;
-    bd.M = (y < S) ? G::ROWMASK : 0u;
-    const bool mover_white = (in[G::META_WORD] & G::META_BIT) != 0;
-    const uint32_t black = rows::load_row<S>(in, y), white = rows::load_row<S>(in + G::NW, y);
-    uint32_t own = mover_white ? white : black, opp = mover_white ? black : white;
-    const uint32_t before_opp = opp;
-    (void)bd.advance(own, opp, a);
-    const uint32_t lg = bd.legal(opp, own, before_opp);
-    const uint32_t nb = mover_white ? opp : own, nw = mover_white ? own : opp;
-    uint32_t w0 = rows::gather_word<S>(nb, half, y), w1 = rows::gather_word<S>(nw, half, y), wl = rows::gather_word<S>(lg, half, y);
-    if (y == G::META_WORD && !mover_white) w0 |= G::META_BIT;   // black moved => white to play
-    if (y == (G::N >> 5)) wl |= 1u << (G::N & 31);              // pass is always legal
-    res.w0 = w0;
-    res.w1 = w1;
-    res.rb = nb;
-    res.rw = nw;
-    res.child_white = !mover_white;
-    if (!out) return;
-    if (y < G::NW) {
-        out[y] = w0;
-        out[G::NW + y] = w1;
-        legal_out[y] = wl;
-    }
-    if constexpr (G::NW % 4 == 0) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 *s = reinterpret_cast<const u32x4 *>(in);
-        u32x4 *d = reinterpret_cast<u32x4 *>(out + 2 * G::NW);
-#pragma unroll
-        for (int c0 = 0; c0 < 14 * G::NW / 4; c0 += 32) {
-            const int c = c0 + y;
-            if (c < 14 * G::NW / 4) d[c] = s[c];
-        }
-    } else {
-#pragma unroll
-        for (int c0 = 0; c0 < 14 * G::NW; c0 += 32) {
-            const int c = c0 + y;
-            if (c < 14 * G::NW) out[2 * G::NW + c] = in[c];
-        }
-    }
-}
 }  // namespace sgo

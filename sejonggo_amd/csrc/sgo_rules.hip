@@ -21,8 +21,6 @@
 
 namespace sgo {
 
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
 // ------------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
@@ -77,6 +75,13 @@ void build_sym_lut(int S, int k, int32_t *lut) {
             }
             lut[x + S * y] = (int32_t)lrint((nx + c) + S * (ny + c));
         }
+}
+
+hipError_t upload_sym_luts(int S, int32_t *d_lut) {
+    const size_t A = (size_t)S * S + 1;
+    std::vector<int32_t> lut(8 * A);
+    for (int k = 0; k < 8; k++) build_sym_lut(S, k, lut.data() + k * A);
+    return hipMemcpy(d_lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice);
 }
 
 // ------------------------------------------------------------------------------------ kernels

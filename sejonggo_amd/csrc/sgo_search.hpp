@@ -67,10 +67,7 @@ struct Eng {
     __device__ __forceinline__ Eng(const Ctx &cc, int gg) : c(cc), g(gg), lane(threadIdx.x & 63), gb0((size_t)gg * cc.cap) {}
 
     // physical block behind local id `blk` (uniform over the wave): private region, or one dependent load for an overflow id
-    __device__ __forceinline__ size_t ph(int blk) const {
-        if (blk < c.cap) return gb0 + blk;
-        return (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
-    }
+    __device__ __forceinline__ size_t ph(int blk) const { return phys_block(c, g, gb0, blk); }
     __device__ __forceinline__ size_t slot_base(int blk) const { return ph(blk) * (size_t)G::APAD; }
     __device__ __forceinline__ bool legal_bit(int blk, int i) const {
         return (c.legal[ph(blk) * G::NW + (i >> 5)] >> (i & 31)) & 1u;

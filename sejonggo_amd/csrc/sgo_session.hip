@@ -1,8 +1,10 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
-// sgo_keys.hip) and of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip).  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the kernels are in
-// sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the SejongGoEngine a GTP
-// front-end drives.
+// sgo_keys.hip) and of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip).  Those two and sgo_rollout_start_sessions
+// (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
+// kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
+// kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
+// SejongGoEngine a GTP front-end drives.
 #include <string.h>
 #include <vector>
 
@@ -12,12 +14,18 @@
 using namespace sgo;
 
 namespace sgo {
-// csrc/sgo_keys.hip: k_session_keys on device pointers
-int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, uint64_t *d_key0, uint64_t *d_canon,
-                        int32_t *d_mask, hipStream_t st);
+// csrc/sgo_keys.hip: k_session_roots and k_keys on device pointers
+int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint64_t *d_key0,
+                        uint64_t *d_canon, int32_t *d_mask, hipStream_t st);
 // csrc/sgo_tactics.hip: k_session_roots, k_tactics_chains and k_tactics_read on device pointers
 int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
                            int32_t *d_n_chains, int32_t *d_chains, hipStream_t st);
+
+int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
+    k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
+    SGO_HIP(hipGetLastError());
+    return SGO_OK;
+}
 }
 
 // Stage n slots (+ optional actions / colours) in the context's staging area, as sgo_start_games does: wait until the previous
@@ -73,6 +81,21 @@ static int session_buffer(sgo_ctx *x, size_t bytes) {
     SGO_HIP(hipHostMalloc((void **)&h.sess_h, cap, hipHostMallocDefault));
     SGO_HIP(hipMalloc((void **)&h.sess_d, cap));
     h.sess_cap = cap;
+    return SGO_OK;
+}
+
+// The shared opening of sgo_session_report, _keys and _tactics (readers: a slot may be listed twice): the list is checked against
+// the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
+static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t *slots, size_t bytes, hipStream_t st) {
+    const Ctx &c = x->c;
+    if (n > c.G) { set_error(std::string(who) + ": more slots than the context has"); return SGO_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= c.G) { set_error(std::string(who) + ": slot out of range"); return SGO_ERR_ARG; }
+    SGO_HIP(hipSetDevice(c.cfg.device_id));
+    const int rc = session_buffer(x, bytes);
+    if (rc != SGO_OK) return rc;
+    memcpy(x->h.sess_h, slots, sizeof(int32_t) * n);
+    SGO_HIP(hipMemcpyAsync(x->h.sess_d, x->h.sess_h, al8(sizeof(int32_t) * (size_t)n), hipMemcpyHostToDevice, st));
     return SGO_OK;
 }
 
@@ -181,16 +204,10 @@ int sgo_session_report(sgo_ctx *x, int n, const int32_t *slots, int K, int D, in
     if (n == 0) return SGO_OK;
     Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    if (n > c.G) { set_error("sgo_session_report: more slots than the context has"); return SGO_ERR_ARG; }
-    for (int i = 0; i < n; i++)
-        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_report: slot out of range"); return SGO_ERR_ARG; }
-    SGO_HIP(hipSetDevice(c.cfg.device_id));
     const size_t rw = report_words(c.A, K, D), head = al8(sizeof(int32_t) * (size_t)n), body = sizeof(int32_t) * rw * n;
-    const int rc = session_buffer(x, head + body);
+    const int rc = stage_session_list(x, "sgo_session_report", n, slots, head + body, st);
     if (rc != SGO_OK) return rc;
     uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    memcpy(h, slots, sizeof(int32_t) * n);
-    SGO_HIP(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, st));
     SGO_DISPATCH(c.S, k_session_report<kS><<<dim3(n), dim3(64), 0, st>>>(c, n, reinterpret_cast<const int32_t *>(d),
                                                                             reinterpret_cast<int32_t *>(d + head), K, D));
     SGO_HIP(hipGetLastError());
@@ -222,25 +239,19 @@ int sgo_session_keys(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, u
     if (n == 0) return SGO_OK;
     Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    if (n > c.G) { set_error("sgo_session_keys: more slots than the context has"); return SGO_ERR_ARG; }
-    for (int i = 0; i < n; i++)
-        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_keys: slot out of range"); return SGO_ERR_ARG; }
-    SGO_HIP(hipSetDevice(c.cfg.device_id));
-    // slots | status | mask | key0 | canon; everything behind the slots comes back in one copy
+    // slots | record index | status | mask | key0 | canon; everything behind the index comes back in one copy
     const size_t ib = al8(sizeof(int32_t) * (size_t)n), kb = sizeof(uint64_t) * (size_t)n;
-    const int rc = session_buffer(x, 3 * ib + 2 * kb);
+    const int rc = stage_session_list(x, "sgo_session_keys", n, slots, 4 * ib + 2 * kb, st);
     if (rc != SGO_OK) return rc;
     uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    memcpy(h, slots, sizeof(int32_t) * n);
-    SGO_HIP(hipMemcpyAsync(d, h, ib, hipMemcpyHostToDevice, st));
-    const int lrc = launch_session_keys(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + ib),
-                                        reinterpret_cast<uint64_t *>(d + 3 * ib), reinterpret_cast<uint64_t *>(d + 3 * ib + kb),
-                                        reinterpret_cast<int32_t *>(d + 2 * ib), st);
+    const int lrc = launch_session_keys(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + 2 * ib),
+                                        reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<uint64_t *>(d + 4 * ib),
+                                        reinterpret_cast<uint64_t *>(d + 4 * ib + kb), reinterpret_cast<int32_t *>(d + 3 * ib), st);
     if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + ib, d + ib, 2 * ib + 2 * kb, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, 2 * ib + 2 * kb, hipMemcpyDeviceToHost, st));
     SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + ib), *hm = reinterpret_cast<const int32_t *>(h + 2 * ib);
-    const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + 3 * ib), *hc = hk + n;
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hm = reinterpret_cast<const int32_t *>(h + 3 * ib);
+    const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + 4 * ib), *hc = hk + n;
     for (int i = 0; i < n; i++) {
         status[i] = hs[i];
         if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
@@ -260,18 +271,12 @@ int sgo_session_tactics(sgo_ctx *x, int n, const int32_t *slots, int max_chains,
     if (n == 0) return SGO_OK;
     Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    if (n > c.G) { set_error("sgo_session_tactics: more slots than the context has"); return SGO_ERR_ARG; }
-    for (int i = 0; i < n; i++)
-        if (slots[i] < 0 || slots[i] >= c.G) { set_error("sgo_session_tactics: slot out of range"); return SGO_ERR_ARG; }
-    SGO_HIP(hipSetDevice(c.cfg.device_id));
     // slots | record index | status | n_chains | chains | libs; everything behind the index comes back in one copy
     const int N = c.S * c.S;
     const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)max_chains * n, lb = al8((size_t)n * N);
-    const int rc = session_buffer(x, 4 * ib + cb + lb);
+    const int rc = stage_session_list(x, "sgo_session_tactics", n, slots, 4 * ib + cb + lb, st);
     if (rc != SGO_OK) return rc;
     uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    memcpy(h, slots, sizeof(int32_t) * n);
-    SGO_HIP(hipMemcpyAsync(d, h, ib, hipMemcpyHostToDevice, st));
     const int lrc = launch_session_tactics(c, n, reinterpret_cast<const int32_t *>(d), max_chains, reinterpret_cast<int32_t *>(d + 2 * ib),
                                            reinterpret_cast<int32_t *>(d + ib), d + 4 * ib + cb, reinterpret_cast<int32_t *>(d + 3 * ib),
                                            reinterpret_cast<int32_t *>(d + 4 * ib), st);

@@ -37,17 +37,15 @@ __global__ __launch_bounds__(64) void k_session_play(Ctx c, int n, StageLayout L
     GameState &st = s.st;
     const int lane = s.lane;
     // every test below is uniform over the wave
-    int rc = SGO_OK;
-    if (!st.session || st.phase != PH_HOLD || st.error) rc = SGO_ERR_STATE;
-    else if (a < 0 || a >= G::A) rc = SGO_ERR_RANGE;
-    const uint32_t *rpos = c.pos + s.e.ph(rc ? 0 : st.root_blk) * G::RW;
-    if (!rc && a < G::N && (((rpos[a >> 5] | rpos[G::NW + (a >> 5)]) >> (a & 31)) & 1u)) rc = SGO_ERR_OCCUPIED;
+    const bool holds = holding(st);
+    const uint32_t *rpos = c.pos + s.e.ph(holds ? st.root_blk : 0) * G::RW;
+    const int rc = holds ? external_move_status<S>(rpos, a) : SGO_ERR_STATE;
     if (rc) {
         if (lane == 0) status[k] = rc;
         return;
     }
-    const int to_play = white_to_play<S>(rpos) ? -1 : 1;
-    const bool in_turn = col == 0 || col == to_play;
+    int to_play;
+    const bool in_turn = moves_in_turn<S>(rpos, col, to_play);
     const size_t sb = s.e.slot_base(st.root_blk);
     int nr = -1;
     if (in_turn && c.bSlot[s.e.ph(st.root_blk)] != -2 && s.e.legal_bit(st.root_blk, a)) nr = s.chosen_child(sb, a);
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(1024) void k_session_arm(Ctx c, int n, StageLayout 
     int32_t *status = reinterpret_cast<int32_t *>(c.stage + L.first);
     int bad = 0;
     for (int i = threadIdx.x; i < n; i += 1024) {
-        const GameState &s = c.gs[slots[i]];
-        if (!s.session || s.phase != PH_HOLD || s.error) bad = 1;
+        if (!holding(c.gs[slots[i]])) bad = 1;
     }
     bad = __syncthreads_or(bad);
     if (!bad) {
@@ -112,6 +109,19 @@ __global__ __launch_bounds__(1024) void k_session_arm(Ctx c, int n, StageLayout 
         }
     }
     if (threadIdx.x == 0) status[0] = bad ? SGO_ERR_STATE : SGO_OK;
+}
+
+// One thread per listed slot: the record index (physical block of c.pos) of the root position of a holding session, what
+// sgo_game_board shows; anything else gets SGO_ERR_STATE and index -1.  The context is only read.  sgo_session_keys,
+// sgo_session_tactics and sgo_rollout_start_sessions run their ordinary record kernels over c.pos with this index.
+__global__ __launch_bounds__(64) void k_session_roots(Ctx c, int n, const int32_t *slots, int32_t *status, int32_t *index) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int g = slots[i];
+    const GameState &s = c.gs[g];
+    const int idx = holding(s) ? (int)phys_block(c, g, s.root_blk) : -1;
+    status[i] = idx >= 0 ? SGO_OK : SGO_ERR_STATE;
+    index[i] = idx;
 }
 
 // ---------------------------------------------------------------------------------------- sgo_session_setup
@@ -150,30 +160,22 @@ __global__ __launch_bounds__(64) void k_session_setup(Ctx c, int n, uint8_t *buf
     const int32_t *colors = reinterpret_cast<const int32_t *>(buf + L.colors) + off;
     int32_t *status = reinterpret_cast<int32_t *>(buf + L.status), *fail_at = reinterpret_cast<int32_t *>(buf + L.fail_at);
     const GameState &old = c.gs[g];
-    if (!old.session || old.phase != PH_HOLD || old.error) {      // uniform over the wave
+    if (!holding(old)) {                                          // uniform over the wave
         if (lane == 0) { status[k] = SGO_ERR_STATE; fail_at[k] = -1; }
         return;
     }
     // the empty board and its legal set, as k_start writes them
     for (int i = lane; i < G::RW; i += 64) rec[i] = 0;
-    for (int i = lane; i < G::NW; i += 64) {
-        uint32_t w = 0xffffffffu;
-        if (i == G::NW - 1) {
-            const int bits = G::A - 32 * (G::NW - 1);
-            w = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
-        }
-        lg[i] = w;
-    }
+    for (int i = lane; i < G::NW; i += 64) lg[i] = empty_legal_word<S>(i);
     __syncthreads();
     if (lane == 0) {
         int rc = SGO_OK, j = 0, player = 1;
         for (; j < nm; j++) {
             const int a = actions[j], col = colors[j];
-            if (a < 0 || a >= G::A) rc = SGO_ERR_RANGE;
-            else if (a < G::N && (((rec[a >> 5] | rec[G::NW + (a >> 5)]) >> (a & 31)) & 1u)) rc = SGO_ERR_OCCUPIED;
+            rc = external_move_status<S>(rec, a);
             if (rc) break;
-            const int to_play = white_to_play<S>(rec) ? -1 : 1;
-            const bool in_turn = col == 0 || col == to_play;
+            int to_play;
+            const bool in_turn = moves_in_turn<S>(rec, col, to_play);
             rc = advance_record<S>(rec, rec, a, !in_turn, lg);    // in == out: the in-place form, as k_session_play
             if (rc) break;
             player = in_turn ? to_play : -to_play;
@@ -261,7 +263,7 @@ __global__ __launch_bounds__(64) void k_session_report(Ctx c, int n, const int32
     const int g = slots[k];
     int32_t *o = out + (size_t)k * report_words(G::A, K, D);
     const GameState &s = c.gs[g];
-    if (!s.session || s.phase != PH_HOLD || s.error) {            // uniform over the wave
+    if (!holding(s)) {                                            // uniform over the wave
         if (lane == 0) o[0] = SGO_ERR_STATE;
         return;
     }

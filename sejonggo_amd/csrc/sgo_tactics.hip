@@ -5,7 +5,9 @@
 //
 //   k_tactics_chains<S>   per listed record: libs, n_chains, words 0..3 of the chain rows (words 4..7 preset to 0, -1, -1, 0)
 //   k_tactics_read<S>     per (row, chain slot): queries A and D of the header's reader; words 4..7 of the chain row
-//   k_session_roots<S>    the record index of the root position of every listed holding session slot (sgo_session_tactics)
+//
+// sgo_session_tactics runs the same two kernels over the context's records, with the root index k_session_roots
+// (sgo_session.hpp) writes.
 //
 // Kernel form: one 32-lane HALF of a wavefront per item, one board row per lane (sgo_rows.hpp), one wavefront per workgroup.
 // The rules are rows::Board<S>::advance / legal / flood: nothing is restated.  The floods vote over the whole wave, so both
@@ -17,8 +19,6 @@
 #include "sgo_rows.hpp"
 
 namespace sgo {
-
-static inline int cdiv_t(long a, long b) { return (int)((a + b - 1) / b); }
 
 // sum of a per-lane count over the 32 lanes of the half, delivered to every lane of it
 SGO_DEV int half_sum(int v) {
@@ -45,10 +45,7 @@ __global__ __launch_bounds__(64) void k_tactics_chains(int n, const uint32_t *re
     const int r = valid ? (index ? index[i] : (int)i) : -1;
     const bool ok = r >= 0 && r < n_records;                         // uniform over the half
     const uint32_t *rec = ok ? records + (size_t)r * G::RW : nullptr;
-    rows::Board<S> bd;
-    bd.half = half;
-    bd.y = y;
-    bd.M = (y < S) ? G::ROWMASK : 0u;
+    const rows::Board<S> bd(half, y);
     uint32_t rb = rec ? rows::load_row<S>(rec, y) : 0u, rw = rec ? rows::load_row<S>(rec + G::NW, y) : 0u;
     const uint32_t emp = ~(rb | rw) & bd.M;
     uint32_t lb[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};               // bit k of the liberty count of the chain on each point of the row
@@ -111,10 +108,7 @@ __global__ __launch_bounds__(64) void k_tactics_read(int n, const uint32_t *reco
     __shared__ int32_t Cs[2][T_FRAMES];
     const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
     const int j = blockIdx.x * 2 + half;                             // chain slot
-    rows::Board<S> bd;
-    bd.half = half;
-    bd.y = y;
-    bd.M = (y < S) ? G::ROWMASK : 0u;
+    const rows::Board<S> bd(half, y);
     for (int i = blockIdx.y; i < n; i += gridDim.y) {                // the trip count is the workgroup's
         const int r = index ? index[i] : i;
         const bool ok = r >= 0 && r < n_records;
@@ -257,35 +251,17 @@ __global__ __launch_bounds__(64) void k_tactics_read(int n, const uint32_t *reco
     }
 }
 
-// One thread per listed slot: the record (physical block) that holds the root position of a holding session, as k_session_keys
-// finds it; anything else gets SGO_ERR_STATE and index -1.  The context is only read.
-template <int S>
-__global__ __launch_bounds__(64) void k_session_roots(Ctx c, int n, const int32_t *slots, int32_t *status, int32_t *index) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const int g = slots[i];
-    const GameState &s = c.gs[g];
-    int idx = -1;
-    if (s.session && s.phase == PH_HOLD && !s.error) {
-        const int blk = s.root_blk;
-        const size_t ph = blk < c.cap ? (size_t)g * c.cap + blk : (size_t)c.G * c.cap + (size_t)c.ovfMap[(size_t)g * c.ovf_cap + (blk - c.cap)];
-        idx = (int)ph;
-    }
-    status[i] = idx >= 0 ? SGO_OK : SGO_ERR_STATE;
-    index[i] = idx;
-}
-
 static int g_tactics_stage = 0;   // 0: both kernels, 1: k_tactics_chains only, 2: k_tactics_read only (timing)
 
 static int launch_tactics(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int max_chains, uint8_t *d_libs,
                           int32_t *d_n_chains, int32_t *d_chains, hipStream_t st) {
     if (g_tactics_stage != 2) {
-        SGO_DISPATCH(S, k_tactics_chains<kS><<<dim3(cdiv_t(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, max_chains, d_libs,
+        SGO_DISPATCH(S, k_tactics_chains<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, max_chains, d_libs,
                                                                                       d_n_chains, d_chains));
         SGO_HIP(hipGetLastError());
     }
     if (g_tactics_stage != 1) {
-        SGO_DISPATCH(S, k_tactics_read<kS><<<dim3(cdiv_t(max_chains, 2), n < 65535 ? n : 65535), dim3(64), 0, st>>>(
+        SGO_DISPATCH(S, k_tactics_read<kS><<<dim3(cdiv(max_chains, 2), n < 65535 ? n : 65535), dim3(64), 0, st>>>(
                             n, d_records, n_records, d_index, max_chains, d_n_chains, d_chains));
         SGO_HIP(hipGetLastError());
     }
@@ -295,10 +271,9 @@ static int launch_tactics(int S, int n, const uint32_t *d_records, int n_records
 // sgo_session_tactics' launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
 int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
                            int32_t *d_n_chains, int32_t *d_chains, hipStream_t st) {
-    SGO_DISPATCH(c.S, k_session_roots<kS><<<dim3(cdiv_t(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index));
-    SGO_HIP(hipGetLastError());
-    const long blocks = (long)c.G * c.cap + c.pool_blocks;
-    return launch_tactics(c.S, n, c.pos, blocks < 0x7fffffffl ? (int)blocks : 0x7fffffff, d_index, max_chains, d_libs, d_n_chains, d_chains, st);
+    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
+    if (rc != SGO_OK) return rc;
+    return launch_tactics(c.S, n, c.pos, ctx_records(c), d_index, max_chains, d_libs, d_n_chains, d_chains, st);
 }
 
 }  // namespace sgo

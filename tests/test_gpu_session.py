@@ -290,6 +290,72 @@ def test_19x19_follow(env):
         p.close()
 
 
+# ---------------------------------------------------------------------------------------------- a root on a shared block
+ROOT_MAX_MOVES = 6
+
+
+def test_root_on_a_shared_block_keys_tactics_rollout_sources(env):
+    """The overflow arm of the root look-up behind sgo_session_keys, sgo_session_tactics and sgo_rollout_start_sessions: 5x5, two
+    sessions, the smallest private region a context takes (energy + 2 = 6 blocks) beside a shared pool.  Slot 0 plays genmoves
+    until its root has an overflow id (root_blk >= 6: after the SECOND genmove with this net and 16 simulations, on id 9; at most
+    ROOT_MAX_MOVES are allowed and the test fails if none gets there), slot 1 keeps its root on block 0 as the control.  Listed in
+    one call each, both slots give what sgo_keys and sgo_tactics give for the board sgo_game_board shows, and the rollout's
+    source records -- read through the pointer sgo_rollout_list hands out -- are that board."""
+    from sejonggo_amd import _lib as L
+    from sejonggo_amd.engine import SessionEngine, unpack_positions
+    from sejonggo_amd.rollout import RolloutEngine
+    from sejonggo_amd.stub_nets import make_stub
+    from tests import rollout_model as M
+    S, E, sims, mc = 5, 4, 16, 16
+    net = make_stub("hash", S)
+    eng = SessionEngine(net, size=S, n_games=2, sims=sims, energy=E, komi=5.5, symmetry="identity", blocks_per_game=E + 2,
+                        shared_blocks=400)
+    rol = RolloutEngine(net, size=S, max_rollouts=4, max_sources=2)
+    try:
+        lib = L.require_gpu()
+        cap = eng.pool_info()["private_per_game"]
+        assert cap == E + 2 and eng.pool_info()["shared_blocks"] == 400
+        eng.open([0, 1])
+        assert not eng.play([1], [7]).any()                # a fresh tree: the root is block 0
+        moves = 0
+        while eng.block_state(0, blocks=False)["root_blk"] < cap and moves < ROOT_MAX_MOVES:
+            (a, _, _), = eng.genmove([0])
+            assert 0 <= a <= S * S
+            moves += 1
+        roots = [eng.block_state(s, blocks=False)["root_blk"] for s in (0, 1)]
+        print("ROOT_ON_SHARED_BLOCK moves=%d root_blk=%s private=%d" % (moves, roots, cap))
+        assert roots[0] >= cap and roots[1] == 0, (moves, roots)
+        _audit(eng)
+        slots = np.array([0, 1], np.int32)
+        boards = np.concatenate([eng.board(s) for s in slots])
+        assert boards[0, :, :, :2].any() and boards[1, :, :, :2].any()
+        rows = np.ascontiguousarray(M.pack_boards(boards), dtype=np.uint32)
+        # keys
+        k0, cn, mk = np.zeros(2, np.uint64), np.zeros(2, np.uint64), np.zeros(2, np.int32)
+        assert lib.sgo_keys(S, 2, L.ptr(rows), None, L.ptr(k0), L.ptr(cn), L.ptr(mk), None) == 0
+        got = eng.keys(slots)
+        assert not got["status"].any() and k0[0] != k0[1]
+        assert np.array_equal(got["key0"], k0) and np.array_equal(got["canon"], cn) and np.array_equal(got["mask"], mk)
+        # tactics
+        libs, nc, chains = np.zeros((2, S * S), np.uint8), np.zeros(2, np.int32), np.zeros((2, mc, 8), np.int32)
+        assert lib.sgo_tactics(S, 2, L.ptr(rows), mc, L.ptr(libs), L.ptr(nc), L.ptr(chains)) == 0
+        t = eng.tactics(slots, max_chains=mc)
+        assert not t.status.any() and libs[0].any() and libs[1].any()
+        assert np.array_equal(t.libs, libs) and np.array_equal(t.n_chains, nc) and np.array_equal(t.chains, chains)
+        # rollout sources: sgo_rollout_start_sessions, then the records behind sgo_rollout_list
+        assert rol.start_sessions(eng, slots, per_src=2, seed=3, max_plies=8) == 2
+        assert list(rol.session_status) == [0, 0]
+        src = rol.source_records(2, 2)
+        assert np.array_equal(unpack_positions(src, S), boards)
+        NW = lib.sgo_plane_words(S)
+        assert np.array_equal(src[:, :2 * NW], rows[:, :2 * NW])         # stones and the to-play bit, word for word
+        assert all(np.array_equal(eng.board(s), boards[i:i + 1]) for i, s in enumerate(slots))
+        assert [eng.block_state(s, blocks=False)["root_blk"] for s in (0, 1)] == roots
+    finally:
+        rol.close()
+        eng.close()
+
+
 # ---------------------------------------------------------------------------------------------- a mixed context
 def _mixed_games(eng, noises, uni):
     eng.start_games([0, 1], noises=noises, uniforms=uni)
