@@ -50,7 +50,8 @@ extern "C" {
  *   sgo_conv_backend removed.   3: the "half-populations" and "packed stem" sections.   4: sgo_heads_* and sgo_net_* (the heads
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
  *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
- *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics). */
+ *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics), the "unconditional life" section
+ *   (sgo_life*, sgo_session_life). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -633,6 +634,50 @@ int sgo_session_tactics(sgo_ctx *ctx, int n, const int32_t *slots, int max_chain
  * out), 2 = k_tactics_read only, on the table an earlier call left in the same buffers (for timing the kernels apart).  Returns
  * the previous stage; other values only query. */
 int sgo_tactics_stage(int stage);
+
+/* ---- unconditional life: which stones can never be captured, and which points are therefore settled? ------------------------------ */
+/* Per packed record: the stones of either colour that no sequence of opponent moves captures even when their owner always passes
+ * (Benson's pass-alive chains), and the points those chains enclose (csrc/sgo_life.hip).  Everything is integer; there are no
+ * search caps and no "unknown".
+ * Inputs of a record, N = S * S: black / white = the bits a < N of planes 0 / 1.  The to-play flag (the top bit of the last word
+ * of plane 0) is NOT a stone and influences no output: the answer is the same for either side to move.  Padding bits and planes
+ * 2..15 are never read.
+ * For a colour X, the other colour called O:
+ *   A CHAIN of X is a maximal 4-connected set of X stones.
+ *   A REGION of X is a maximal 4-connected set of points that are NOT X: empty points and O stones together.
+ *   Region R is VITAL to chain C iff R holds at least one empty point and EVERY empty point of R is 4-adjacent to a stone of C.
+ *     O stones inside R do not matter.  A region without an empty point is vital to no chain (that occurs only in an illegal
+ *     record).
+ *   Let CC = all chains of X and RR = all regions of X.  Repeat until nothing is removed: remove from CC every chain that has
+ *     fewer than two vital regions in RR; remove from RR every region that is 4-adjacent to a stone of a chain removed so far.
+ *     The fixed point does not depend on the order of the removals; how many passes an implementation takes is not part of the
+ *     interface.
+ *   alive_X = the stones of the chains left in CC.
+ *   terr_X  = the points (empty or O stones) of the regions left in RR that are vital to at least one chain left in CC.  A region
+ *     that survives in RR without being vital to anyone is not territory: the open board next to a living wall is such a region.
+ *   safe_X  = alive_X | terr_X.
+ * The two colours are computed independently.  Illegal records (a chain without a liberty) go through the same definitions
+ * without special cases.
+ * OUTPUTS per listed row:
+ *   sets   uint32 [4][sgo_plane_words(S)] = alive_black, alive_white, terr_black, terr_white; bit order as the legal bitsets of
+ *          sgo_legal_dev; all bits a >= N are zero.
+ *   counts int32 [8] = |alive_black|, |alive_white|, |terr_black|, |terr_white|, dead_white (white stones in terr_black),
+ *          dead_black (black stones in terr_white), unsettled = N - |safe_black | safe_white|, margin = |safe_black| - |safe_white|.
+ *
+ * sgo_life_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_sets uint32 [n][4][sgo_plane_words(S)], d_counts int32 [n][8].  A row whose record index is outside [0, n_records) gets
+ * all-zero sets and counts.  ONE launch on `stream` (one wavefront per row: a half per colour), no allocation, no synchronisation,
+ * capturable; n == 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, a NULL
+ * d_records or output. */
+int sgo_life_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
+                 void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests. */
+int sgo_life(int S, int n, const uint32_t *records, uint32_t *sets, int32_t *counts);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], sets [n][4][sgo_plane_words(S)], counts [n][8].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is
+ * not a holding session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be listed
+ * repeatedly. */
+int sgo_session_life(sgo_ctx *ctx, int n, const int32_t *slots, int32_t *status, uint32_t *sets, int32_t *counts, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

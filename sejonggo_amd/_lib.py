@@ -38,6 +38,7 @@ SYMBOLS = [
     "sgo_records_create", "sgo_records_destroy", "sgo_records_replay", "sgo_records_list", "sgo_records_score_dev",
     "sgo_keys_dev", "sgo_keys", "sgo_session_keys", "sgo_keys_mode",
     "sgo_tactics_dev", "sgo_tactics", "sgo_session_tactics", "sgo_tactics_stage",
+    "sgo_life_dev", "sgo_life", "sgo_session_life",
 ]
 
 
@@ -187,6 +188,9 @@ def load():
     lib.sgo_tactics.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
     lib.sgo_tactics_stage.argtypes = [C.c_int]
     lib.sgo_session_tactics.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_life_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_life.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_session_life.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
     _lib = lib
     return lib
 

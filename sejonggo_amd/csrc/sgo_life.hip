@@ -1,0 +1,166 @@
+// sgo_life.hip -- unconditional life on the device (include/sgo.h "unconditional life"): per packed record the stones of either
+// colour that no sequence of opponent moves can capture (Benson's pass-alive chains) and the points those chains enclose.  A
+// translation unit of its own, like sgo_tactics.hip: tests/test_engine_isa.py pins the kernel set of sgo_engine.hip.
+//
+//   k_life<S>   per listed record: the four sets (alive_black, alive_white, terr_black, terr_white) and the eight counts
+//
+// sgo_session_life runs the same kernel over the context's records, with the root index k_session_roots (sgo_session.hpp) writes.
+//
+// Kernel form: one 32-lane HALF of a wavefront per (row, colour) -- half 0 reads the record for black, half 1 for white -- one board
+// row per lane (sgo_rows.hpp), one wavefront per workgroup.  Chains and regions are rows::Board<S>::flood / nbr4: nothing is
+// restated.  The floods vote over the whole wave, so both halves run every loop in lockstep: a half that has reached its fixed
+// point, or whose row is out of range, goes on with an EMPTY board (its floods end at once) and only its stores differ.  No flood
+// or shuffle sits under a per-half branch.  Everything lives in registers: no LDS, no scratch.
+#include <string.h>
+
+#include "sgo_engine_state.hpp"
+#include "sgo_half.hpp"
+#include "sgo_rows.hpp"
+
+namespace sgo {
+
+// X = the half's colour, O = the other.  Three row-bitboards carry the header's iteration: `live` (the stones of the chains
+// still in C), `reg` (the points of the regions still in R), and per round v1 / v2 (the stones of the chains with >= 1 / >= 2
+// vital regions found so far).  A region that is still in R touches live chains only (a region next to a removed chain was
+// removed with it), so the chains a region can be vital to are the at most four live chains on the neighbours of ONE of its
+// empty points -- the lowest -- since a vital region has every empty point next to the chain.
+// TRIPS: a round that is not the last removes at least one chain, so a half takes at most chains + 1 rounds; a round takes one
+// trip per region still in R (at most N: every trip clears at least the seed from `rest`), and a trip one flood for the region
+// and at most four for the chains (every trip of the inner loop clears at least one of the four neighbours from `cand`): at
+// most 5 floods per region, (chains + 1) * N * 5 floods per launch and half, plus one per round for the removal.  Termination
+// does not depend on the data beyond that.
+template <int S>
+__global__ __launch_bounds__(64) void k_life(int n, const uint32_t *records, int n_records, const int32_t *index, uint32_t *sets,
+                                             int32_t *counts) {
+    using G = Geo<S>;
+    const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
+    const long i = blockIdx.x;                                       // the row: both halves of the wave
+    if (i >= n) return;                                              // the whole workgroup
+    const int r = index ? index[i] : (int)i;
+    const bool ok = r >= 0 && r < n_records;                         // uniform over the wave
+    const uint32_t *rec = ok ? records + (size_t)r * G::RW : nullptr;
+    const rows::Board<S> bd(half, y);
+    const uint32_t rb = rec ? rows::load_row<S>(rec, y) : 0u, rw = rec ? rows::load_row<S>(rec + G::NW, y) : 0u;
+    const uint32_t own = half ? rw : rb, opp = half ? rb : rw;
+    const uint32_t emp = ~(rb | rw) & bd.M;
+    uint32_t live = own, reg = ok ? (~own & bd.M) : 0u;
+    uint32_t alive = 0u, terr = 0u;
+    bool done = !ok;
+    do {
+        uint32_t v1 = 0u, v2 = 0u, t = 0u, rest = reg;
+        while (__any(rest != 0)) {                                   // the regions still in R, by lowest point
+            const int lo = lowest_point<S>(rest, half);
+            const uint32_t seed = (lo >= 0 && y == lo / S) ? (1u << (lo % S)) : 0u;
+            const uint32_t R = bd.flood(seed, rest);
+            rest &= ~R;
+            const uint32_t E = R & emp;
+            const int e0 = lowest_point<S>(E, half);
+            const uint32_t eb = (e0 >= 0 && y == e0 / S) ? (1u << (e0 % S)) : 0u;
+            uint32_t cand = bd.nbr4(eb) & live;                      // at most four stones
+            bool vital = false;
+            while (__any(cand != 0)) {                               // the distinct live chains on them
+                const int c0 = lowest_point<S>(cand, half);
+                const uint32_t cb = (c0 >= 0 && y == c0 / S) ? (1u << (c0 % S)) : 0u;
+                const uint32_t C = bd.flood(cb, live);
+                const bool is_vital = c0 >= 0 && !rows::half_any(E & ~bd.nbr4(C), half);
+                if (is_vital) {
+                    v2 |= C & v1;
+                    v1 |= C;
+                    vital = true;
+                }
+                cand &= ~C;
+            }
+            if (vital) t |= R;
+        }
+        const uint32_t removed = live & ~v2;
+        const bool fixed = !rows::half_any(removed, half);           // the same in every lane of the half
+        const uint32_t gone = bd.flood(bd.nbr4(removed) & reg, reg); // the regions next to a removed chain
+        if (!done && fixed) {
+            alive = live;
+            terr = t;
+            done = true;
+        }
+        live = done ? 0u : v2;
+        reg = done ? 0u : (reg & ~gone);
+    } while (__any(!done));
+
+    // every lane takes part in the gathers and the sums; only the stores are conditional
+    const uint32_t safe = alive | terr;
+    const uint32_t wa = rows::gather_word<S>(alive, half, y), wt = rows::gather_word<S>(terr, half, y);
+    const int n_alive = half_sum(__popc(alive)), n_terr = half_sum(__popc(terr)), n_dead = half_sum(__popc(terr & opp));
+    const int n_safe = half_sum(__popc(safe));
+    const uint32_t other = (uint32_t)__shfl((int)safe, (int)(threadIdx.x ^ 32), 64);     // the cross-half exchange
+    const int n_other = __shfl(n_safe, (int)(threadIdx.x ^ 32), 64);
+    const int n_union = half_sum(__popc(safe | other));
+    uint32_t *so = sets + (size_t)i * 4 * G::NW;
+    if (y < G::NW) {
+        so[(size_t)half * G::NW + y] = wa;                           // alive_black | alive_white
+        so[(size_t)(2 + half) * G::NW + y] = wt;                     // terr_black | terr_white
+    }
+    if (y == 0) {
+        int32_t *co = counts + (size_t)i * 8;
+        co[half] = n_alive;
+        co[2 + half] = n_terr;
+        co[4 + half] = n_dead;                                       // black's half: white stones in terr_black
+        if (half == 0) {
+            co[6] = ok ? G::N - n_union : 0;
+            co[7] = n_safe - n_other;
+        }
+    }
+}
+
+static int launch_life(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
+                       hipStream_t st) {
+    SGO_DISPATCH(S, k_life<kS><<<dim3(n), dim3(64), 0, st>>>(n, d_records, n_records, d_index, d_sets, d_counts));
+    SGO_HIP(hipGetLastError());
+    return SGO_OK;
+}
+
+// sgo_session_life's launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
+int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint32_t *d_sets,
+                        int32_t *d_counts, hipStream_t st) {
+    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
+    if (rc != SGO_OK) return rc;
+    return launch_life(c.S, n, c.pos, ctx_records(c), d_index, d_sets, d_counts, st);
+}
+
+}  // namespace sgo
+
+using namespace sgo;
+
+extern "C" {
+
+int sgo_life_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
+                 void *stream) {
+    if (!size_ok(S) || n < 0 || n_records < 0 || !d_records || !d_sets || !d_counts) {
+        set_error("sgo_life_dev: bad argument (unsupported size, n < 0, n_records < 0, a NULL record array or output)");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    return launch_life(S, n, d_records, n_records, d_index, d_sets, d_counts, (hipStream_t)stream);
+}
+
+int sgo_life(int S, int n, const uint32_t *records, uint32_t *sets, int32_t *counts) {
+    if (!size_ok(S) || n < 0 || !records || !sets || !counts) {
+        set_error("sgo_life: bad argument (unsupported size, n < 0, a NULL record array or output)");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    // one block: records | sets | counts.  Every row is written whole, so nothing of the caller's goes in.
+    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), sb = (size_t)n * 4 * sgo_plane_words(S) * sizeof(uint32_t);
+    const size_t cb = (size_t)n * 8 * sizeof(int32_t);
+    uint8_t *d = nullptr;
+    SGO_HIP(hipMalloc((void **)&d, rb + sb + cb));
+    uint32_t *d_sets = reinterpret_cast<uint32_t *>(d + rb);
+    int32_t *d_counts = reinterpret_cast<int32_t *>(d + rb + sb);
+    int rc = SGO_OK;
+    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = launch_life(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, d_sets, d_counts, nullptr);
+    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(sets, d_sets, sb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(e, "sgo_life", __FILE__, __LINE__);
+    return rc;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
-// sgo_keys.hip) and of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip).  Those two and sgo_rollout_start_sessions
+// sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip) and of sgo_session_life ("unconditional life";
+// sgo_life.hip).  Those three and sgo_rollout_start_sessions
 // (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
 // kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
@@ -20,6 +21,9 @@ int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_
 // csrc/sgo_tactics.hip: k_session_roots, k_tactics_chains and k_tactics_read on device pointers
 int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
                            int32_t *d_n_chains, int32_t *d_chains, hipStream_t st);
+// csrc/sgo_life.hip: k_session_roots and k_life on device pointers
+int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint32_t *d_sets,
+                        int32_t *d_counts, hipStream_t st);
 
 int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
     k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
@@ -84,7 +88,7 @@ static int session_buffer(sgo_ctx *x, size_t bytes) {
     return SGO_OK;
 }
 
-// The shared opening of sgo_session_report, _keys and _tactics (readers: a slot may be listed twice): the list is checked against
+// The shared opening of sgo_session_report, _keys, _tactics and _life (readers: a slot may be listed twice): the list is checked against
 // the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
 static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t *slots, size_t bytes, hipStream_t st) {
     const Ctx &c = x->c;
@@ -293,6 +297,34 @@ int sgo_session_tactics(sgo_ctx *x, int n, const int32_t *slots, int max_chains,
         memcpy(libs + (size_t)i * N, hl + (size_t)i * N, N);
         const int stored = hn[i] < max_chains ? hn[i] : max_chains;   // the chain rows behind them were not written
         memcpy(chains + (size_t)i * max_chains * 8, hc + (size_t)i * max_chains * 8, sizeof(int32_t) * 8 * (size_t)stored);
+    }
+    return SGO_OK;
+}
+
+int sgo_session_life(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, uint32_t *sets, int32_t *counts, void *stream) {
+    if (!x || n < 0 || (n && (!slots || !status || !sets || !counts))) { set_error("sgo_session_life: bad argument"); return SGO_ERR_ARG; }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    // slots | record index | status | counts | sets; everything behind the index comes back in one copy
+    const size_t NW = (size_t)sgo_plane_words(c.S);
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n, sb = sizeof(uint32_t) * 4 * NW * (size_t)n;
+    const int rc = stage_session_list(x, "sgo_session_life", n, slots, 3 * ib + cb + sb, st);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    const int lrc = launch_session_life(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + 2 * ib),
+                                        reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<uint32_t *>(d + 3 * ib + cb),
+                                        reinterpret_cast<int32_t *>(d + 3 * ib), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, ib + cb + sb, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hc = reinterpret_cast<const int32_t *>(h + 3 * ib);
+    const uint32_t *hw = reinterpret_cast<const uint32_t *>(h + 3 * ib + cb);
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
+        memcpy(sets + (size_t)i * 4 * NW, hw + (size_t)i * 4 * NW, sizeof(uint32_t) * 4 * NW);
     }
     return SGO_OK;
 }

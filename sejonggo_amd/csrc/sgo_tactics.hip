@@ -16,24 +16,10 @@
 #include <string.h>
 
 #include "sgo_engine_state.hpp"
+#include "sgo_half.hpp"
 #include "sgo_rows.hpp"
 
 namespace sgo {
-
-// sum of a per-lane count over the 32 lanes of the half, delivered to every lane of it
-SGO_DEV int half_sum(int v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
-// index y * S + x of the lowest set bit of a set (rows per lane), the same in every lane of the half; -1 for the empty set
-template <int S>
-SGO_DEV int lowest_point(uint32_t v, int half) {
-    const uint32_t nz = rows::half_ballot(v != 0, half);
-    const int first = nz ? (__ffs((int)nz) - 1) : 0;
-    const int x = __shfl(v ? __builtin_ctz(v) : 0, half * 32 + first, 64);
-    return nz ? first * S + x : -1;
-}
 
 template <int S>
 __global__ __launch_bounds__(64) void k_tactics_chains(int n, const uint32_t *records, int n_records, const int32_t *index, int max_chains,

@@ -760,6 +760,20 @@ class SessionEngine(SelfPlayEngine):
                                                     self._stream_ptr()), "sgo_session_tactics")
         return out
 
+    def life(self, slots):
+        """Unconditional life of the root positions of the listed holding sessions (sgo_session_life; include/sgo.h "unconditional
+        life"): a life.Life with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays zero).
+        Boards and trees are only read."""
+        from .life import Life
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n, NW = len(slots), self.lib.sgo_plane_words(self.S)
+        out = Life(self.S, np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32))
+        out.status = np.zeros(n, np.int32)
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_life(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(out.status), _lib.ptr(out.sets),
+                                                 _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_life")
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

@@ -241,6 +241,13 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the slot is not a holding session")
         return t.chains_of(0)
 
+    def life(self):
+        """Unconditional life of the position on the board (engine.SessionEngine.life): a life.Life with one row."""
+        v = self.engine.life([self.slot])
+        if int(v.status[0]):
+            raise ValueError("the slot is not a holding session")
+        return v
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -291,7 +298,7 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "sgo-book", "sgo-ladders", "quit"])
+                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -457,7 +464,15 @@ class GTPEngine(object):
         chains = self._engine_method("tactics")()
         return "\n".join(format_chain(c, self._vertex) for c in chains if c.capturable or c.dead)
 
-    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders"}      # GTP private extensions carry a hyphen; methods cannot
+    def sgo_life(self):
+        """Private extension `sgo-life`: unconditional life of the position (include/sgo.h "unconditional life") -- S lines of S
+        characters from the top row down: B / W an alive stone, b / w a point of black / white territory (empty, or a dead stone of
+        the other colour), . anything else; then one line `settled P/N black SB white SW`."""
+        from .life import format_board
+        return format_board(self._engine_method("life")(), 0)
+
+    ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
+               "sgo-life": "sgo_life"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

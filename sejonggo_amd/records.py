@@ -349,6 +349,21 @@ class DeviceRecords(object):
                             "sgo_tactics_dev")
         return libs, n_chains, chains
 
+    def life(self, index):
+        """(sets int32 [n, 4, NW] holding the uint32 bit patterns, counts int32 [n, 8]) device tensors of the listed records
+        (sgo_life_dev, one launch; include/sgo.h "unconditional life"); an index outside the object gives the zero row."""
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        index = index.contiguous()
+        n = int(index.shape[0])
+        sets = torch.zeros((n, 4, self.NW), dtype=torch.int32, device=self.device)
+        counts = torch.zeros((n, 8), dtype=torch.int32, device=self.device)
+        if n:
+            P = self._lib.ptr
+            self._lib.check(self.lib.sgo_life_dev(C.c_int(self.S), C.c_int(n), C.c_void_p(self.rec_ptr), C.c_int(self.cap), P(index),
+                                                  P(sets), P(counts), self._lib.stream_ptr()), "sgo_life_dev")
+        return sets, counts
+
     def stones(self, index):
         """int8 [n, N] (host): +1 black, -1 white on the listed records; an index outside the object gives the empty board."""
         from .tactics import stones_of
@@ -464,14 +479,33 @@ class RecordSet(object):
         large collection give the set a smaller max_entries (the chunk size) or a smaller max_chains."""
         from .tactics import Tactics
         for ch in self.replay():
-            n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
-            base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int64) + np.arange(len(ch.games))
-            have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1
-            index = np.full(int(n_entries.sum()) + len(ch.games), -1, np.int32)
-            for b, h in zip(base, have):
-                index[int(b):int(b + h)] = np.arange(int(b), int(b + h))
+            index = self._record_index(ch)
             libs, n_chains, chains = self.backend.tactics(index, max_chains)
             ch.tactics = Tactics(self.S, _host(libs, np.uint8), _host(n_chains), _host(chains))
+            if stones:
+                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
+            yield ch
+
+    def _record_index(self, ch):
+        """int32 [records of the chunk]: the record's own index where the replay wrote it, -1 behind a refused entry"""
+        n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
+        base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int64) + np.arange(len(ch.games))
+        have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1
+        index = np.full(int(n_entries.sum()) + len(ch.games), -1, np.int32)
+        for b, h in zip(base, have):
+            index[int(b):int(b + h)] = np.arange(int(b), int(b + h))
+        return index
+
+    # ------------------------------------------------------------------ unconditional life
+    def life(self, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `life`, a life.Life with one row per RECORD of the chunk (one
+        backend call per chunk): row ch.index[e] is the position before entry e, row ch.index[e] + 1 the position after it.
+        Records that were not written (behind a refused entry) give the zero row.  stones=True adds ch.stones as `tactics` does."""
+        from .life import Life
+        for ch in self.replay():
+            index = self._record_index(ch)
+            sets, counts = self.backend.life(index)
+            ch.life = Life(self.S, _host(sets, np.uint32), _host(counts))
             if stones:
                 ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
             yield ch
@@ -634,6 +668,24 @@ class RecordSet(object):
         return out
 
 
+def life_lines(record_set):
+    """[{"name", "plies", "first_alive", "unsettled"}] per game from one RecordSet.life pass: the number of entries played, the
+    first ply (0 = the empty board, k = after entry k) whose position has a non-empty alive set (None: none), and `unsettled` of
+    the position after the last played entry."""
+    out = []
+    for ch in record_set.life():
+        v, base = ch.life, 0
+        for i, g in enumerate(ch.games):
+            n = len(record_set.records[g].entries)
+            played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
+            rows = v.counts[base:base + played + 1]
+            alive = np.flatnonzero((rows[:, 0] + rows[:, 1]) > 0)
+            out.append({"name": record_set.records[g].name, "plies": played, "first_alive": int(alive[0]) if len(alive) else None,
+                        "unsettled": int(rows[-1, 6])})
+            base += n + 1
+    return out
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -670,6 +722,8 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--book", default=None, help="write the opening book of the records to this .npz")
     ap.add_argument("--book-plies", type=int, default=30, help="moves whose node index is below N enter the book (default 30)")
     ap.add_argument("--duplicates", action="store_true", help="list the records that are one game, in any orientation")
+    ap.add_argument("--life", action="store_true",
+                    help="per game: plies, the first ply with an unconditionally alive stone (or -), unsettled points at the last ply")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -711,6 +765,11 @@ def main(argv=None, out=sys.stdout):
                 out.write("duplicates: %s\n" % " ".join(names))
             out.write("duplicate groups %d\n" % len(groups))
             doc["duplicates"] = groups
+        if a.life:
+            doc["life"] = life_lines(rs)
+            for d in doc["life"]:
+                out.write("life %s plies %d first_alive %s unsettled %d\n" % (
+                    d["name"], d["plies"], "-" if d["first_alive"] is None else "%d" % d["first_alive"], d["unsettled"]))
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

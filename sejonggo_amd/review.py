@@ -3,7 +3,7 @@ them set up in one launch (engine.SessionEngine.setup), searched together withou
 all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
-                                           [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics]
+                                           [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -13,7 +13,10 @@ positions of a chunk in one batch) and adds the score lead (mean of black - whit
 of the rollouts won on the board (komi aside) and the number of stones judged dead.  --tactics reads the chains and ladders of
 every position of the record in one call (records.RecordSet.tactics) and flags a move `ladder` when it runs out a chain that was
 dead even with its owner to move and is still capturable afterwards, `missed` when it leaves an opponent chain of three or more
-stones standing that could have been caught.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+stones standing that could have been caught.  --life reads the unconditional life of every position of the record in one call
+(records.RecordSet.life): each row gains life = {settled, black, white} (the points safe for either colour, for black, for white, in
+the position before the move), a move is flagged `inside` when it is played on a point that lay in either colour's territory and
+`decided` at the first position without an unsettled point.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -162,10 +165,54 @@ def add_tactics(rows, game, record_set=None):
     return rows
 
 
+def life_rows(game, record_set):
+    """{move number: {"settled", "black", "white", "flags"}} of the B / W moves of `game` (life.review_flags) from one RecordSet.life
+    pass over a set that holds the game as its only record: the figures of the position BEFORE the move."""
+    from .life import review_flags
+    out = {}
+    for ch in record_set.life():
+        v, m, decided = ch.life, 0, False
+        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+            if is_setup:
+                continue
+            m += 1
+            if not ch.valid[e]:
+                continue
+            r = int(ch.index[e])
+            c = v.counts[r]
+            flags = review_flags(game.size, int(action), v, r, decided)
+            decided = decided or v.settled(r)
+            out[m] = {"settled": game.size * game.size - int(c[6]), "black": int(c[0]) + int(c[2]), "white": int(c[1]) + int(c[3]),
+                      "flags": flags}
+    return out
+
+
+def add_life(rows, game, record_set=None):
+    """Adds `life` ({settled, black, white}) and `life_flags` to every row of a review.  record_set None: a device RecordSet of
+    the game."""
+    from .records import Record, RecordSet
+    own = record_set is None
+    if own:
+        entries = [(int(a), int(c)) for a, c in game.moves]
+        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    try:
+        found = life_rows(game, record_set)
+    finally:
+        if own:
+            record_set.close()
+    for row in rows:
+        d = found.get(row["move_number"])
+        if d is not None:
+            row["life"] = {k: d[k] for k in ("settled", "black", "white")}
+            row["life_flags"] = list(d["flags"])
+    return rows
+
+
 def format_row(row):
     text = _format_row(row)
-    if row.get("tactics"):
-        text += "  | " + " ".join(row["tactics"])
+    flags = list(row.get("tactics") or []) + list(row.get("life_flags") or [])
+    if flags:
+        text += "  | " + " ".join(flags)
     return text
 
 
@@ -216,6 +263,7 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--symmetry", default="random1", choices=["random1", "avg8", "identity"])
     ap.add_argument("--rollouts", type=int, default=0, help="policy rollouts per position: score lead, black's win share, dead stones")
     ap.add_argument("--tactics", action="store_true", help="flag moves that run out a dead ladder or miss a capturable chain")
+    ap.add_argument("--life", action="store_true", help="flag moves played inside settled territory and the position that settled the board")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
@@ -236,6 +284,8 @@ def main(argv=None, out=sys.stdout):
             destroy_predicting_workers(conf['GPUs'][:1])
     if a.tactics:
         add_tactics(rows, game)
+    if a.life:
+        add_life(rows, game)
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.json:
