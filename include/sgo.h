@@ -51,7 +51,7 @@ extern "C" {
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
  *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
  *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics), the "unconditional life" section
- *   (sgo_life*, sgo_session_life). */
+ *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -678,6 +678,73 @@ int sgo_life(int S, int n, const uint32_t *records, uint32_t *sets, int32_t *cou
  * not a holding session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be listed
  * repeatedly. */
 int sgo_session_life(sgo_ctx *ctx, int n, const int32_t *slots, int32_t *status, uint32_t *sets, int32_t *counts, void *stream);
+
+/* ---- shape search: where does a local pattern occur in a position? ---------------------------------------------------------------- */
+/* Per packed record: every place at which a small grid of black / white / empty / don't-care cells occurs, in any of its sixteen
+ * variants (the eight symmetries of the grid, colours as drawn or exchanged), anchored to the board edges the shape names
+ * (csrc/sgo_shapes.hip).  What a search for a joseki or a side shape in a game collection stands on.  Everything is integer.
+ * N = S * S, NW = sgo_plane_words(S).
+ * Inputs of a record: black / white = the bits a < N of planes 0 / 1.  The to-play flag (the top bit of the last word of plane 0) is
+ * NOT a stone; at S = 5 it shares the only word with the stones.  Padding bits and planes 2..15 are never read.  A point is EMPTY
+ * iff it is on the board and in neither set.
+ * A SHAPE is a grid of w columns and h rows, 1 <= w, h <= S.  Each cell c[j][i] (row j < h counted from the top, column i < w
+ * counted from the left, as board rows y and columns x are) is one of X, O, empty, don't-care.  Bit i of x[j] / o[j] / e[j] says
+ * that cell (i, j) is X / O / must be empty; a cell in none of the three is don't-care.  `edges` is a bit set of the sides of the
+ * grid that must lie on the board's edge: L = 1, T = 2, R = 4, B = 8.  `reserved` is 0. */
+typedef struct sgo_shape { int32_t w, h, edges, reserved; uint32_t x[19], o[19], e[19]; } sgo_shape;
+/* VARIANTS: sixteen, v = 8 * c + g.  c = 1 exchanges X and O (empty and don't-care cells stay).  g transforms the grid; the new
+ * grid has w' columns and h' rows:
+ *   g   w', h'   c'[j][i] =            new L, T, R, B = old
+ *   0   w, h     c[j][i]               L, T, R, B
+ *   1   h, w     c[i][j]               T, L, B, R
+ *   2   w, h     c[j][w-1-i]           R, T, L, B
+ *   3   w, h     c[h-1-j][i]           L, B, R, T
+ *   4   h, w     c[h-1-i][j]           B, L, T, R
+ *   5   w, h     c[h-1-j][w-1-i]       R, B, L, T
+ *   6   h, w     c[i][w-1-j]           T, R, B, L
+ *   7   h, w     c[h-1-i][w-1-j]       B, R, T, L
+ * An edge flag stays with the side of the grid it was attached to (the column or row of cells that lay on that side is carried to
+ * a side of the new grid, and the flag goes with it); should the last column of the table ever disagree with that rule, the rule
+ * holds.  Variant v is DROPPED when an earlier variant v' < v has the same w', h', cells and edges: a symmetric shape is counted
+ * once per place.  The others are KEPT.
+ * MATCHING: a kept variant matches the record at (x0, y0), 0 <= x0 <= S - w', 0 <= y0 <= S - h', iff every X / O / empty cell
+ * (i, j) finds the point (y0 + j) * S + x0 + i black / white / empty, and every edge flag of the variant holds: L: x0 == 0,
+ * T: y0 == 0, R: x0 + w' == S, B: y0 + h' == S.  Don't-care cells ask nothing of their points, but the whole window lies on the
+ * board, don't-care cells included.
+ * OUTPUTS per listed row:
+ *   hits  int32 [4] = n_hits  the number of triples (kept v, x0, y0) that match,
+ *                     first   the smallest (v * S + y0) * S + x0 among them, -1 when there is none,
+ *                     vmask   bit v set iff variant v matches somewhere,
+ *                     n_cover the number of bits set in cover.
+ *   cover uint32 [NW] = the union over all matches of the board points under cells that are not don't-care; bit order as the legal
+ *         bitsets of sgo_legal_dev; all bits a >= N are zero.
+ * A row whose record index is outside [0, n_records) gives {0, -1, 0, 0} and a zero cover.
+ *
+ * sgo_shape_compile: pure HOST arithmetic like sgo_sym_lut (no device is needed).  Writes the table the kernels read,
+ * SGO_SHAPE_TABLE_WORDS words: words 0..15 = {S, n_kept, kept_mask (bit v: variant v is kept), w, h, edges, 0 ...}; the t-th kept
+ * variant in ascending v occupies the 64 words from 16 + 64 * t: {v, w', h', edges', x'[19], o'[19], e'[19], 0, 0, 0}, where bit i
+ * of x'[j] / o'[j] / e'[j] says that cell (i, j) of the variant must be black / white / empty (the exchange of c = 1 is already
+ * made); unused slots and unused rows are zero.  SGO_ERR_ARG (nothing written): an unsupported S, w or h outside [1, S], a bit at a
+ * column >= w or in a row >= h, a cell in two of the three sets, edges outside [0, 15], reserved != 0, a NULL argument. */
+#define SGO_SHAPE_TABLE_WORDS (16 + 16 * 64)
+int sgo_shape_compile(int S, const sgo_shape *shape, uint32_t *table);
+/* Row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place, and matches the
+ * table d_table [SGO_SHAPE_TABLE_WORDS] (DEVICE memory, as sgo_shape_compile wrote it for the same S).  d_hits int32 [n][4],
+ * d_cover uint32 [n][sgo_plane_words(S)].  ONE launch on `stream` (one half-wavefront per row), no allocation, no synchronisation,
+ * capturable; n == 0 is a no-op; rows >= n are not written.  The table is not read on the host: a table compiled for another size
+ * is the caller's error here (the two entry points below compile it themselves and refuse a word 0 that is not S).  SGO_ERR_ARG:
+ * an unsupported S, n < 0, n_records < 0, a NULL d_records, d_table or output. */
+int sgo_shapes_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_table, int32_t *d_hits,
+                   uint32_t *d_cover, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (compile, copy in, run, copy back): for drop-in use and
+ * parity tests.  SGO_ERR_ARG as both of the above. */
+int sgo_shapes(int S, int n, const uint32_t *records, const sgo_shape *shape, int32_t *hits, uint32_t *cover);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], hits [n][4], cover [n][sgo_plane_words(S)].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a
+ * holding session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be listed
+ * repeatedly.  SGO_ERR_ARG: a shape sgo_shape_compile refuses at the context's size, a slot outside the context, a NULL argument. */
+int sgo_session_shapes(sgo_ctx *ctx, int n, const int32_t *slots, const sgo_shape *shape, int32_t *status, int32_t *hits, uint32_t *cover,
+                       void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

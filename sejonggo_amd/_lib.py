@@ -39,6 +39,7 @@ SYMBOLS = [
     "sgo_keys_dev", "sgo_keys", "sgo_session_keys", "sgo_keys_mode",
     "sgo_tactics_dev", "sgo_tactics", "sgo_session_tactics", "sgo_tactics_stage",
     "sgo_life_dev", "sgo_life", "sgo_session_life",
+    "sgo_shape_compile", "sgo_shapes_dev", "sgo_shapes", "sgo_session_shapes",
 ]
 
 
@@ -191,6 +192,10 @@ def load():
     lib.sgo_life_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     lib.sgo_life.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.sgo_session_life.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_shape_compile.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.sgo_shapes_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_shapes.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_session_shapes.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
     _lib = lib
     return lib
 

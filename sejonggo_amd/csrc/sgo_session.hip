@@ -1,7 +1,7 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
-// sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip) and of sgo_session_life ("unconditional life";
-// sgo_life.hip).  Those three and sgo_rollout_start_sessions
+// sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
+// sgo_life.hip) and of sgo_session_shapes ("shape search"; sgo_shapes.hip).  Those four and sgo_rollout_start_sessions
 // (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
 // kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
@@ -24,6 +24,10 @@ int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_
 // csrc/sgo_life.hip: k_session_roots and k_life on device pointers
 int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint32_t *d_sets,
                         int32_t *d_counts, hipStream_t st);
+// csrc/sgo_shapes.hip: the checked table of a shape (host), and k_session_roots and k_shapes on device pointers
+int session_shape_table(int S, const sgo_shape *shape, uint32_t *table);
+int launch_session_shapes(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, const uint32_t *d_table,
+                          int32_t *d_hits, uint32_t *d_cover, hipStream_t st);
 
 int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
     k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
@@ -88,7 +92,7 @@ static int session_buffer(sgo_ctx *x, size_t bytes) {
     return SGO_OK;
 }
 
-// The shared opening of sgo_session_report, _keys, _tactics and _life (readers: a slot may be listed twice): the list is checked against
+// The shared opening of sgo_session_report, _keys, _tactics, _life and _shapes (readers: a slot may be listed twice): the list is checked against
 // the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
 static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t *slots, size_t bytes, hipStream_t st) {
     const Ctx &c = x->c;
@@ -325,6 +329,42 @@ int sgo_session_life(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, u
         if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
         memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
         memcpy(sets + (size_t)i * 4 * NW, hw + (size_t)i * 4 * NW, sizeof(uint32_t) * 4 * NW);
+    }
+    return SGO_OK;
+}
+
+int sgo_session_shapes(sgo_ctx *x, int n, const int32_t *slots, const sgo_shape *shape, int32_t *status, int32_t *hits, uint32_t *cover,
+                       void *stream) {
+    if (!x || n < 0 || !shape || (n && (!slots || !status || !hits || !cover))) { set_error("sgo_session_shapes: bad argument"); return SGO_ERR_ARG; }
+    Ctx &c = x->c;
+    uint32_t table[SGO_SHAPE_TABLE_WORDS];
+    const int crc = session_shape_table(c.S, shape, table);
+    if (crc != SGO_OK) return crc;
+    if ((int)table[0] != c.S) { set_error("sgo_session_shapes: the table was compiled for another size"); return SGO_ERR_ARG; }
+    if (n == 0) return SGO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // slots | table | record index | status | hits | cover; everything behind the index comes back in one copy
+    const size_t NW = (size_t)sgo_plane_words(c.S);
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), tb = sizeof(table), hb = sizeof(int32_t) * 4 * (size_t)n, cb = sizeof(uint32_t) * NW * (size_t)n;
+    const int rc = stage_session_list(x, "sgo_session_shapes", n, slots, 3 * ib + tb + hb + cb, st);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    memcpy(h + ib, table, tb);
+    SGO_HIP(hipMemcpyAsync(d + ib, h + ib, tb, hipMemcpyHostToDevice, st));
+    const size_t so = 2 * ib + tb, ho = so + ib, co = ho + hb;
+    const int lrc = launch_session_shapes(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + so),
+                                          reinterpret_cast<int32_t *>(d + ib + tb), reinterpret_cast<const uint32_t *>(d + ib),
+                                          reinterpret_cast<int32_t *>(d + ho), reinterpret_cast<uint32_t *>(d + co), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + so, d + so, ib + hb + cb, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + so), *hh = reinterpret_cast<const int32_t *>(h + ho);
+    const uint32_t *hc = reinterpret_cast<const uint32_t *>(h + co);
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        memcpy(hits + (size_t)i * 4, hh + (size_t)i * 4, sizeof(int32_t) * 4);
+        memcpy(cover + (size_t)i * NW, hc + (size_t)i * NW, sizeof(uint32_t) * NW);
     }
     return SGO_OK;
 }

@@ -774,6 +774,23 @@ class SessionEngine(SelfPlayEngine):
                                                  _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_life")
         return out
 
+    def shapes(self, slots, shape):
+        """Where a shapes.Shape occurs in the root positions of the listed holding sessions (sgo_session_shapes; include/sgo.h
+        "shape search"): a shapes.Shapes with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row
+        stays {0, -1, 0, 0}).  Boards and trees are only read."""
+        from .shapes import Shapes
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n, NW = len(slots), self.lib.sgo_plane_words(self.S)
+        hits = np.zeros((n, 4), np.int32)
+        hits[:, 1] = -1
+        out = Shapes(self.S, hits, np.zeros((n, NW), np.uint32))
+        out.status = np.zeros(n, np.int32)
+        s = shape.to_struct()
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_shapes(self.ctx, C.c_int(n), _lib.ptr(slots), C.byref(s), _lib.ptr(out.status),
+                                                   _lib.ptr(out.hits), _lib.ptr(out.cover_words), self._stream_ptr()), "sgo_session_shapes")
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

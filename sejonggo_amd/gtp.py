@@ -248,6 +248,13 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the slot is not a holding session")
         return v
 
+    def shapes(self, shape):
+        """Where a shapes.Shape occurs in the position on the board (engine.SessionEngine.shapes): a shapes.Shapes with one row."""
+        v = self.engine.shapes([self.slot], shape)
+        if int(v.status[0]):
+            raise ValueError("the slot is not a holding session")
+        return v
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -298,7 +305,7 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "quit"])
+                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -471,8 +478,21 @@ class GTPEngine(object):
         from .life import format_board
         return format_board(self._engine_method("life")(), 0)
 
+    def sgo_find(self, *rows):
+        """Private extension `sgo-find ROW/ROW/...`: where the shape drawn by the rows (shapes.Shape.parse: X O . * ?, `|` and lines
+        of `-` for the edges; rows joined by `/`) occurs in the position (include/sgo.h "shape search") -- S lines of S characters
+        from the top row down: # a point under a cared cell of a match, . anything else; then one line `hits H variants V cover K`."""
+        from .shapes import Shape, format_cover
+        if not rows:
+            raise GTPFailure("syntax error")
+        try:
+            shape = Shape.parse("/".join(rows))
+        except ValueError as e:
+            raise GTPFailure("bad shape: %s" % e)
+        return format_cover(self._engine_method("shapes")(shape), 0)
+
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
-               "sgo-life": "sgo_life"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-life": "sgo_life", "sgo-find": "sgo_find"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -3,7 +3,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
 
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
-                                        [--book OUT.npz] [--book-plies N] [--duplicates]
+                                        [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -32,6 +32,12 @@ reflections of the board do not change.  --book groups the recorded moves of the
 (canonical key, move in the canonical frame) and writes count / wins / losses per group as one .npz (Book); `gtp --device --book`
 plays from it.  --duplicates lists the records whose key sequences are equal ply for ply: the same game, in any orientation.
 Ko status and history are no part of a key.
+
+SHAPE SEARCH (include/sgo.h "shape search", csrc/sgo_shapes.hip).  --find SHAPE.txt reads a picture of a local shape (shapes.py:
+X O . and * for don't-care, `|` and lines of `-` for the board edges), searches every position of every record for it in all
+sixteen variants, and prints the games matched / searched and, for the first matching position of each game, the table of the
+moves recorded next -- on which cell of the shape as drawn, by the side drawn as X or O, elsewhere, or none -- sorted by count,
+with the mover's wins and losses.
 
 A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
 skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
@@ -364,6 +370,24 @@ class DeviceRecords(object):
                                                   P(sets), P(counts), self._lib.stream_ptr()), "sgo_life_dev")
         return sets, counts
 
+    def shapes(self, index, shape):
+        """(hits int32 [n, 4], cover int32 [n, NW] holding the uint32 bit patterns) device tensors of the listed records for a
+        shapes.Shape (sgo_shape_compile on the host, then sgo_shapes_dev, one launch; include/sgo.h "shape search"); an index
+        outside the object gives {0, -1, 0, 0} and a zero cover."""
+        from .shapes import compile_table
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        index = index.contiguous()
+        n = int(index.shape[0])
+        table = torch.from_numpy(compile_table(self.S, shape).view(np.int32)).to(self.device)
+        hits = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
+        cover = torch.zeros((n, self.NW), dtype=torch.int32, device=self.device)
+        if n:
+            P = self._lib.ptr
+            self._lib.check(self.lib.sgo_shapes_dev(C.c_int(self.S), C.c_int(n), C.c_void_p(self.rec_ptr), C.c_int(self.cap), P(index),
+                                                    P(table), P(hits), P(cover), self._lib.stream_ptr()), "sgo_shapes_dev")
+        return hits, cover
+
     def stones(self, index):
         """int8 [n, N] (host): +1 black, -1 white on the listed records; an index outside the object gives the empty board."""
         from .tactics import stones_of
@@ -509,6 +533,49 @@ class RecordSet(object):
             if stones:
                 ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
             yield ch
+
+    # ------------------------------------------------------------------ shape search
+    def shapes(self, shape):
+        """Generator of Chunks as `replay` gives them, each with `shapes`, a shapes.Shapes with one row per RECORD of the chunk
+        (one backend call per chunk), rows as in `life`.  Records that were not written give {0, -1, 0, 0}."""
+        from .shapes import Shapes
+        for ch in self.replay():
+            hits, cover = self.backend.shapes(self._record_index(ch), shape)
+            ch.shapes = Shapes(self.S, _host(hits), _host(cover, np.uint32))
+            yield ch
+
+    def find(self, shape):
+        """Where a shapes.Shape first occurs in every game, and what was played next.  {"searched", "matched", "games": [{"name",
+        "ply" (0 = the empty board, k = after entry k), "variant", "x0", "y0", "next" (a shapes.continuation key)}] of the games
+        that hold the shape, "continuations": [{"key", "label", "count", "wins", "losses"}] sorted by count (ties by label)}.
+        The move counted is the entry recorded from the first matching position, taken into the frame of the shape as drawn;
+        wins / losses are the mover's, by value_targets, where the record has a result."""
+        from .shapes import continuation, continuation_label
+        games, tally, searched = [], {}, 0
+        for ch in self.shapes(shape):
+            v, base, off = ch.shapes, 0, 0
+            for i, g in enumerate(ch.games):
+                n = len(self.records[g].entries)
+                played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
+                searched += 1
+                rows = np.flatnonzero(v.hits[base:base + played + 1, 0] > 0)
+                if len(rows):
+                    ply = int(rows[0])
+                    first = v.first(base + ply)
+                    e = off + ply
+                    has_move = ply < played
+                    key = continuation(shape, self.S, first, int(ch.action[e]) if has_move else None, int(ch.colour[e]) if has_move else 0)
+                    games.append({"name": self.records[g].name, "ply": ply, "variant": first[0], "x0": first[1], "y0": first[2], "next": key})
+                    t = tally.setdefault(key, [0, 0, 0])
+                    t[0] += 1
+                    if has_move:
+                        t[1] += int(ch.z[e] > 0)
+                        t[2] += int(ch.z[e] < 0)
+                base += n + 1
+                off += n
+        rows = [{"key": k, "label": continuation_label(k), "count": t[0], "wins": t[1], "losses": t[2]} for k, t in tally.items()]
+        rows.sort(key=lambda d: (-d["count"], d["label"]))
+        return {"searched": searched, "matched": len(games), "games": games, "continuations": rows}
 
     def book(self, plies=30, min_count=1):
         """Book of the played B / W moves whose node index (the reference's move_n) is below `plies`, grouped by (canon,
@@ -724,6 +791,9 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--duplicates", action="store_true", help="list the records that are one game, in any orientation")
     ap.add_argument("--life", action="store_true",
                     help="per game: plies, the first ply with an unconditionally alive stone (or -), unsettled points at the last ply")
+    ap.add_argument("--find", default=None, metavar="SHAPE.txt",
+                    help="search every position for the shape drawn in this file (shapes.Shape.parse): games matched / searched and "
+                         "the table of the moves played next")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -770,6 +840,16 @@ def main(argv=None, out=sys.stdout):
             for d in doc["life"]:
                 out.write("life %s plies %d first_alive %s unsettled %d\n" % (
                     d["name"], d["plies"], "-" if d["first_alive"] is None else "%d" % d["first_alive"], d["unsettled"]))
+        if a.find:
+            from .shapes import Shape
+            with open(a.find) as f:
+                found = rs.find(Shape.parse(f.read()))
+            out.write("find %s: games matched %d / searched %d\n" % (a.find, found["matched"], found["searched"]))
+            for d in found["continuations"]:
+                out.write("find next %-10s count %d wins %d losses %d\n" % (d["label"], d["count"], d["wins"], d["losses"]))
+            doc["find"] = {"matched": found["matched"], "searched": found["searched"],
+                           "games": [dict(d, next=list(d["next"])) for d in found["games"]],
+                           "continuations": [dict(d, key=list(d["key"])) for d in found["continuations"]]}
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

@@ -4,6 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
+                                           [--find SHAPE.txt]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -16,7 +17,9 @@ dead even with its owner to move and is still capturable afterwards, `missed` wh
 stones standing that could have been caught.  --life reads the unconditional life of every position of the record in one call
 (records.RecordSet.life): each row gains life = {settled, black, white} (the points safe for either colour, for black, for white, in
 the position before the move), a move is flagged `inside` when it is played on a point that lay in either colour's territory and
-`decided` at the first position without an unsettled point.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+`decided` at the first position without an unsettled point.  --find SHAPE.txt searches every position of the record for the shape
+drawn in the file (shapes.Shape.parse, records.RecordSet.shapes): the move after which it first occurs is flagged `appears`, the
+first move after which it is gone again `disappears`.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -208,9 +211,52 @@ def add_life(rows, game, record_set=None):
     return rows
 
 
+def find_rows(game, record_set, shape):
+    """{move number: {"hits", "flags"}} of the B / W moves of `game` from one RecordSet.shapes pass over a set that holds the game
+    as its only record: `hits` = n_hits of the position AFTER the move, `flags` = shapes.review_flags of the positions around it,
+    each flag given once (the first appearance, the first disappearance after it)."""
+    from .shapes import review_flags
+    out = {}
+    for ch in record_set.shapes(shape):
+        v, m, seen, gone = ch.shapes, 0, False, False
+        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+            if is_setup:
+                continue
+            m += 1
+            if not ch.valid[e]:
+                continue
+            r = int(ch.index[e])
+            before, after = v.n_hits(r) > 0, v.n_hits(r + 1) > 0
+            flags = [f for f in review_flags(before, after) if not (seen if f == "appears" else gone)]
+            seen, gone = seen or before or after, gone or "disappears" in flags
+            out[m] = {"hits": v.n_hits(r + 1), "flags": flags}
+    return out
+
+
+def add_find(rows, game, shape, record_set=None):
+    """Adds `find` (n_hits of the position after the move) and `find_flags` to every row of a review.  record_set None: a device
+    RecordSet of the game."""
+    from .records import Record, RecordSet
+    own = record_set is None
+    if own:
+        entries = [(int(a), int(c)) for a, c in game.moves]
+        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    try:
+        found = find_rows(game, record_set, shape)
+    finally:
+        if own:
+            record_set.close()
+    for row in rows:
+        d = found.get(row["move_number"])
+        if d is not None:
+            row["find"] = d["hits"]
+            row["find_flags"] = list(d["flags"])
+    return rows
+
+
 def format_row(row):
     text = _format_row(row)
-    flags = list(row.get("tactics") or []) + list(row.get("life_flags") or [])
+    flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -264,6 +310,7 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--rollouts", type=int, default=0, help="policy rollouts per position: score lead, black's win share, dead stones")
     ap.add_argument("--tactics", action="store_true", help="flag moves that run out a dead ladder or miss a capturable chain")
     ap.add_argument("--life", action="store_true", help="flag moves played inside settled territory and the position that settled the board")
+    ap.add_argument("--find", default=None, metavar="SHAPE.txt", help="flag the moves after which the shape drawn in this file first appears and disappears")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
@@ -286,6 +333,10 @@ def main(argv=None, out=sys.stdout):
         add_tactics(rows, game)
     if a.life:
         add_life(rows, game)
+    if a.find:
+        from .shapes import Shape
+        with open(a.find) as f:
+            add_find(rows, game, Shape.parse(f.read()))
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.json:
