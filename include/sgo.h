@@ -746,6 +746,68 @@ int sgo_shapes(int S, int n, const uint32_t *records, const sgo_shape *shape, in
 int sgo_session_shapes(sgo_ctx *ctx, int n, const int32_t *slots, const sgo_shape *shape, int32_t *status, int32_t *hits, uint32_t *cover,
                        void *stream);
 
+/* ---- move outcomes: what would a stone on each point do? -------------------------------------------------------------------------- */
+/* Per packed record and per point of the board: what ONE ply by a chosen side on that point captures, how large the mover's new
+ * chain is and how many liberties it is left with, which of the mover's chains it joins, which opponent chains it puts in atari;
+ * and a per-record summary (csrc/sgo_moves.hip).  What a review tool, a record statistic and a GTP front end ask of a move
+ * without playing it.  Everything is integer.  N = S * S.
+ * Inputs of a record: black / white = the bits a < N of planes 0 / 1; the to-play flag is read as sgo_keys_dev reads it (the top
+ * bit of the last word of plane 0; NOT a stone, at S = 5 it shares the only word with the stones); planes 2 / 3 = black / white
+ * one ply ago, bits a < N, used only for the ko test; padding bits and planes 4..15 are never read.
+ * `side` chooses the MOVER M.  side = 0: M is the record's side to move (white iff the flag is set), and `prev` = M's stones one
+ * ply ago (plane 2 for black, plane 3 for white).  side = 1: M is the other colour; there is no `prev` and so no ko restriction
+ * (the convention of the tactics reader's root).  "own" = M's stones, "opp" = the other colour's.  A CHAIN is a maximal
+ * 4-connected set of stones of one colour; its LIBERTIES are the empty points 4-adjacent to it.
+ * PER POINT a (index y * S + x) a row int16[8] = {flags, captured, size, libs, joined, weakest, ataris, atari_stones}:
+ *   flags & SGO_MOVES_OCCUPIED: a holds a stone.  Words 1..7 are then 0, and ALLOWED and SUICIDE are never set.
+ *   flags & SGO_MOVES_KO: `prev` exists, prev & ~own is exactly one point, and that point is a.  Stated literally: in a constructed
+ *     record it may coincide with OCCUPIED (an opp stone on a).
+ *   flags & SGO_MOVES_ALLOWED: bit a of sgo_legal_moves for M to move with that `prev` -- the project's rule: a point without an
+ *     empty neighbour only if it captures, and the one-stone ko approximation (play.py:78-80), i.e. never a KO point.
+ *   For an EMPTY a let P' be the position after one ply of sgo_make_play by M on a (captures first, then suicide is executed); the
+ *   ply is played whether or not it is ALLOWED.
+ *   captured = the number of opp stones of the record that are gone in P'.
+ *   flags & SGO_MOVES_SUICIDE: a is empty in P'.  Then size = libs = ataris = atari_stones = 0.
+ *   size = the stones of M's chain on a in P';  libs = its liberties in P' (no saturation).
+ *   joined = the number of DISTINCT own chains of the position BEFORE the ply that have a stone 4-adjacent to a (0..4).
+ *   weakest = the smallest liberty count among those chains BEFORE the ply (a itself counts as a liberty of theirs); 0 when
+ *     joined is 0.
+ *   ataris = the number of DISTINCT opp chains of P' that have a stone 4-adjacent to a and exactly one liberty in P';
+ *   atari_stones = the stones of those chains together.
+ *   (So an empty point with no stone among its neighbours has {ALLOWED unless KO, 0, 1, its on-board neighbours, 0, 0, 0, 0}.)
+ * PER RECORD counts int32[8]; entries 0..6 are taken over the ALLOWED points only:
+ *   0 allowed           the number of ALLOWED points
+ *   1 capturing         points with captured > 0
+ *   2 max_captured      the largest captured
+ *   3 max_capture_move  the lowest a that reaches it; -1 when nothing captures
+ *   4 self_atari        points with libs == 1 and captured == 0
+ *   5 atari_giving      points with ataris > 0
+ *   6 escapes           points with weakest == 1 and libs >= 2
+ *   7 forbidden_sound   EMPTY points with none of ALLOWED, KO and SUICIDE: the moves the inherited rule forbids although the stone
+ *                       would stand (no empty neighbour, captures nothing, joins a chain that keeps a liberty)
+ *
+ * sgo_moves_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_moves int16 [n][N][8] (16-byte aligned: a point's row is one store), d_counts int32 [n][8].  A row whose record index is outside
+ * [0, n_records) gets all-zero rows and counts.  ONE launch on `stream` (one half-wavefront per row), no allocation, no
+ * synchronisation, capturable; n == 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0,
+ * side outside {0, 1}, a NULL d_records or output, a d_moves that is not 16-byte aligned. */
+#define SGO_MOVES_ALLOWED 1
+#define SGO_MOVES_OCCUPIED 2
+#define SGO_MOVES_KO 4
+#define SGO_MOVES_SUICIDE 8
+int sgo_moves_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_moves,
+                  int32_t *d_counts, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests.
+ * No alignment is asked of host buffers. */
+int sgo_moves(int S, int n, const uint32_t *records, int side, int16_t *moves, int32_t *counts);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], moves [n][N][8], counts [n][8].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding
+ * session: that row's outputs are left as the caller filled them.  The context is only read; a slot may be listed repeatedly.
+ * No alignment is asked of the host arrays: the kernel writes into the context's own staging block, at a 16-byte boundary, and the
+ * rows are copied out of it.  SGO_ERR_ARG: side outside {0, 1}, a slot outside the context, a NULL argument. */
+int sgo_session_moves(sgo_ctx *ctx, int n, const int32_t *slots, int side, int32_t *status, int16_t *moves, int32_t *counts,
+                      void *stream);
+
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */
 int sgo_root_table(sgo_ctx *ctx, int slot, int32_t *N, float *W, float *Q, double *P, int8_t *EX, int32_t *root_count,

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sgo_tactics_dev", "sgo_tactics", "sgo_session_tactics", "sgo_tactics_stage",
     "sgo_life_dev", "sgo_life", "sgo_session_life",
     "sgo_shape_compile", "sgo_shapes_dev", "sgo_shapes", "sgo_session_shapes",
+    "sgo_moves_dev", "sgo_moves", "sgo_session_moves",
 ]
 
 
@@ -196,6 +197,9 @@ def load():
     lib.sgo_shapes_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     lib.sgo_shapes.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.sgo_session_shapes.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    lib.sgo_moves_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_moves.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 2
+    lib.sgo_session_moves.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     _lib = lib
     return lib
 

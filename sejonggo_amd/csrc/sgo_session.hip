@@ -1,7 +1,8 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
 // sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
-// sgo_life.hip) and of sgo_session_shapes ("shape search"; sgo_shapes.hip).  Those four and sgo_rollout_start_sessions
+// sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip) and of sgo_session_moves ("move outcomes"; sgo_moves.hip).
+// Those five and sgo_rollout_start_sessions
 // (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
 // kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
@@ -28,6 +29,9 @@ int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_
 int session_shape_table(int S, const sgo_shape *shape, uint32_t *table);
 int launch_session_shapes(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, const uint32_t *d_table,
                           int32_t *d_hits, uint32_t *d_cover, hipStream_t st);
+// csrc/sgo_moves.hip: k_session_roots and k_moves on device pointers
+int launch_session_moves(const Ctx &c, int n, const int32_t *d_slots, int side, int32_t *d_status, int32_t *d_index, int16_t *d_moves,
+                         int32_t *d_counts, hipStream_t st);
 
 int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
     k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
@@ -92,7 +96,7 @@ static int session_buffer(sgo_ctx *x, size_t bytes) {
     return SGO_OK;
 }
 
-// The shared opening of sgo_session_report, _keys, _tactics, _life and _shapes (readers: a slot may be listed twice): the list is checked against
+// The shared opening of sgo_session_report, _keys, _tactics, _life, _shapes and _moves (readers: a slot may be listed twice): the list is checked against
 // the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
 static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t *slots, size_t bytes, hipStream_t st) {
     const Ctx &c = x->c;
@@ -365,6 +369,38 @@ int sgo_session_shapes(sgo_ctx *x, int n, const int32_t *slots, const sgo_shape 
         if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
         memcpy(hits + (size_t)i * 4, hh + (size_t)i * 4, sizeof(int32_t) * 4);
         memcpy(cover + (size_t)i * NW, hc + (size_t)i * NW, sizeof(uint32_t) * NW);
+    }
+    return SGO_OK;
+}
+
+int sgo_session_moves(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t *status, int16_t *moves, int32_t *counts, void *stream) {
+    if (!x || n < 0 || (side != 0 && side != 1) || (n && (!slots || !status || !moves || !counts))) {
+        set_error("sgo_session_moves: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    // slots | record index | status | counts | (to a 16-byte boundary) moves; everything behind the index comes back in one copy
+    const size_t N = (size_t)c.S * c.S;
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n, mb = sizeof(int16_t) * 8 * N * (size_t)n;
+    const size_t mo = (3 * ib + cb + 15) & ~(size_t)15;
+    const int rc = stage_session_list(x, "sgo_session_moves", n, slots, mo + mb, st);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    const int lrc = launch_session_moves(c, n, reinterpret_cast<const int32_t *>(d), side, reinterpret_cast<int32_t *>(d + 2 * ib),
+                                         reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<int16_t *>(d + mo),
+                                         reinterpret_cast<int32_t *>(d + 3 * ib), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, mo + mb - 2 * ib, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hc = reinterpret_cast<const int32_t *>(h + 3 * ib);
+    const int16_t *hm = reinterpret_cast<const int16_t *>(h + mo);
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
+        memcpy(moves + (size_t)i * N * 8, hm + (size_t)i * N * 8, sizeof(int16_t) * 8 * N);
     }
     return SGO_OK;
 }

@@ -791,6 +791,19 @@ class SessionEngine(SelfPlayEngine):
                                                    _lib.ptr(out.hits), _lib.ptr(out.cover_words), self._stream_ptr()), "sgo_session_shapes")
         return out
 
+    def moves(self, slots, side=0):
+        """What one ply on every point would do in the root positions of the listed holding sessions (sgo_session_moves;
+        include/sgo.h "move outcomes"): a moves.Moves with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding
+        session; that row stays zero).  side 0: the side to move, 1: the other colour.  Boards and trees are only read."""
+        from .moves import Moves
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(slots)
+        out = Moves(self.S, np.zeros((n, self.S * self.S, 8), np.int16), np.zeros((n, 8), np.int32), status=np.zeros(n, np.int32))
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_moves(self.ctx, C.c_int(n), _lib.ptr(slots), C.c_int(int(side)), _lib.ptr(out.status),
+                                                  _lib.ptr(out.rows), _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_moves")
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

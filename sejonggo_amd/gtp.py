@@ -255,6 +255,14 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the slot is not a holding session")
         return v
 
+    def move_outcomes(self, side=0):
+        """What one ply on every point of the position on the board would do (engine.SessionEngine.moves): a moves.Moves with one
+        row.  side 0: the side to move, 1: the other colour.  (`moves` is this engine's move list.)"""
+        v = self.engine.moves([self.slot], side)
+        if int(v.status[0]):
+            raise ValueError("the slot is not a holding session")
+        return v
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -305,7 +313,7 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "quit"])
+                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -491,8 +499,26 @@ class GTPEngine(object):
             raise GTPFailure("bad shape: %s" % e)
         return format_cover(self._engine_method("shapes")(shape), 0)
 
+    def sgo_moves(self, *words):
+        """Private extension `sgo-moves [capture|atari|escape|selfatari|forbidden|all] [opponent]`: what one ply on a point would do
+        (include/sgo.h "move outcomes") -- one line per point of the kind in ascending point order (default all: every empty
+        point), `V captures C size Z liberties L joins J ataris A`, then `ko` / `suicide` / `forbidden` where they hold.  The
+        mover is the side to move; with `opponent` the other colour, so `opponent capture` lists the stones en prise.  capture,
+        atari, escape (a chain with one liberty gets two or more) and selfatari list allowed moves only; forbidden lists the
+        points the legal-move rule forbids although the stone would stand."""
+        from .moves import KINDS, format_kind
+        kind, side = "all", 0
+        for w in words:
+            if w == "opponent" and side == 0:
+                side = 1
+            elif w in KINDS and kind == "all":
+                kind = w
+            else:
+                raise GTPFailure("syntax error")
+        return format_kind(self._engine_method("move_outcomes")(side), 0, kind, self._vertex)
+
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
-               "sgo-life": "sgo_life", "sgo-find": "sgo_find"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -3,7 +3,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
 
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
-                                        [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt]
+                                        [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt] [--moves]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -38,6 +38,12 @@ X O . and * for don't-care, `|` and lines of `-` for the board edges), searches 
 sixteen variants, and prints the games matched / searched and, for the first matching position of each game, the table of the
 moves recorded next -- on which cell of the shape as drawn, by the side drawn as X or O, elsewhere, or none -- sorted by count,
 with the mover's wins and losses.
+
+MOVE OUTCOMES (include/sgo.h "move outcomes", csrc/sgo_moves.hip).  --moves reads, for every position, what one ply on every point
+would do, keeps the row of the move that was played, and prints per bucket of --bucket moves the share of the played moves that
+capture / give atari / escape (a chain with one liberty gets two or more) / are self-atari, each beside the mean share of the
+ALLOWED moves of the same positions that do -- what the players chose against what the board offered -- and the number of points
+the inherited legal-move rule forbids although the stone would stand, with the positions that had any.
 
 A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
 skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
@@ -388,6 +394,41 @@ class DeviceRecords(object):
                                                     P(table), P(hits), P(cover), self._lib.stream_ptr()), "sgo_shapes_dev")
         return hits, cover
 
+    def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
+        """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
+        index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
+        one call.  With action int [n]: (played int16 [n, 8], counts, in_turn bool [n]) device tensors -- of the table only the row
+        of the listed action is kept (rows[arange, action], gathered on the device; the zero row for a pass or an action off the
+        board), so nothing of size n * N leaves the device; in_turn says that `colour` [n] (+1 black, -1 white; None: not asked,
+        all True) is the colour side 0 moves for, i.e. the record's side to move."""
+        from .moves import moves_dev
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        index = index.contiguous()
+        n = int(index.shape[0])
+        if action is None:
+            if n == 0:
+                return (torch.zeros((0, self.N, 8), dtype=torch.int16, device=self.device), torch.zeros((0, 8), dtype=torch.int32, device=self.device))
+            return moves_dev(self.S, self.records, index, side, self.lib)
+        action = torch.from_numpy(np.ascontiguousarray(action, np.int64)).to(self.device)
+        played = torch.zeros((n, 8), dtype=torch.int16, device=self.device)
+        counts = torch.zeros((n, 8), dtype=torch.int32, device=self.device)
+        for lo in range(0, n, int(rows_per_call)):
+            hi = min(n, lo + int(rows_per_call))
+            rows, c = moves_dev(self.S, self.records, index[lo:hi].contiguous(), side, self.lib)
+            a = action[lo:hi]
+            on = (a >= 0) & (a < self.N)
+            picked = rows[torch.arange(hi - lo, device=self.device), torch.where(on, a, torch.zeros_like(a))]
+            played[lo:hi] = picked * on[:, None].to(torch.int16)
+            counts[lo:hi] = c
+        in_turn = torch.ones(n, dtype=torch.bool, device=self.device)
+        if colour is not None and n:
+            ok = (index >= 0) & (index < self.cap)
+            flag = self.records[torch.where(ok, index, torch.zeros_like(index)).long(), self.NW - 1] < 0      # the top bit of plane 0's last word
+            col = torch.from_numpy(np.ascontiguousarray(colour, np.int32)).to(self.device)
+            in_turn = ok & (torch.where(flag, -1, 1) == col)
+        return played, counts, in_turn
+
     def stones(self, index):
         """int8 [n, N] (host): +1 black, -1 white on the listed records; an index outside the object gives the empty board."""
         from .tactics import stones_of
@@ -542,6 +583,21 @@ class RecordSet(object):
         for ch in self.replay():
             hits, cover = self.backend.shapes(self._record_index(ch), shape)
             ch.shapes = Shapes(self.S, _host(hits), _host(cover, np.uint32))
+            yield ch
+
+    # ------------------------------------------------------------------ move outcomes
+    def moves(self, side=0):
+        """Generator of Chunks as `replay` gives them, each with one row per ENTRY beside its fields (one backend call per chunk):
+        played int16 [rows, 8], the row of the move-outcome table (include/sgo.h "move outcomes") for the entry's action in the
+        position before it (zero for a pass); move_counts int32 [rows, 8], that position's counts; in_turn bool [rows], the entry's
+        colour is the colour the rows were computed for (side 0: the record's side to move -- False for a set-up stone or a move out
+        of turn, whose row then describes the other colour's stone).  The table itself, N rows per position, stays on the device:
+        only the played rows are copied.  Rows that were not played are zero."""
+        for ch in self.replay():
+            played, counts, in_turn = self.backend.moves(np.where(ch.valid, ch.index, -1).astype(np.int32), side, ch.action,
+                                                         ch.colour if side == 0 else -ch.colour)
+            ch.played, ch.move_counts = _host(played, np.int16), _host(counts)
+            ch.in_turn = _host(in_turn, bool) & ch.valid
             yield ch
 
     def find(self, shape):
@@ -753,6 +809,29 @@ def life_lines(record_set):
     return out
 
 
+def moves_table(record_set, width=20):
+    """The table of `--moves` (moves.bucket_table) from one RecordSet.moves pass: per bucket of `width` moves the share of the played
+    moves that capture / give atari / escape / are self-atari beside the mean share of the allowed moves of the same positions
+    that do, the forbidden-sound points and the positions that had any.  Set-up stones and moves out of turn are left out."""
+    from .moves import bucket_table
+    ply, action, played, counts = [], [], [], []
+    for ch in record_set.moves():
+        keep = ch.in_turn & ~ch.setup
+        first = {}
+        number = np.zeros(len(ch.action), np.int64)                  # the move number inside the game, set-up stones not counted
+        for e in np.flatnonzero(ch.valid & ~ch.setup):
+            g = int(ch.game[e])
+            number[e] = first.get(g, 0)
+            first[g] = number[e] + 1
+        ply.append(number[keep])
+        action.append(ch.action[keep])
+        played.append(ch.played[keep])
+        counts.append(ch.move_counts[keep])
+    if not ply:
+        return []
+    return bucket_table(np.concatenate(ply), np.concatenate(action), np.concatenate(played), np.concatenate(counts), record_set.S, width)
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -794,6 +873,10 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--find", default=None, metavar="SHAPE.txt",
                     help="search every position for the shape drawn in this file (shapes.Shape.parse): games matched / searched and "
                          "the table of the moves played next")
+    ap.add_argument("--moves", action="store_true",
+                    help="per 20-move bucket: the share of the played moves that capture / give atari / escape / are self-atari beside "
+                         "the mean share of the allowed moves of the same positions that do, and the points the inherited legal-move "
+                         "rule forbids although the stone would stand")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -850,6 +933,13 @@ def main(argv=None, out=sys.stdout):
             doc["find"] = {"matched": found["matched"], "searched": found["searched"],
                            "games": [dict(d, next=list(d["next"])) for d in found["games"]],
                            "continuations": [dict(d, key=list(d["key"])) for d in found["continuations"]]}
+        if a.moves:
+            from .moves import format_bucket_table
+            doc["moves"] = moves_table(rs, a.bucket)
+            if doc["moves"]:
+                out.write(format_bucket_table(doc["moves"]) + "\n")
+            out.write("moves: forbidden-sound points %d in %d positions\n" % (
+                sum(r["forbidden_sound"] for r in doc["moves"]), sum(r["positions_forbidden"] for r in doc["moves"])))
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

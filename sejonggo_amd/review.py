@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt]
+                                           [--find SHAPE.txt] [--moves]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -19,7 +19,12 @@ stones standing that could have been caught.  --life reads the unconditional lif
 the position before the move), a move is flagged `inside` when it is played on a point that lay in either colour's territory and
 `decided` at the first position without an unsettled point.  --find SHAPE.txt searches every position of the record for the shape
 drawn in the file (shapes.Shape.parse, records.RecordSet.shapes): the move after which it first occurs is flagged `appears`, the
-first move after which it is gone again `disappears`.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+first move after which it is gone again `disappears`.  --moves reads what one ply on every point of every position would do
+(records.RecordSet.moves; include/sgo.h "move outcomes") and flags each played move from its row in the position before it:
+`captures N`, `atari` (it leaves an opponent chain next to it with one liberty), `escape` (a chain of the mover's with one liberty
+gets two or more), `self-atari` (two or more stones left with one liberty, nothing captured; a one-stone throw-in is not flagged) and
+`missed-capture K at V` (it captured nothing while V would have taken K >= 3 stones).  These are flags, not verdicts: one ply is
+looked at and nothing is read out.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -254,9 +259,45 @@ def add_find(rows, game, shape, record_set=None):
     return rows
 
 
+def moves_rows(game, record_set):
+    """{move number: flags} of the B / W moves of `game` (moves.review_flags) from one RecordSet.moves pass over a set that holds the
+    game as its only record: the row of the played move in the position BEFORE it.  A move out of turn gets no flag: the table is
+    the side to move's."""
+    from .moves import review_flags
+    out = {}
+    for ch in record_set.moves():
+        m = 0
+        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+            if is_setup:
+                continue
+            m += 1
+            if not ch.valid[e]:
+                continue
+            out[m] = review_flags(game.size, int(action), ch.played[e], ch.move_counts[e], lambda a: vertex(a, game.size)) if ch.in_turn[e] else []
+    return out
+
+
+def add_moves(rows, game, record_set=None):
+    """Adds `moves_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    from .records import Record, RecordSet
+    own = record_set is None
+    if own:
+        entries = [(int(a), int(c)) for a, c in game.moves]
+        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    try:
+        found = moves_rows(game, record_set)
+    finally:
+        if own:
+            record_set.close()
+    for row in rows:
+        row["moves_flags"] = list(found.get(row["move_number"], []))
+    return rows
+
+
 def format_row(row):
     text = _format_row(row)
-    flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or [])
+    flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
+        list(row.get("moves_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -311,6 +352,9 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--tactics", action="store_true", help="flag moves that run out a dead ladder or miss a capturable chain")
     ap.add_argument("--life", action="store_true", help="flag moves played inside settled territory and the position that settled the board")
     ap.add_argument("--find", default=None, metavar="SHAPE.txt", help="flag the moves after which the shape drawn in this file first appears and disappears")
+    ap.add_argument("--moves", action="store_true",
+                    help="flag what each played move did in one ply: captures N, atari, escape, self-atari, missed-capture K at V "
+                         "(flags, not verdicts: nothing is read out)")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
@@ -337,6 +381,8 @@ def main(argv=None, out=sys.stdout):
         from .shapes import Shape
         with open(a.find) as f:
             add_find(rows, game, Shape.parse(f.read()))
+    if a.moves:
+        add_moves(rows, game)
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.json:
