@@ -51,7 +51,8 @@ extern "C" {
  *   as one kernel, the whole-net forward).   Added since without a bump: the "interactive games" section (sgo_session_*),
  *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
  *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics), the "unconditional life" section
- *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes). */
+ *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes), the "move
+ *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -807,6 +808,62 @@ int sgo_moves(int S, int n, const uint32_t *records, int side, int16_t *moves, i
  * rows are copied out of it.  SGO_ERR_ARG: side outside {0, 1}, a slot outside the context, a NULL argument. */
 int sgo_session_moves(sgo_ctx *ctx, int n, const int32_t *slots, int side, int32_t *status, int16_t *moves, int32_t *counts,
                       void *stream);
+
+/* ---- influence: who holds what right now, and by how much?  (an ESTIMATE, not a proof) --------------------------------------------- */
+/* Per packed record: Bouzy's dilation / erosion map of the stones, the territory and moyo sets read off it, and an area-score
+ * estimate (csrc/sgo_influence.hip).  The heuristic counterpart of the "unconditional life" section: that one is proved and says
+ * little before the endgame, this one answers for every position and can be wrong.  Everything is integer, a fixed number of steps,
+ * no loop depends on the data.  N = S * S.
+ * Inputs of a record: black / white = the bits a < N of planes 0 / 1.  The to-play flag (the top bit of the last word of plane 0;
+ * at S = 5 it shares the only word with the stones) is NOT a stone and changes no output.  Planes 2..15 and padding bits are never
+ * read.
+ * `dead` (optional), per ROW a bitset uint32 [sgo_plane_words(S)] in the bit order of the legal bitsets: a stone whose bit is set is
+ * LIFTED before anything else, its point is treated as empty.  Bits on empty points and bits a >= N are ignored.  NULL: nothing is
+ * lifted.  The LIVE stones are the stones that are not lifted.  (A point in both planes occurs only in an illegal record; it is
+ * read as a black stone.)
+ * PARAMETERS: dilate in [0, SGO_INFLUENCE_MAX_DILATE], erode_moyo <= erode_terr, both in [0, SGO_INFLUENCE_MAX_ERODE].  The
+ * classical triples (dilate, erode_moyo, erode_terr) are territory / moyo = (5, 10, 21) and area = (4, 0, 0).
+ * THE MAP: v[a] starts at +128 on a live black stone, -128 on a live white one, 0 elsewhere.  A NEIGHBOUR of a is one of the at
+ * most four ON-BOARD 4-adjacent points; off-board points do not exist: they are neither positive, negative nor zero.  Every step
+ * reads the previous map and writes a new one (Jacobi: all points at once).
+ *   DILATION step: pos(a) = the number of neighbours with v > 0, neg(a) = the number with v < 0.
+ *     if v[a] >= 0 and neg(a) == 0: v'[a] = v[a] + pos(a);   if v[a] <= 0 and pos(a) == 0: v'[a] = v[a] - neg(a);
+ *     otherwise v'[a] = v[a].  (When both conditions hold, both add 0.)
+ *   EROSION step: if v[a] > 0: v'[a] = max(0, v[a] - #{neighbours with v <= 0});
+ *     if v[a] < 0: v'[a] = min(0, v[a] + #{neighbours with v >= 0});   if v[a] == 0 it stays 0.
+ *   SCHEDULE: `dilate` dilation steps, then `erode_terr` erosion steps.  The map after the first `erode_moyo` erosion steps is the
+ *     MOYO map (erode_moyo == 0: the dilated map itself), the final one the TERRITORY map.
+ *   BOUNDS: |v| <= 128 + 4 * 8 = 160; a live stone keeps at least 128 - 4 * 31 = 4, so its sign never changes (hence the cap 31).
+ * OUTPUTS per listed row:
+ *   values int16 [N] = the territory map.
+ *   sets   uint32 [4][sgo_plane_words(S)] = terr_black, terr_white, moyo_black, moyo_white: the points WITHOUT a live stone whose
+ *          value is > 0 / < 0 in the territory map / in the moyo map (a lifted stone's point can be territory); bit order as the
+ *          legal bitsets of sgo_legal_dev; all bits a >= N are zero.
+ *   counts int32 [8] = |terr_black|, |terr_white|, |moyo_black|, |moyo_white|, live black stones, live white stones,
+ *          neutral = N - live stones - |terr_black| - |terr_white|,
+ *          margin = (live_black + |terr_black|) - (live_white + |terr_white|): the area-score estimate before komi.
+ *
+ * sgo_influence_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_dead uint32 [n][sgo_plane_words(S)] per ROW (not per record) or NULL; d_values int16 [n][N], d_sets uint32
+ * [n][4][sgo_plane_words(S)], d_counts int32 [n][8].  A row whose record index is outside [0, n_records) gets all-zero outputs.
+ * ONE launch on `stream` (one half-wavefront per row), no allocation, no synchronisation, capturable; n == 0 is a no-op; rows >= n
+ * are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, dilate / erode_moyo / erode_terr out of range,
+ * erode_moyo > erode_terr, a NULL d_records or output. */
+#define SGO_INFLUENCE_MAX_DILATE 8
+#define SGO_INFLUENCE_MAX_ERODE 31
+int sgo_influence_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_dead, int dilate,
+                      int erode_moyo, int erode_terr, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order, dead [n][sgo_plane_words(S)] or NULL (copy in, run, copy
+ * back): for drop-in use and parity tests. */
+int sgo_influence(int S, int n, const uint32_t *records, const uint32_t *dead, int dilate, int erode_moyo, int erode_terr, int16_t *values,
+                  uint32_t *sets, int32_t *counts);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: dead [n][sgo_plane_words(S)] or NULL, status [n], values [n][N], sets [n][4][sgo_plane_words(S)], counts [n][8].
+ * status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: that row's outputs are left as the caller filled
+ * them.  The context is only read; a slot may be listed repeatedly.  SGO_ERR_ARG: parameters as above, a slot outside the context,
+ * a NULL argument other than dead. */
+int sgo_session_influence(sgo_ctx *ctx, int n, const int32_t *slots, const uint32_t *dead, int dilate, int erode_moyo, int erode_terr,
+                          int32_t *status, int16_t *values, uint32_t *sets, int32_t *counts, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

@@ -1,8 +1,9 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
 // sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
-// sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip) and of sgo_session_moves ("move outcomes"; sgo_moves.hip).
-// Those five and sgo_rollout_start_sessions
+// sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip) and of
+// sgo_session_influence ("influence"; sgo_influence.hip).
+// Those six and sgo_rollout_start_sessions
 // (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
 // kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
@@ -32,6 +33,10 @@ int launch_session_shapes(const Ctx &c, int n, const int32_t *d_slots, int32_t *
 // csrc/sgo_moves.hip: k_session_roots and k_moves on device pointers
 int launch_session_moves(const Ctx &c, int n, const int32_t *d_slots, int side, int32_t *d_status, int32_t *d_index, int16_t *d_moves,
                          int32_t *d_counts, hipStream_t st);
+// csrc/sgo_influence.hip: the parameter check (host), and k_session_roots and k_influence on device pointers
+bool session_influence_params_ok(int dilate, int erode_moyo, int erode_terr);
+int launch_session_influence(const Ctx &c, int n, const int32_t *d_slots, const uint32_t *d_dead, int dilate, int erode_moyo, int erode_terr,
+                             int32_t *d_status, int32_t *d_index, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st);
 
 int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
     k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
@@ -401,6 +406,47 @@ int sgo_session_moves(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t
         if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
         memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
         memcpy(moves + (size_t)i * N * 8, hm + (size_t)i * N * 8, sizeof(int16_t) * 8 * N);
+    }
+    return SGO_OK;
+}
+
+int sgo_session_influence(sgo_ctx *x, int n, const int32_t *slots, const uint32_t *dead, int dilate, int erode_moyo, int erode_terr,
+                          int32_t *status, int16_t *values, uint32_t *sets, int32_t *counts, void *stream) {
+    if (!x || n < 0 || !session_influence_params_ok(dilate, erode_moyo, erode_terr) || (n && (!slots || !status || !values || !sets || !counts))) {
+        set_error("sgo_session_influence: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    // slots | dead | record index | status | counts | sets | values; everything behind the index comes back in one copy
+    const size_t N = (size_t)c.S * c.S, NW = (size_t)sgo_plane_words(c.S);
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), db = al8(sizeof(uint32_t) * NW * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n;
+    const size_t sb = sizeof(uint32_t) * 4 * NW * (size_t)n, vb = sizeof(int16_t) * N * (size_t)n;
+    const size_t xo = ib + db, so = xo + ib, co = so + ib, wo = co + cb, vo = wo + sb;
+    const int rc = stage_session_list(x, "sgo_session_influence", n, slots, vo + vb, st);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
+    if (dead) {
+        memcpy(h + ib, dead, sizeof(uint32_t) * NW * (size_t)n);
+        SGO_HIP(hipMemcpyAsync(d + ib, h + ib, db, hipMemcpyHostToDevice, st));
+    }
+    const int lrc = launch_session_influence(c, n, reinterpret_cast<const int32_t *>(d), dead ? reinterpret_cast<const uint32_t *>(d + ib) : nullptr,
+                                             dilate, erode_moyo, erode_terr, reinterpret_cast<int32_t *>(d + so), reinterpret_cast<int32_t *>(d + xo),
+                                             reinterpret_cast<int16_t *>(d + vo), reinterpret_cast<uint32_t *>(d + wo),
+                                             reinterpret_cast<int32_t *>(d + co), st);
+    if (lrc != SGO_OK) return lrc;
+    SGO_HIP(hipMemcpyAsync(h + so, d + so, vo + vb - so, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + so), *hc = reinterpret_cast<const int32_t *>(h + co);
+    const uint32_t *hw = reinterpret_cast<const uint32_t *>(h + wo);
+    const int16_t *hv = reinterpret_cast<const int16_t *>(h + vo);
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
+        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
+        memcpy(sets + (size_t)i * 4 * NW, hw + (size_t)i * 4 * NW, sizeof(uint32_t) * 4 * NW);
+        memcpy(values + (size_t)i * N, hv + (size_t)i * N, sizeof(int16_t) * N);
     }
     return SGO_OK;
 }

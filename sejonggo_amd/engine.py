@@ -774,6 +774,33 @@ class SessionEngine(SelfPlayEngine):
                                                  _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_life")
         return out
 
+    def influence(self, slots, dead="life", dilate=5, erode_moyo=10, erode_terr=21):
+        """Bouzy's influence map of the root positions of the listed holding sessions (sgo_session_influence; include/sgo.h
+        "influence"): an influence.Influence with status int32 [n] (SGO_ERR_STATE: not a holding session; that row stays zero).  An
+        estimate, not a proof.  dead "life": the stones sgo_session_life proves dead are lifted first -- the rows' `dead` sets are
+        terr_black | terr_white (a territory set holds empty points and the other colour's stones only, and bits on empty points
+        lift nothing); None: nothing is lifted; or uint32 [n, NW] of the caller's.  Boards and trees are only read."""
+        from .influence import Influence, check_params
+        dilate, erode_moyo, erode_terr = check_params(dilate, erode_moyo, erode_terr)
+        if isinstance(dead, str) and dead != "life":
+            raise ValueError("influence: dead is None, \"life\" or an array of bitsets")
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n, NW = len(slots), self.lib.sgo_plane_words(self.S)
+        if isinstance(dead, str):
+            proved = self.life(slots).sets
+            dead = np.ascontiguousarray(proved[:, 2] | proved[:, 3], dtype=np.uint32)
+        elif dead is not None:
+            dead = np.ascontiguousarray(dead, dtype=np.uint32)
+            if dead.shape != (n, NW):
+                raise ValueError("influence: dead must be [n, NW] words, one row per slot")
+        out = Influence(self.S, np.zeros((n, self.S * self.S), np.int16), np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32),
+                        status=np.zeros(n, np.int32))
+        with self._on_stream():
+            _lib.check(self.lib.sgo_session_influence(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(dead), C.c_int(dilate),
+                                                      C.c_int(erode_moyo), C.c_int(erode_terr), _lib.ptr(out.status), _lib.ptr(out.values),
+                                                      _lib.ptr(out.sets), _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_influence")
+        return out
+
     def shapes(self, slots, shape):
         """Where a shapes.Shape occurs in the root positions of the listed holding sessions (sgo_session_shapes; include/sgo.h
         "shape search"): a shapes.Shapes with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row

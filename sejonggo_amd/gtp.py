@@ -248,6 +248,15 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the slot is not a holding session")
         return v
 
+    def influence(self, dead="life", **params):
+        """Bouzy's influence map of the position on the board (engine.SessionEngine.influence): (an influence.Influence with one
+        row, the stones int8 [S * S], +1 black).  dead "life": proved-dead stones are lifted first; None: none are."""
+        from .rollout import real_board
+        v = self.engine.influence([self.slot], dead=dead, **params)
+        if int(v.status[0]):
+            raise ValueError("the slot is not a holding session")
+        return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
+
     def shapes(self, shape):
         """Where a shapes.Shape occurs in the position on the board (engine.SessionEngine.shapes): a shapes.Shapes with one row."""
         v = self.engine.shapes([self.slot], shape)
@@ -313,7 +322,8 @@ class GTPEngine(object):
     def list_commands(self):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
-                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "quit"])
+                          "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
+                          "sgo-estimate", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -517,8 +527,38 @@ class GTPEngine(object):
                 raise GTPFailure("syntax error")
         return format_kind(self._engine_method("move_outcomes")(side), 0, kind, self._vertex)
 
+    def _influence(self, words):
+        from .influence import PRESETS
+        preset, dead = None, "life"
+        for w in words:
+            if w == "nodead" and dead is not None:
+                dead = None
+            elif w in PRESETS and preset is None:
+                preset = w
+            else:
+                raise GTPFailure("syntax error")
+        return self._engine_method("influence")(dead=dead, **PRESETS[preset or "territory"])
+
+    def sgo_influence(self, *words):
+        """Private extension `sgo-influence [territory|area] [nodead]`: Bouzy's influence map of the position (include/sgo.h
+        "influence"; an estimate, not a proof) -- S lines of S characters from the top row down: X / O a live stone, b / w a point of
+        black / white territory, + / - black / white moyo beyond the territory, . neutral; then `estimate B+x.x black P white Q
+        neutral R komi K`.  territory (default) is the triple (5, 10, 21), area (4, 0, 0).  The stones unconditional life proves
+        dead are lifted first unless `nodead` is given."""
+        from .influence import format_board
+        v, stones = self._influence(words)
+        return format_board(v, stones, 0, float(self._komi))
+
+    def sgo_estimate(self, *words):
+        """Private extension `sgo-estimate [territory|area] [nodead]`: the score of `sgo-influence`'s estimate line alone, `B+x.x` /
+        `W+x.x` / `0` (live stones + territory, minus komi)."""
+        from .influence import score_text
+        v, _ = self._influence(words)
+        return score_text(v.estimate(0, float(self._komi)))
+
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
-               "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
+               "sgo-estimate": "sgo_estimate"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

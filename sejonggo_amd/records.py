@@ -4,6 +4,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
                                         [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt] [--moves]
+                                        [--influence]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -44,6 +45,11 @@ would do, keeps the row of the move that was played, and prints per bucket of --
 capture / give atari / escape (a chain with one liberty gets two or more) / are self-atari, each beside the mean share of the
 ALLOWED moves of the same positions that do -- what the players chose against what the board offered -- and the number of points
 the inherited legal-move rule forbids although the stone would stand, with the positions that had any.
+
+INFLUENCE (include/sgo.h "influence", csrc/sgo_influence.hip).  --influence reads Bouzy's dilation / erosion map of every position
+(the classical territory triple; the stones unconditional life proves dead lifted first) and prints per bucket of --bucket plies the
+mean |margin|, the mean number of neutral points and the mean moyo beyond territory per colour, and per game the estimate at the
+last position (before komi: a Record keeps none).  An estimate, not a proof.
 
 A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
 skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
@@ -376,6 +382,26 @@ class DeviceRecords(object):
                                                   P(sets), P(counts), self._lib.stream_ptr()), "sgo_life_dev")
         return sets, counts
 
+    def influence(self, index, dead=None, dilate=5, erode_moyo=10, erode_terr=21):
+        """(values int16 [n, N], sets int32 [n, 4, NW] holding the uint32 bit patterns, counts int32 [n, 8]) device tensors of the
+        listed records (sgo_influence_dev, one launch; include/sgo.h "influence"); an index outside the object gives the zero row.
+        dead "life": the stones sgo_life_dev proves dead are lifted first (one more launch and two mask operations on the device);
+        None: nothing is lifted; or a tensor / array [n, NW] of the rows' own."""
+        from .influence import check_params, dead_from_life, influence_dev
+        dilate, erode_moyo, erode_terr = check_params(dilate, erode_moyo, erode_terr)
+        if isinstance(dead, str) and dead != "life":
+            raise ValueError("influence: dead is None, \"life\" or an array of bitsets")
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        index = index.contiguous()
+        n = int(index.shape[0])
+        if isinstance(dead, str):
+            life_sets, _ = self.life(index)
+            ok = (index >= 0) & (index < self.cap)
+            planes = self.records[torch.where(ok, index, torch.zeros_like(index)).long(), :2 * self.NW]
+            dead = dead_from_life(life_sets, planes[:, :self.NW], planes[:, self.NW:]).contiguous()
+        return influence_dev(self.S, self.records, index, n, dead, dilate, erode_moyo, erode_terr, self.lib, self.rec_ptr, self.cap)
+
     def shapes(self, index, shape):
         """(hits int32 [n, 4], cover int32 [n, NW] holding the uint32 bit patterns) device tensors of the listed records for a
         shapes.Shape (sgo_shape_compile on the host, then sgo_shapes_dev, one launch; include/sgo.h "shape search"); an index
@@ -571,6 +597,21 @@ class RecordSet(object):
             index = self._record_index(ch)
             sets, counts = self.backend.life(index)
             ch.life = Life(self.S, _host(sets, np.uint32), _host(counts))
+            if stones:
+                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
+            yield ch
+
+    # ------------------------------------------------------------------ influence and territory estimate
+    def influence(self, dead="life", stones=False, dilate=5, erode_moyo=10, erode_terr=21):
+        """Generator of Chunks as `replay` gives them, each with `influence`, an influence.Influence with one row per RECORD of the
+        chunk (one backend call per chunk), rows as in `life`.  dead "life": the stones unconditional life proves dead are lifted
+        first; None: nothing is lifted.  Records that were not written give the zero row.  stones=True adds ch.stones as `tactics`
+        does."""
+        from .influence import Influence
+        for ch in self.replay():
+            index = self._record_index(ch)
+            values, sets, counts = self.backend.influence(index, dead, dilate, erode_moyo, erode_terr)
+            ch.influence = Influence(self.S, _host(values, np.int16), _host(sets, np.uint32), _host(counts))
             if stones:
                 ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
             yield ch
@@ -809,6 +850,30 @@ def life_lines(record_set):
     return out
 
 
+def influence_table(record_set, width=20, dead="life"):
+    """The figures of `--influence` from one RecordSet.influence pass (the classical territory triple).  {"buckets": [{"first_ply",
+    "positions", "abs_margin", "neutral", "moyo_beyond_black", "moyo_beyond_white"}] per `width` plies (ply 0 = the position before
+    the first entry): the means of |margin|, of neutral and of |moyo| - |territory| per colour; "games": [{"name", "plies",
+    "margin"}]: the margin (the estimate before komi; a Record keeps no komi) of the position after the last played entry}."""
+    sums, games = {}, []
+    for ch in record_set.influence(dead=dead):
+        v, base = ch.influence, 0
+        for i, g in enumerate(ch.games):
+            n = len(record_set.records[g].entries)
+            played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
+            rows = v.counts[base:base + played + 1].astype(np.int64)
+            for k in range(0, played + 1, width):
+                part = rows[k:k + width]
+                s = sums.setdefault(k // width, np.zeros(5, np.int64))
+                s += [len(part), int(np.abs(part[:, 7]).sum()), int(part[:, 6].sum()), int((part[:, 2] - part[:, 0]).sum()),
+                      int((part[:, 3] - part[:, 1]).sum())]
+            games.append({"name": record_set.records[g].name, "plies": played, "margin": int(rows[-1, 7])})
+            base += n + 1
+    buckets = [{"first_ply": b * width, "positions": int(s[0]), "abs_margin": float(s[1]) / int(s[0]), "neutral": float(s[2]) / int(s[0]),
+                "moyo_beyond_black": float(s[3]) / int(s[0]), "moyo_beyond_white": float(s[4]) / int(s[0])} for b, s in sorted(sums.items())]
+    return {"buckets": buckets, "games": games}
+
+
 def moves_table(record_set, width=20):
     """The table of `--moves` (moves.bucket_table) from one RecordSet.moves pass: per bucket of `width` moves the share of the played
     moves that capture / give atari / escape / are self-atari beside the mean share of the allowed moves of the same positions
@@ -877,6 +942,10 @@ def main(argv=None, out=sys.stdout):
                     help="per 20-move bucket: the share of the played moves that capture / give atari / escape / are self-atari beside "
                          "the mean share of the allowed moves of the same positions that do, and the points the inherited legal-move "
                          "rule forbids although the stone would stand")
+    ap.add_argument("--influence", action="store_true",
+                    help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
+                         "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
+                         "the last position")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -940,6 +1009,15 @@ def main(argv=None, out=sys.stdout):
                 out.write(format_bucket_table(doc["moves"]) + "\n")
             out.write("moves: forbidden-sound points %d in %d positions\n" % (
                 sum(r["forbidden_sound"] for r in doc["moves"]), sum(r["positions_forbidden"] for r in doc["moves"])))
+        if a.influence:
+            from .influence import score_text
+            doc["influence"] = influence_table(rs, a.bucket)
+            for d in doc["influence"]["buckets"]:
+                out.write("influence %d-%d positions %d  |margin| %.1f  neutral %.1f  moyo beyond territory black %.1f white %.1f\n" % (
+                    d["first_ply"], d["first_ply"] + a.bucket - 1, d["positions"], d["abs_margin"], d["neutral"], d["moyo_beyond_black"],
+                    d["moyo_beyond_white"]))
+            for d in doc["influence"]["games"]:
+                out.write("influence %s plies %d estimate %s\n" % (d["name"], d["plies"], score_text(d["margin"])))
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

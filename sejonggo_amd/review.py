@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt] [--moves]
+                                           [--find SHAPE.txt] [--moves] [--influence]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -24,7 +24,12 @@ first move after which it is gone again `disappears`.  --moves reads what one pl
 `captures N`, `atari` (it leaves an opponent chain next to it with one liberty), `escape` (a chain of the mover's with one liberty
 gets two or more), `self-atari` (two or more stones left with one liberty, nothing captured; a one-stone throw-in is not flagged) and
 `missed-capture K at V` (it captured nothing while V would have taken K >= 3 stones).  These are flags, not verdicts: one ply is
-looked at and nothing is read out.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+looked at and nothing is read out.  --influence reads Bouzy's influence map of every position of the record in one call
+(records.RecordSet.influence; include/sgo.h "influence"; the stones unconditional life proves dead are lifted first): each row gains
+`estimate` (live stones + territory of black minus white's, minus the record's komi, in front of the move) and `gain` (the change of
+that margin across the move in the mover's favour), and a last line names the three moves with the highest and the three with the
+lowest gain.  An estimate, and numbers, not verdicts.  Given without --sims, --net and --rollouts it searches nothing and loads no
+net: the lines then hold the move and the two figures only.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import json
 import string
@@ -294,8 +299,67 @@ def add_moves(rows, game, record_set=None):
     return rows
 
 
+def influence_rows(game, record_set, komi=0.0, dead="life"):
+    """{move number: {"estimate", "gain"}} of the B / W moves of `game` (influence.review_fields) from one RecordSet.influence pass
+    over a set that holds the game as its only record: the estimate in front of the move, and what the move did to the margin."""
+    from .influence import review_fields
+    out = {}
+    for ch in record_set.influence(dead=dead):
+        v, m = ch.influence, 0
+        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+            if is_setup:
+                continue
+            m += 1
+            if not ch.valid[e]:
+                continue
+            r = int(ch.index[e])
+            out[m] = review_fields(v, r, r + 1, int(colour), komi)
+    return out
+
+
+def add_influence(rows, game, record_set=None, komi=None):
+    """Adds `estimate` (Bouzy's area-score estimate of the position in front of the move, proved-dead stones lifted, minus komi;
+    positive = black) and `gain` (the change of the margin across the move in the mover's favour) to every row of a review.
+    komi None: the record's, 0 when it has none.  record_set None: a device RecordSet of the game.  Numbers, not verdicts."""
+    from .records import Record, RecordSet
+    own = record_set is None
+    if own:
+        entries = [(int(a), int(c)) for a, c in game.moves]
+        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    if komi is None:
+        komi = game.komi if game.komi is not None else 0.0
+    try:
+        found = influence_rows(game, record_set, komi)
+    finally:
+        if own:
+            record_set.close()
+    for row in rows:
+        d = found.get(row["move_number"])
+        if d is not None:
+            row["estimate"], row["gain"] = d["estimate"], d["gain"]
+    return rows
+
+
+def influence_summary(rows, top=3):
+    """`influence: highest gain M (+g) ...; lowest gain M (-g) ...` of the rows add_influence filled"""
+    from .influence import review_summary
+    gains = {row["move_number"]: row.get("gain") for row in rows}
+    best, worst = review_summary(sorted(gains.items()), top)
+    part = lambda ms: " ".join("%d (%+d)" % (m, gains[m]) for m in ms) or "-"            # noqa: E731
+    return "influence: highest gain %s; lowest gain %s" % (part(best), part(worst))
+
+
+def bare_rows(game, every=1):
+    """the rows of a review without a search: move_number, colour, played"""
+    return [{"move_number": m, "colour": "B" if colour > 0 else "W", "played": vertex(played, game.size)}
+            for m, _, (played, colour) in positions_of(game, every)]
+
+
 def format_row(row):
     text = _format_row(row)
+    if row.get("estimate") is not None:
+        from .influence import score_text
+        text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
         list(row.get("moves_flags") or [])
     if flags:
@@ -309,6 +373,8 @@ def _format_row(row):
     if "error" in row:
         return "%4d %s %-4s  set-up refused (%d at entry %d)" % (row["move_number"], row["colour"], row["played"], row["error"],
                                                                  row["fail_at"])
+    if "top" not in row:                                    # a review without a search (bare_rows)
+        return "%4d %s %-4s" % (row["move_number"], row["colour"], row["played"])
     pv = " ".join(row["top"][0]["pv"]) if row["top"] else ""
     text = "%4d %s %-4s share %5.1f%% mean %+.4f  best %-4s mean %+.4f  pv %s" % (
         row["move_number"], row["colour"], row["played"], 100.0 * row["played_share"], row["played_mean"], row["best"],
@@ -343,8 +409,12 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--every", type=int, default=1, help="review every k-th position")
     ap.add_argument("--top", type=int, default=3)
     ap.add_argument("--depth", type=int, default=8)
-    ap.add_argument("--net", default="best", choices=["best", "hash", "uniform"],
-                    help="best: the model the configuration names; hash / uniform: the stub nets (no weights needed)")
+    ap.add_argument("--net", default=None, choices=["best", "hash", "uniform"],
+                    help="best (default): the model the configuration names; hash / uniform: the stub nets (no weights needed)")
+    ap.add_argument("--influence", action="store_true",
+                    help="per move: Bouzy's estimate in front of it (proved-dead stones lifted, minus the record's komi) and the gain "
+                         "of the margin across it; a summary of the three highest and lowest gains.  Given without --sims, --net "
+                         "and --rollouts, nothing is searched and no net is loaded")
     ap.add_argument("--energy", type=int, default=None)
     ap.add_argument("--games", type=int, default=None, help="session slots = positions per chunk (default: as many as reviewed, at most 1024)")
     ap.add_argument("--symmetry", default="random1", choices=["random1", "avg8", "identity"])
@@ -360,19 +430,25 @@ def main(argv=None, out=sys.stdout):
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
+    # --influence with nothing that asks for a search or a net: the record kernels alone
+    searched = not (a.influence and a.sims is None and a.net is None and not a.rollouts)
+    a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
     n_pos = len(positions_of(game, a.every))
-    net = _net(a.net, game.size)
-    eng = SessionEngine(net, size=game.size, n_games=a.games or max(1, min(1024, n_pos)), sims=sims, energy=energy,
-                        komi=game.komi if game.komi is not None else conf['KOMI'], symmetry=a.symmetry)
-    try:
-        rows = review(eng, game, sims=sims, every=a.every, top=a.top, depth=a.depth, rollouts=a.rollouts, komi=eng.komi)
-    finally:
-        eng.close()
-        if a.net == "best":
-            from .predicting_queue_worker import destroy_predicting_workers
-            destroy_predicting_workers(conf['GPUs'][:1])
+    net = _net(a.net, game.size) if searched else None
+    if searched:
+        eng = SessionEngine(net, size=game.size, n_games=a.games or max(1, min(1024, n_pos)), sims=sims, energy=energy,
+                            komi=game.komi if game.komi is not None else conf['KOMI'], symmetry=a.symmetry)
+        try:
+            rows = review(eng, game, sims=sims, every=a.every, top=a.top, depth=a.depth, rollouts=a.rollouts, komi=eng.komi)
+        finally:
+            eng.close()
+            if a.net == "best":
+                from .predicting_queue_worker import destroy_predicting_workers
+                destroy_predicting_workers(conf['GPUs'][:1])
+    else:
+        rows, sims, energy = bare_rows(game, a.every), 0, 0
     if a.tactics:
         add_tactics(rows, game)
     if a.life:
@@ -383,11 +459,16 @@ def main(argv=None, out=sys.stdout):
             add_find(rows, game, Shape.parse(f.read()))
     if a.moves:
         add_moves(rows, game)
+    if a.influence:
+        add_influence(rows, game)
     for row in rows:
         out.write(format_row(row) + "\n")
+    if a.influence:
+        out.write(influence_summary(rows) + "\n")
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net), a.rollouts), f, indent=1, sort_keys=True)
+            json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net) if searched else None, a.rollouts), f, indent=1,
+                      sort_keys=True)
             f.write("\n")
     return 0
 
