@@ -1,0 +1,57 @@
+// sgo_analysis.hpp -- what the six position analyses (keys, tactics, life, shapes, moves, influence) share on the host: the record
+// launchers of their translation units, which sgo_session.hip runs over the context's root records, and the one body of their
+// host entries sgo_X.  Host code only; every kernel stays in its own file.
+#pragma once
+#include "sgo_common.hpp"
+
+namespace sgo {
+
+// The record launchers: n listed records (d_index == nullptr: record i) of d_records; every pointer is device memory.
+int launch_keys(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
+                uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_action, hipStream_t st);
+int launch_tactics(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int max_chains, uint8_t *d_libs,
+                   int32_t *d_n_chains, int32_t *d_chains, hipStream_t st);
+int launch_life(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
+                hipStream_t st);
+int launch_shapes(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_table,
+                  int32_t *d_hits, uint32_t *d_cover, hipStream_t st);
+int launch_moves(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_moves,
+                 int32_t *d_counts, hipStream_t st);
+int launch_influence(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_dead, int dilate,
+                     int erode_moyo, int erode_terr, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st);
+
+// The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
+// (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip).
+int session_shape_table(int S, const sgo_shape *shape, uint32_t *table);
+bool influence_params_ok(int dilate, int erode_moyo, int erode_terr);
+
+// One array of a host entry's device block.  `up` (or nullptr) is copied in before the launch, `down` (or nullptr) is filled
+// from it afterwards; an array with neither is only room.
+struct HostArray {
+    size_t bytes;
+    const void *up;
+    void *down;
+};
+
+// The body of a host entry sgo_X: one hipMalloc holds the arrays (each on a 16-byte boundary) and the records behind them,
+// launch(d_records, d) runs on the null stream with d[k] the device address of a[k], the outputs come down, hipFree.
+template <size_t NA, class Launch>
+int host_entry(const char *who, const uint32_t *records, size_t record_bytes, const HostArray (&a)[NA], Launch launch) {
+    size_t off[NA], at = 0;
+    for (size_t k = 0; k < NA; k++) { off[k] = at; at += (a[k].bytes + 15) & ~(size_t)15; }
+    uint8_t *d = nullptr, *p[NA];
+    SGO_HIP(hipMalloc((void **)&d, at + record_bytes));
+    for (size_t k = 0; k < NA; k++) p[k] = d + off[k];
+    int rc = SGO_OK;
+    hipError_t e = hipMemcpy(d + at, records, record_bytes, hipMemcpyHostToDevice);
+    for (size_t k = 0; k < NA; k++)
+        if (e == hipSuccess && a[k].up) e = hipMemcpy(p[k], a[k].up, a[k].bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = launch(reinterpret_cast<const uint32_t *>(d + at), p);
+    for (size_t k = 0; k < NA; k++)
+        if (e == hipSuccess && rc == SGO_OK && a[k].down) e = hipMemcpy(a[k].down, p[k], a[k].bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(e, who, __FILE__, __LINE__);
+    return rc;
+}
+
+}  // namespace sgo

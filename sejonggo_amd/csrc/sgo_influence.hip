@@ -19,6 +19,7 @@
 // Everything lives in registers: no LDS, no scratch, no atomics.
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
 #include "sgo_rows.hpp"
@@ -123,27 +124,17 @@ __global__ __launch_bounds__(64) void k_influence(int n, const uint32_t *__restr
     }
 }
 
-static bool influence_params_ok(int dilate, int erode_moyo, int erode_terr) {
+bool influence_params_ok(int dilate, int erode_moyo, int erode_terr) {
     return dilate >= 0 && dilate <= SGO_INFLUENCE_MAX_DILATE && erode_moyo >= 0 && erode_terr >= 0 && erode_terr <= SGO_INFLUENCE_MAX_ERODE &&
            erode_moyo <= erode_terr;
 }
 
-static int launch_influence(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_dead, int dilate,
-                            int erode_moyo, int erode_terr, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st) {
+int launch_influence(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_dead, int dilate,
+                     int erode_moyo, int erode_terr, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st) {
     SGO_DISPATCH(S, k_influence<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, d_dead, dilate, erode_moyo,
                                                                          erode_terr, d_values, d_sets, d_counts));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
-}
-
-// sgo_session_influence's check and launches (csrc/sgo_session.hip stages the slots and the dead sets and copies the rows back);
-// every pointer is device memory
-bool session_influence_params_ok(int dilate, int erode_moyo, int erode_terr) { return influence_params_ok(dilate, erode_moyo, erode_terr); }
-int launch_session_influence(const Ctx &c, int n, const int32_t *d_slots, const uint32_t *d_dead, int dilate, int erode_moyo, int erode_terr,
-                             int32_t *d_status, int32_t *d_index, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    return launch_influence(c.S, n, c.pos, ctx_records(c), d_index, d_dead, dilate, erode_moyo, erode_terr, d_values, d_sets, d_counts, st);
 }
 
 }  // namespace sgo
@@ -173,27 +164,13 @@ int sgo_influence(int S, int n, const uint32_t *records, const uint32_t *dead, i
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    // one block: records | dead | sets | counts | values.  Every row is written whole, so nothing of the caller's goes in.
-    const size_t NW = (size_t)sgo_plane_words(S);
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), db = (size_t)n * NW * sizeof(uint32_t), sb = 4 * db;
-    const size_t cb = (size_t)n * 8 * sizeof(int32_t), vb = (size_t)n * S * S * sizeof(int16_t);
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, rb + db + sb + cb + vb));
-    uint32_t *d_dead = reinterpret_cast<uint32_t *>(d + rb), *d_sets = reinterpret_cast<uint32_t *>(d + rb + db);
-    int32_t *d_counts = reinterpret_cast<int32_t *>(d + rb + db + sb);
-    int16_t *d_values = reinterpret_cast<int16_t *>(d + rb + db + sb + cb);
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && dead) e = hipMemcpy(d_dead, dead, db, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = launch_influence(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, dead ? d_dead : nullptr, dilate, erode_moyo, erode_terr,
-                              d_values, d_sets, d_counts, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(sets, d_sets, sb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(values, d_values, vb, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_influence", __FILE__, __LINE__);
-    return rc;
+    // every row is written whole, so nothing of the caller's goes in
+    const size_t db = (size_t)n * sgo_plane_words(S) * sizeof(uint32_t);
+    const HostArray a[] = {{db, dead, nullptr}, {4 * db, nullptr, sets}, {(size_t)n * 8 * sizeof(int32_t), nullptr, counts}, {(size_t)n * S * S * sizeof(int16_t), nullptr, values}};
+    return host_entry("sgo_influence", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_influence(S, n, d_records, n, nullptr, dead ? reinterpret_cast<const uint32_t *>(d[0]) : nullptr, dilate, erode_moyo, erode_terr,
+                                reinterpret_cast<int16_t *>(d[3]), reinterpret_cast<uint32_t *>(d[1]), reinterpret_cast<int32_t *>(d[2]), nullptr);
+    });
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //
 //   k_keys<S, INLINE>     per listed record: key0, canon, mask, canon_action
 //
-// sgo_session_keys runs the same kernel over the context's records, with the root index k_session_roots (sgo_session.hpp) writes.
+// sgo_session_keys runs the same launcher over the context's records, with the root index k_session_roots (sgo_session.hpp) writes.
 //
 // Kernel form: one 32-lane HALF of a wavefront per record, one board row per lane (sgo_rows.hpp load_row), as k_records_score.
 // A record gives 2 of its 16 planes; they are read in place through the index list, no record is copied.  Each lane walks the
@@ -15,12 +15,13 @@
 //
 // z comes from a table z[2][N] in LDS (5.8 KB at 19x19), written once per 256-thread workgroup, which then strides over the
 // records (INLINE = false, the product), or is computed where it is needed (INLINE = true: eight splitmix rounds per stone;
-// sgo_keys_mode selects it for A/B timing, and the few rows of sgo_session_keys use it: no table to fill).  Same bits either way.
+// sgo_keys_mode selects it for A/B timing).  Same bits either way.
 //
 // Nothing branches around a shuffle on a per-record condition: a half whose row is out of range or does not exist reads no
 // stones and only its final stores differ.
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_rows.hpp"
 
@@ -149,8 +150,8 @@ __global__ __launch_bounds__(256) void k_keys(int n, const uint32_t *records, in
 
 static int g_keys_mode = 0;       // 0: the LDS table, 1: splitmix inline
 
-static int launch_keys(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
-                       uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_action, hipStream_t st) {
+int launch_keys(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_target,
+                uint64_t *d_key0, uint64_t *d_canon, int32_t *d_mask, int32_t *d_action, hipStream_t st) {
     const int blocks = cdiv(n, 8) < 4096 ? cdiv(n, 8) : 4096;
     if (g_keys_mode == 1) {
         SGO_DISPATCH(S, k_keys<kS, true><<<dim3(blocks), dim3(256), 0, st>>>(n, d_records, n_records, d_index, d_target, d_key0, d_canon,
@@ -159,20 +160,6 @@ static int launch_keys(int S, int n, const uint32_t *d_records, int n_records, c
         SGO_DISPATCH(S, k_keys<kS, false><<<dim3(blocks), dim3(256), 0, st>>>(n, d_records, n_records, d_index, d_target, d_key0, d_canon,
                                                                                d_mask, d_action));
     }
-    SGO_HIP(hipGetLastError());
-    return SGO_OK;
-}
-
-// sgo_session_keys' launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory.
-// k_session_roots names the root records, k_keys reads them in place from the context's blocks -- in the inline form whatever
-// sgo_keys_mode says: no table is worth filling for these few rows.  A refused slot (index -1) gets the zero row.
-int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint64_t *d_key0,
-                        uint64_t *d_canon, int32_t *d_mask, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    const int blocks = cdiv(n, 8) < 4096 ? cdiv(n, 8) : 4096;
-    SGO_DISPATCH(c.S, k_keys<kS, true><<<dim3(blocks), dim3(256), 0, st>>>(n, c.pos, ctx_records(c), d_index, nullptr, d_key0, d_canon,
-                                                                           d_mask, nullptr));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
 }
@@ -206,25 +193,12 @@ int sgo_keys(int S, int n, const uint32_t *records, const int32_t *target, uint6
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    // one block: records | key0 | canon | mask | target | action
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), kb = (size_t)n * sizeof(uint64_t), ib = (size_t)n * sizeof(int32_t);
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, rb + 2 * kb + 3 * ib));
-    uint64_t *d_key0 = reinterpret_cast<uint64_t *>(d + rb), *d_canon = d_key0 + n;
-    int32_t *d_mask = reinterpret_cast<int32_t *>(d + rb + 2 * kb), *d_target = d_mask + n, *d_action = d_target + n;
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && target) e = hipMemcpy(d_target, target, ib, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = launch_keys(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, target ? d_target : nullptr, d_key0, d_canon, d_mask,
-                         d_action, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(key0, d_key0, kb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(canon, d_canon, kb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(mask, d_mask, ib, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK && target) e = hipMemcpy(canon_action, d_action, ib, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_keys", __FILE__, __LINE__);
-    return rc;
+    const size_t kb = (size_t)n * sizeof(uint64_t), ib = (size_t)n * sizeof(int32_t);
+    const HostArray a[] = {{kb, nullptr, key0}, {kb, nullptr, canon}, {ib, nullptr, mask}, {ib, target, nullptr}, {ib, nullptr, target ? canon_action : nullptr}};
+    return host_entry("sgo_keys", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_keys(S, n, d_records, n, nullptr, target ? reinterpret_cast<const int32_t *>(d[3]) : nullptr, reinterpret_cast<uint64_t *>(d[0]),
+                           reinterpret_cast<uint64_t *>(d[1]), reinterpret_cast<int32_t *>(d[2]), reinterpret_cast<int32_t *>(d[4]), nullptr);
+    });
 }
 
 }  // extern "C"

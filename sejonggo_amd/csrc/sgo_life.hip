@@ -13,6 +13,7 @@
 // or shuffle sits under a per-half branch.  Everything lives in registers: no LDS, no scratch.
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
 #include "sgo_rows.hpp"
@@ -109,19 +110,11 @@ __global__ __launch_bounds__(64) void k_life(int n, const uint32_t *records, int
     }
 }
 
-static int launch_life(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
-                       hipStream_t st) {
+int launch_life(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, uint32_t *d_sets, int32_t *d_counts,
+                hipStream_t st) {
     SGO_DISPATCH(S, k_life<kS><<<dim3(n), dim3(64), 0, st>>>(n, d_records, n_records, d_index, d_sets, d_counts));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
-}
-
-// sgo_session_life's launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
-int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint32_t *d_sets,
-                        int32_t *d_counts, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    return launch_life(c.S, n, c.pos, ctx_records(c), d_index, d_sets, d_counts, st);
 }
 
 }  // namespace sgo
@@ -146,21 +139,11 @@ int sgo_life(int S, int n, const uint32_t *records, uint32_t *sets, int32_t *cou
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    // one block: records | sets | counts.  Every row is written whole, so nothing of the caller's goes in.
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), sb = (size_t)n * 4 * sgo_plane_words(S) * sizeof(uint32_t);
-    const size_t cb = (size_t)n * 8 * sizeof(int32_t);
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, rb + sb + cb));
-    uint32_t *d_sets = reinterpret_cast<uint32_t *>(d + rb);
-    int32_t *d_counts = reinterpret_cast<int32_t *>(d + rb + sb);
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = launch_life(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, d_sets, d_counts, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(sets, d_sets, sb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_life", __FILE__, __LINE__);
-    return rc;
+    // every row is written whole, so nothing of the caller's goes in
+    const HostArray a[] = {{(size_t)n * 4 * sgo_plane_words(S) * sizeof(uint32_t), nullptr, sets}, {(size_t)n * 8 * sizeof(int32_t), nullptr, counts}};
+    return host_entry("sgo_life", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_life(S, n, d_records, n, nullptr, reinterpret_cast<uint32_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), nullptr);
+    });
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 // lives in registers: no LDS, no scratch, no atomics (the counts are ballots and half_sum).
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
 #include "sgo_rows.hpp"
@@ -160,20 +161,12 @@ __global__ __launch_bounds__(64) void k_moves(int n, const uint32_t *records, in
     }
 }
 
-static int launch_moves(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_moves,
-                        int32_t *d_counts, hipStream_t st) {
+int launch_moves(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_moves,
+                 int32_t *d_counts, hipStream_t st) {
     SGO_DISPATCH(S, k_moves<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, side,
                                                                          reinterpret_cast<moves_u32x4 *>(d_moves), d_counts));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
-}
-
-// sgo_session_moves' launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
-int launch_session_moves(const Ctx &c, int n, const int32_t *d_slots, int side, int32_t *d_status, int32_t *d_index, int16_t *d_moves,
-                         int32_t *d_counts, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    return launch_moves(c.S, n, c.pos, ctx_records(c), d_index, side, d_moves, d_counts, st);
 }
 
 }  // namespace sgo
@@ -200,22 +193,11 @@ int sgo_moves(int S, int n, const uint32_t *records, int side, int16_t *moves, i
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    // one block: moves | counts | records.  Every row is written whole, so nothing of the caller's goes in.
-    const size_t mb = (size_t)n * S * S * 8 * sizeof(int16_t), cb = (size_t)n * 8 * sizeof(int32_t);
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t);
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, mb + cb + rb));
-    int16_t *d_moves = reinterpret_cast<int16_t *>(d);
-    int32_t *d_counts = reinterpret_cast<int32_t *>(d + mb);
-    uint32_t *d_rec = reinterpret_cast<uint32_t *>(d + mb + cb);
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d_rec, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = launch_moves(S, n, d_rec, n, nullptr, side, d_moves, d_counts, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(moves, d_moves, mb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_moves", __FILE__, __LINE__);
-    return rc;
+    // every row is written whole, so nothing of the caller's goes in
+    const HostArray a[] = {{(size_t)n * S * S * 8 * sizeof(int16_t), nullptr, moves}, {(size_t)n * 8 * sizeof(int32_t), nullptr, counts}};
+    return host_entry("sgo_moves", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_moves(S, n, d_records, n, nullptr, side, reinterpret_cast<int16_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), nullptr);
+    });
 }
 
 }  // extern "C"

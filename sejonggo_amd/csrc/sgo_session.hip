@@ -3,41 +3,22 @@
 // sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
 // sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip) and of
 // sgo_session_influence ("influence"; sgo_influence.hip).
-// Those six and sgo_rollout_start_sessions
-// (sgo_rollout.hip) find the root records of the listed slots with launch_session_roots below and run their ordinary record
-// kernels over the context's blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
+// Those six (session_rows below, over the launchers of sgo_analysis.hpp) and sgo_rollout_start_sessions (sgo_rollout.hip) find
+// the root records of the listed slots with launch_session_roots below and run their ordinary record kernels over the context's
+// blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
 // SejongGoEngine a GTP front-end drives.
 #include <string.h>
+#include <functional>
 #include <vector>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_session.hpp"
 
 using namespace sgo;
 
 namespace sgo {
-// csrc/sgo_keys.hip: k_session_roots and k_keys on device pointers
-int launch_session_keys(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint64_t *d_key0,
-                        uint64_t *d_canon, int32_t *d_mask, hipStream_t st);
-// csrc/sgo_tactics.hip: k_session_roots, k_tactics_chains and k_tactics_read on device pointers
-int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
-                           int32_t *d_n_chains, int32_t *d_chains, hipStream_t st);
-// csrc/sgo_life.hip: k_session_roots and k_life on device pointers
-int launch_session_life(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, uint32_t *d_sets,
-                        int32_t *d_counts, hipStream_t st);
-// csrc/sgo_shapes.hip: the checked table of a shape (host), and k_session_roots and k_shapes on device pointers
-int session_shape_table(int S, const sgo_shape *shape, uint32_t *table);
-int launch_session_shapes(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, const uint32_t *d_table,
-                          int32_t *d_hits, uint32_t *d_cover, hipStream_t st);
-// csrc/sgo_moves.hip: k_session_roots and k_moves on device pointers
-int launch_session_moves(const Ctx &c, int n, const int32_t *d_slots, int side, int32_t *d_status, int32_t *d_index, int16_t *d_moves,
-                         int32_t *d_counts, hipStream_t st);
-// csrc/sgo_influence.hip: the parameter check (host), and k_session_roots and k_influence on device pointers
-bool session_influence_params_ok(int dilate, int erode_moyo, int erode_terr);
-int launch_session_influence(const Ctx &c, int n, const int32_t *d_slots, const uint32_t *d_dead, int dilate, int erode_moyo, int erode_terr,
-                             int32_t *d_status, int32_t *d_index, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st);
-
 int launch_session_roots(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, hipStream_t st) {
     k_session_roots<<<dim3(cdiv(n, 64)), dim3(64), 0, st>>>(c, n, d_slots, d_status, d_index);
     SGO_HIP(hipGetLastError());
@@ -101,8 +82,8 @@ static int session_buffer(sgo_ctx *x, size_t bytes) {
     return SGO_OK;
 }
 
-// The shared opening of sgo_session_report, _keys, _tactics, _life, _shapes and _moves (readers: a slot may be listed twice): the list is checked against
-// the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
+// The shared opening of sgo_session_report and of session_rows below (readers: a slot may be listed twice): the list is checked
+// against the context, the device set, the session buffer grown to `bytes`, and the slots staged in its first al8(4 n) bytes.
 static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t *slots, size_t bytes, hipStream_t st) {
     const Ctx &c = x->c;
     if (n > c.G) { set_error(std::string(who) + ": more slots than the context has"); return SGO_ERR_ARG; }
@@ -113,6 +94,56 @@ static int stage_session_list(sgo_ctx *x, const char *who, int n, const int32_t 
     if (rc != SGO_OK) return rc;
     memcpy(x->h.sess_h, slots, sizeof(int32_t) * n);
     SGO_HIP(hipMemcpyAsync(x->h.sess_d, x->h.sess_h, al8(sizeof(int32_t) * (size_t)n), hipMemcpyHostToDevice, st));
+    return SGO_OK;
+}
+
+// One output column of a session analysis: `row` bytes per listed slot in the caller's array `dst`, the device column on an
+// `align`-byte boundary (8 at the least).  Where a kernel leaves the end of a row unwritten, `stored(i)` gives the bytes of row i
+// to copy; it runs after the columns before it have their row i.
+struct RowCol {
+    void *dst;
+    size_t row, align;
+    std::function<size_t(int)> stored;
+};
+
+// The body of the six session analyses (keys, tactics, life, shapes, moves, influence).  The session buffer is laid out as
+//     slots | input | record index | status | columns
+// the slots (and `input`, where there is one: a shape table, the dead sets) go up, k_session_roots names the root records,
+// launch(d_index, d_input, d_cols) runs the ordinary record launcher over the context's blocks, and everything behind the index
+// comes back in ONE copy.  A refused slot keeps its status; its rows stay as the caller filled them.
+template <size_t NC, class Launch>
+static int session_rows(sgo_ctx *x, const char *who, int n, const int32_t *slots, const void *input, size_t input_bytes, int32_t *status,
+                        const RowCol (&cols)[NC], hipStream_t st, Launch launch) {
+    const size_t ib = al8(sizeof(int32_t) * (size_t)n), xo = ib + (input ? al8(input_bytes) : 0), so = xo + ib;
+    size_t off[NC], end = so + ib;
+    for (size_t k = 0; k < NC; k++) {
+        const size_t a = cols[k].align < 8 ? 8 : cols[k].align;
+        off[k] = (end + a - 1) & ~(a - 1);
+        end = off[k] + cols[k].row * n;
+    }
+    int rc = stage_session_list(x, who, n, slots, end, st);
+    if (rc != SGO_OK) return rc;
+    uint8_t *h = x->h.sess_h, *d = x->h.sess_d, *dc[NC];
+    for (size_t k = 0; k < NC; k++) dc[k] = d + off[k];
+    if (input) {
+        memcpy(h + ib, input, input_bytes);
+        SGO_HIP(hipMemcpyAsync(d + ib, h + ib, input_bytes, hipMemcpyHostToDevice, st));
+    }
+    int32_t *d_index = reinterpret_cast<int32_t *>(d + xo);
+    rc = launch_session_roots(x->c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + so), d_index, st);
+    if (rc == SGO_OK) rc = launch(d_index, input ? d + ib : nullptr, dc);
+    if (rc != SGO_OK) return rc;
+    SGO_HIP(hipMemcpyAsync(h + so, d + so, end - so, hipMemcpyDeviceToHost, st));
+    SGO_HIP(hipStreamSynchronize(st));
+    const int32_t *hs = reinterpret_cast<const int32_t *>(h + so);
+    for (int i = 0; i < n; i++) {
+        status[i] = hs[i];
+        if (hs[i] != SGO_OK) continue;
+        for (size_t k = 0; k < NC; k++) {
+            const RowCol &col = cols[k];
+            memcpy(static_cast<uint8_t *>(col.dst) + col.row * i, h + off[k] + col.row * i, col.stored ? col.stored(i) : col.row);
+        }
+    }
     return SGO_OK;
 }
 
@@ -254,29 +285,13 @@ int sgo_session_keys(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, u
                      void *stream) {
     if (!x || n < 0 || (n && (!slots || !status || !key0 || !canon || !mask))) { set_error("sgo_session_keys: bad argument"); return SGO_ERR_ARG; }
     if (n == 0) return SGO_OK;
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    // slots | record index | status | mask | key0 | canon; everything behind the index comes back in one copy
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), kb = sizeof(uint64_t) * (size_t)n;
-    const int rc = stage_session_list(x, "sgo_session_keys", n, slots, 4 * ib + 2 * kb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    const int lrc = launch_session_keys(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + 2 * ib),
-                                        reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<uint64_t *>(d + 4 * ib),
-                                        reinterpret_cast<uint64_t *>(d + 4 * ib + kb), reinterpret_cast<int32_t *>(d + 3 * ib), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, 2 * ib + 2 * kb, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hm = reinterpret_cast<const int32_t *>(h + 3 * ib);
-    const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + 4 * ib), *hc = hk + n;
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        key0[i] = hk[i];
-        canon[i] = hc[i];
-        mask[i] = hm[i];
-    }
-    return SGO_OK;
+    const RowCol cols[] = {{mask, sizeof(int32_t), 4}, {key0, sizeof(uint64_t), 8}, {canon, sizeof(uint64_t), 8}};
+    return session_rows(x, "sgo_session_keys", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_keys(c.S, n, c.pos, ctx_records(c), d_index, nullptr, reinterpret_cast<uint64_t *>(d[1]), reinterpret_cast<uint64_t *>(d[2]),
+                           reinterpret_cast<int32_t *>(d[0]), nullptr, st);
+    });
 }
 
 int sgo_session_tactics(sgo_ctx *x, int n, const int32_t *slots, int max_chains, int32_t *status, uint8_t *libs, int32_t *n_chains,
@@ -286,96 +301,46 @@ int sgo_session_tactics(sgo_ctx *x, int n, const int32_t *slots, int max_chains,
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    // slots | record index | status | n_chains | chains | libs; everything behind the index comes back in one copy
-    const int N = c.S * c.S;
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)max_chains * n, lb = al8((size_t)n * N);
-    const int rc = stage_session_list(x, "sgo_session_tactics", n, slots, 4 * ib + cb + lb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    const int lrc = launch_session_tactics(c, n, reinterpret_cast<const int32_t *>(d), max_chains, reinterpret_cast<int32_t *>(d + 2 * ib),
-                                           reinterpret_cast<int32_t *>(d + ib), d + 4 * ib + cb, reinterpret_cast<int32_t *>(d + 3 * ib),
-                                           reinterpret_cast<int32_t *>(d + 4 * ib), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, 2 * ib + cb + lb, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hn = reinterpret_cast<const int32_t *>(h + 3 * ib);
-    const int32_t *hc = reinterpret_cast<const int32_t *>(h + 4 * ib);
-    const uint8_t *hl = h + 4 * ib + cb;
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        n_chains[i] = hn[i];
-        memcpy(libs + (size_t)i * N, hl + (size_t)i * N, N);
-        const int stored = hn[i] < max_chains ? hn[i] : max_chains;   // the chain rows behind them were not written
-        memcpy(chains + (size_t)i * max_chains * 8, hc + (size_t)i * max_chains * 8, sizeof(int32_t) * 8 * (size_t)stored);
-    }
-    return SGO_OK;
+    const size_t chain = sizeof(int32_t) * 8;
+    // the chain rows behind min(n_chains, max_chains) were not written; n_chains stands before them, so its row is scattered first
+    const RowCol cols[] = {{n_chains, sizeof(int32_t), 4},
+                           {chains, chain * max_chains, 4, [=](int i) { return chain * (n_chains[i] < max_chains ? n_chains[i] : max_chains); }},
+                           {libs, (size_t)c.S * c.S, 1}};
+    return session_rows(x, "sgo_session_tactics", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_tactics(c.S, n, c.pos, ctx_records(c), d_index, max_chains, d[2], reinterpret_cast<int32_t *>(d[0]),
+                              reinterpret_cast<int32_t *>(d[1]), st);
+    });
 }
 
 int sgo_session_life(sgo_ctx *x, int n, const int32_t *slots, int32_t *status, uint32_t *sets, int32_t *counts, void *stream) {
     if (!x || n < 0 || (n && (!slots || !status || !sets || !counts))) { set_error("sgo_session_life: bad argument"); return SGO_ERR_ARG; }
     if (n == 0) return SGO_OK;
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    // slots | record index | status | counts | sets; everything behind the index comes back in one copy
-    const size_t NW = (size_t)sgo_plane_words(c.S);
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n, sb = sizeof(uint32_t) * 4 * NW * (size_t)n;
-    const int rc = stage_session_list(x, "sgo_session_life", n, slots, 3 * ib + cb + sb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    const int lrc = launch_session_life(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + 2 * ib),
-                                        reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<uint32_t *>(d + 3 * ib + cb),
-                                        reinterpret_cast<int32_t *>(d + 3 * ib), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, ib + cb + sb, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hc = reinterpret_cast<const int32_t *>(h + 3 * ib);
-    const uint32_t *hw = reinterpret_cast<const uint32_t *>(h + 3 * ib + cb);
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
-        memcpy(sets + (size_t)i * 4 * NW, hw + (size_t)i * 4 * NW, sizeof(uint32_t) * 4 * NW);
-    }
-    return SGO_OK;
+    const RowCol cols[] = {{counts, sizeof(int32_t) * 8, 4}, {sets, sizeof(uint32_t) * 4 * sgo_plane_words(c.S), 4}};
+    return session_rows(x, "sgo_session_life", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_life(c.S, n, c.pos, ctx_records(c), d_index, reinterpret_cast<uint32_t *>(d[1]), reinterpret_cast<int32_t *>(d[0]), st);
+    });
 }
 
 int sgo_session_shapes(sgo_ctx *x, int n, const int32_t *slots, const sgo_shape *shape, int32_t *status, int32_t *hits, uint32_t *cover,
                        void *stream) {
     if (!x || n < 0 || !shape || (n && (!slots || !status || !hits || !cover))) { set_error("sgo_session_shapes: bad argument"); return SGO_ERR_ARG; }
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     uint32_t table[SGO_SHAPE_TABLE_WORDS];
     const int crc = session_shape_table(c.S, shape, table);
     if (crc != SGO_OK) return crc;
     if ((int)table[0] != c.S) { set_error("sgo_session_shapes: the table was compiled for another size"); return SGO_ERR_ARG; }
     if (n == 0) return SGO_OK;
     hipStream_t st = (hipStream_t)stream;
-    // slots | table | record index | status | hits | cover; everything behind the index comes back in one copy
-    const size_t NW = (size_t)sgo_plane_words(c.S);
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), tb = sizeof(table), hb = sizeof(int32_t) * 4 * (size_t)n, cb = sizeof(uint32_t) * NW * (size_t)n;
-    const int rc = stage_session_list(x, "sgo_session_shapes", n, slots, 3 * ib + tb + hb + cb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    memcpy(h + ib, table, tb);
-    SGO_HIP(hipMemcpyAsync(d + ib, h + ib, tb, hipMemcpyHostToDevice, st));
-    const size_t so = 2 * ib + tb, ho = so + ib, co = ho + hb;
-    const int lrc = launch_session_shapes(c, n, reinterpret_cast<const int32_t *>(d), reinterpret_cast<int32_t *>(d + so),
-                                          reinterpret_cast<int32_t *>(d + ib + tb), reinterpret_cast<const uint32_t *>(d + ib),
-                                          reinterpret_cast<int32_t *>(d + ho), reinterpret_cast<uint32_t *>(d + co), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + so, d + so, ib + hb + cb, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + so), *hh = reinterpret_cast<const int32_t *>(h + ho);
-    const uint32_t *hc = reinterpret_cast<const uint32_t *>(h + co);
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        memcpy(hits + (size_t)i * 4, hh + (size_t)i * 4, sizeof(int32_t) * 4);
-        memcpy(cover + (size_t)i * NW, hc + (size_t)i * NW, sizeof(uint32_t) * NW);
-    }
-    return SGO_OK;
+    const RowCol cols[] = {{hits, sizeof(int32_t) * 4, 4}, {cover, sizeof(uint32_t) * sgo_plane_words(c.S), 4}};
+    return session_rows(x, "sgo_session_shapes", n, slots, table, sizeof(table), status, cols, st,
+                        [&](const int32_t *d_index, const uint8_t *d_table, uint8_t *const *d) {
+        return launch_shapes(c.S, n, c.pos, ctx_records(c), d_index, reinterpret_cast<const uint32_t *>(d_table), reinterpret_cast<int32_t *>(d[0]),
+                             reinterpret_cast<uint32_t *>(d[1]), st);
+    });
 }
 
 int sgo_session_moves(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t *status, int16_t *moves, int32_t *counts, void *stream) {
@@ -384,71 +349,30 @@ int sgo_session_moves(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    // slots | record index | status | counts | (to a 16-byte boundary) moves; everything behind the index comes back in one copy
-    const size_t N = (size_t)c.S * c.S;
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n, mb = sizeof(int16_t) * 8 * N * (size_t)n;
-    const size_t mo = (3 * ib + cb + 15) & ~(size_t)15;
-    const int rc = stage_session_list(x, "sgo_session_moves", n, slots, mo + mb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    const int lrc = launch_session_moves(c, n, reinterpret_cast<const int32_t *>(d), side, reinterpret_cast<int32_t *>(d + 2 * ib),
-                                         reinterpret_cast<int32_t *>(d + ib), reinterpret_cast<int16_t *>(d + mo),
-                                         reinterpret_cast<int32_t *>(d + 3 * ib), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + 2 * ib, d + 2 * ib, mo + mb - 2 * ib, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + 2 * ib), *hc = reinterpret_cast<const int32_t *>(h + 3 * ib);
-    const int16_t *hm = reinterpret_cast<const int16_t *>(h + mo);
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
-        memcpy(moves + (size_t)i * N * 8, hm + (size_t)i * N * 8, sizeof(int16_t) * 8 * N);
-    }
-    return SGO_OK;
+    const RowCol cols[] = {{counts, sizeof(int32_t) * 8, 4}, {moves, sizeof(int16_t) * 8 * c.S * c.S, 16}};     // k_moves stores 16 bytes at a time
+    return session_rows(x, "sgo_session_moves", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_moves(c.S, n, c.pos, ctx_records(c), d_index, side, reinterpret_cast<int16_t *>(d[1]), reinterpret_cast<int32_t *>(d[0]), st);
+    });
 }
 
 int sgo_session_influence(sgo_ctx *x, int n, const int32_t *slots, const uint32_t *dead, int dilate, int erode_moyo, int erode_terr,
                           int32_t *status, int16_t *values, uint32_t *sets, int32_t *counts, void *stream) {
-    if (!x || n < 0 || !session_influence_params_ok(dilate, erode_moyo, erode_terr) || (n && (!slots || !status || !values || !sets || !counts))) {
+    if (!x || n < 0 || !influence_params_ok(dilate, erode_moyo, erode_terr) || (n && (!slots || !status || !values || !sets || !counts))) {
         set_error("sgo_session_influence: bad argument");
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    Ctx &c = x->c;
+    const Ctx &c = x->c;
     hipStream_t st = (hipStream_t)stream;
-    // slots | dead | record index | status | counts | sets | values; everything behind the index comes back in one copy
-    const size_t N = (size_t)c.S * c.S, NW = (size_t)sgo_plane_words(c.S);
-    const size_t ib = al8(sizeof(int32_t) * (size_t)n), db = al8(sizeof(uint32_t) * NW * (size_t)n), cb = sizeof(int32_t) * 8 * (size_t)n;
-    const size_t sb = sizeof(uint32_t) * 4 * NW * (size_t)n, vb = sizeof(int16_t) * N * (size_t)n;
-    const size_t xo = ib + db, so = xo + ib, co = so + ib, wo = co + cb, vo = wo + sb;
-    const int rc = stage_session_list(x, "sgo_session_influence", n, slots, vo + vb, st);
-    if (rc != SGO_OK) return rc;
-    uint8_t *h = x->h.sess_h, *d = x->h.sess_d;
-    if (dead) {
-        memcpy(h + ib, dead, sizeof(uint32_t) * NW * (size_t)n);
-        SGO_HIP(hipMemcpyAsync(d + ib, h + ib, db, hipMemcpyHostToDevice, st));
-    }
-    const int lrc = launch_session_influence(c, n, reinterpret_cast<const int32_t *>(d), dead ? reinterpret_cast<const uint32_t *>(d + ib) : nullptr,
-                                             dilate, erode_moyo, erode_terr, reinterpret_cast<int32_t *>(d + so), reinterpret_cast<int32_t *>(d + xo),
-                                             reinterpret_cast<int16_t *>(d + vo), reinterpret_cast<uint32_t *>(d + wo),
-                                             reinterpret_cast<int32_t *>(d + co), st);
-    if (lrc != SGO_OK) return lrc;
-    SGO_HIP(hipMemcpyAsync(h + so, d + so, vo + vb - so, hipMemcpyDeviceToHost, st));
-    SGO_HIP(hipStreamSynchronize(st));
-    const int32_t *hs = reinterpret_cast<const int32_t *>(h + so), *hc = reinterpret_cast<const int32_t *>(h + co);
-    const uint32_t *hw = reinterpret_cast<const uint32_t *>(h + wo);
-    const int16_t *hv = reinterpret_cast<const int16_t *>(h + vo);
-    for (int i = 0; i < n; i++) {
-        status[i] = hs[i];
-        if (hs[i] != SGO_OK) continue;                      // the rows of a refused slot stay as the caller filled them
-        memcpy(counts + (size_t)i * 8, hc + (size_t)i * 8, sizeof(int32_t) * 8);
-        memcpy(sets + (size_t)i * 4 * NW, hw + (size_t)i * 4 * NW, sizeof(uint32_t) * 4 * NW);
-        memcpy(values + (size_t)i * N, hv + (size_t)i * N, sizeof(int16_t) * N);
-    }
-    return SGO_OK;
+    const size_t plane = sizeof(uint32_t) * sgo_plane_words(c.S);
+    const RowCol cols[] = {{counts, sizeof(int32_t) * 8, 4}, {sets, 4 * plane, 4}, {values, sizeof(int16_t) * c.S * c.S, 2}};
+    return session_rows(x, "sgo_session_influence", n, slots, dead, plane * n, status, cols, st,
+                        [&](const int32_t *d_index, const uint8_t *d_dead, uint8_t *const *d) {
+        return launch_influence(c.S, n, c.pos, ctx_records(c), d_index, reinterpret_cast<const uint32_t *>(d_dead), dilate, erode_moyo, erode_terr,
+                                reinterpret_cast<int16_t *>(d[2]), reinterpret_cast<uint32_t *>(d[1]), reinterpret_cast<int32_t *>(d[0]), st);
+    });
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 // code on an empty board with its matches masked off; only its stores differ.  Everything lives in registers: no LDS, no scratch.
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
 #include "sgo_rows.hpp"
@@ -100,20 +101,11 @@ __global__ __launch_bounds__(64) void k_shapes(int n, const uint32_t *__restrict
     }
 }
 
-static int launch_shapes(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_table,
-                         int32_t *d_hits, uint32_t *d_cover, hipStream_t st) {
+int launch_shapes(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_table,
+                  int32_t *d_hits, uint32_t *d_cover, hipStream_t st) {
     SGO_DISPATCH(S, k_shapes<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, d_table, d_hits, d_cover));
     SGO_HIP(hipGetLastError());
     return SGO_OK;
-}
-
-// sgo_session_shapes' launches (csrc/sgo_session.hip stages the slots and the table and copies the rows back); every pointer is
-// device memory
-int launch_session_shapes(const Ctx &c, int n, const int32_t *d_slots, int32_t *d_status, int32_t *d_index, const uint32_t *d_table,
-                          int32_t *d_hits, uint32_t *d_cover, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    return launch_shapes(c.S, n, c.pos, ctx_records(c), d_index, d_table, d_hits, d_cover, st);
 }
 
 // ---- the host side: the sixteen variants of a shape as row masks ---------------------------------------------------------------
@@ -234,22 +226,11 @@ int sgo_shapes(int S, int n, const uint32_t *records, const sgo_shape *shape, in
     if (crc != SGO_OK) return crc;
     if ((int)table[0] != S) { set_error("sgo_shapes: the table was compiled for another size"); return SGO_ERR_ARG; }
     if (n == 0) return SGO_OK;
-    // one block: records | table | hits | cover.  Every row is written whole, so nothing of the caller's goes in.
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), tb = sizeof(table), hb = (size_t)n * 4 * sizeof(int32_t);
-    const size_t cb = (size_t)n * sgo_plane_words(S) * sizeof(uint32_t);
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, rb + tb + hb + cb));
-    uint32_t *d_table = reinterpret_cast<uint32_t *>(d + rb), *d_cover = reinterpret_cast<uint32_t *>(d + rb + tb + hb);
-    int32_t *d_hits = reinterpret_cast<int32_t *>(d + rb + tb);
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_table, table, tb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = launch_shapes(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, d_table, d_hits, d_cover, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(hits, d_hits, hb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(cover, d_cover, cb, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_shapes", __FILE__, __LINE__);
-    return rc;
+    // every row is written whole, so nothing of the caller's goes in
+    const HostArray a[] = {{sizeof(table), table, nullptr}, {(size_t)n * 4 * sizeof(int32_t), nullptr, hits}, {(size_t)n * sgo_plane_words(S) * sizeof(uint32_t), nullptr, cover}};
+    return host_entry("sgo_shapes", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_shapes(S, n, d_records, n, nullptr, reinterpret_cast<const uint32_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<uint32_t *>(d[2]), nullptr);
+    });
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 // once) and only its stores differ.  No flood, advance or shuffle sits under a per-item branch.
 #include <string.h>
 
+#include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
 #include "sgo_rows.hpp"
@@ -239,8 +240,8 @@ __global__ __launch_bounds__(64) void k_tactics_read(int n, const uint32_t *reco
 
 static int g_tactics_stage = 0;   // 0: both kernels, 1: k_tactics_chains only, 2: k_tactics_read only (timing)
 
-static int launch_tactics(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int max_chains, uint8_t *d_libs,
-                          int32_t *d_n_chains, int32_t *d_chains, hipStream_t st) {
+int launch_tactics(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int max_chains, uint8_t *d_libs,
+                   int32_t *d_n_chains, int32_t *d_chains, hipStream_t st) {
     if (g_tactics_stage != 2) {
         SGO_DISPATCH(S, k_tactics_chains<kS><<<dim3(cdiv(n, 2)), dim3(64), 0, st>>>(n, d_records, n_records, d_index, max_chains, d_libs,
                                                                                       d_n_chains, d_chains));
@@ -252,14 +253,6 @@ static int launch_tactics(int S, int n, const uint32_t *d_records, int n_records
         SGO_HIP(hipGetLastError());
     }
     return SGO_OK;
-}
-
-// sgo_session_tactics' launches (csrc/sgo_session.hip stages the slots and copies the rows back); every pointer is device memory
-int launch_session_tactics(const Ctx &c, int n, const int32_t *d_slots, int max_chains, int32_t *d_status, int32_t *d_index, uint8_t *d_libs,
-                           int32_t *d_n_chains, int32_t *d_chains, hipStream_t st) {
-    const int rc = launch_session_roots(c, n, d_slots, d_status, d_index, st);
-    if (rc != SGO_OK) return rc;
-    return launch_tactics(c.S, n, c.pos, ctx_records(c), d_index, max_chains, d_libs, d_n_chains, d_chains, st);
 }
 
 }  // namespace sgo
@@ -291,23 +284,11 @@ int sgo_tactics(int S, int n, const uint32_t *records, int max_chains, uint8_t *
         return SGO_ERR_ARG;
     }
     if (n == 0) return SGO_OK;
-    // one block: records | chains | n_chains | libs.  The caller's chain rows go in, so that unwritten rows come back as they were.
-    const size_t rb = (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), cb = (size_t)n * max_chains * 8 * sizeof(int32_t);
-    const size_t ib = (size_t)n * sizeof(int32_t), lb = (size_t)n * S * S;
-    uint8_t *d = nullptr;
-    SGO_HIP(hipMalloc((void **)&d, rb + cb + ib + lb));
-    int32_t *d_chains = reinterpret_cast<int32_t *>(d + rb), *d_n = reinterpret_cast<int32_t *>(d + rb + cb);
-    uint8_t *d_libs = d + rb + cb + ib;
-    int rc = SGO_OK;
-    hipError_t e = hipMemcpy(d, records, rb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_chains, chains, cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = launch_tactics(S, n, reinterpret_cast<const uint32_t *>(d), n, nullptr, max_chains, d_libs, d_n, d_chains, nullptr);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(chains, d_chains, cb, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(n_chains, d_n, ib, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == SGO_OK) e = hipMemcpy(libs, d_libs, lb, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "sgo_tactics", __FILE__, __LINE__);
-    return rc;
+    // the caller's chain rows go in, so that unwritten rows come back as they were
+    const HostArray a[] = {{(size_t)n * max_chains * 8 * sizeof(int32_t), chains, chains}, {(size_t)n * sizeof(int32_t), nullptr, n_chains}, {(size_t)n * S * S, nullptr, libs}};
+    return host_entry("sgo_tactics", records, (size_t)n * sgo_packed_words(S) * sizeof(uint32_t), a, [&](const uint32_t *d_records, uint8_t *const *d) {
+        return launch_tactics(S, n, d_records, n, nullptr, max_chains, d[2], reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<int32_t *>(d[0]), nullptr);
+    });
 }
 
 }  // extern "C"

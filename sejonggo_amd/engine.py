@@ -732,32 +732,32 @@ class SessionEngine(SelfPlayEngine):
                                                 "P", "top_action", "pv")] + [self._stream_ptr()])), "sgo_session_report")
         return out
 
+    def _analysis(self, call, slots, head, *arrays):
+        """call(ctx, n, slots, *head, status, *arrays, stream) on the engine's stream, checked: one of the six sgo_session_X that
+        analyse the root positions of the listed holding sessions.  Returns the int32 status [n] the call filled (SGO_ERR_STATE:
+        not a holding session; that slot's rows in `arrays` stay as they were)."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        status, ptr = np.zeros(len(slots), np.int32), _lib.ptr
+        with self._on_stream():
+            _lib.check(call(self.ctx, len(slots), ptr(slots), *head, ptr(status), *map(ptr, arrays), self._stream_ptr()), call.__name__)
+        return status
+
     def keys(self, slots):
         """The position keys of the root positions of the listed holding sessions (sgo_session_keys; include/sgo.h "position
         keys"), one launch: {"status" int32 [n] (SGO_ERR_STATE: not a holding session; that row stays 0), "key0", "canon" uint64
         [n], "mask" int32 [n]}.  Boards and trees are only read."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n = len(slots)
-        out = {"status": np.zeros(n, np.int32), "key0": np.zeros(n, np.uint64), "canon": np.zeros(n, np.uint64),
-               "mask": np.zeros(n, np.int32)}
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_keys(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(out["status"]), _lib.ptr(out["key0"]),
-                                                 _lib.ptr(out["canon"]), _lib.ptr(out["mask"]), self._stream_ptr()), "sgo_session_keys")
-        return out
+        key0, canon, mask = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.int32)
+        return {"status": self._analysis(self.lib.sgo_session_keys, slots, (), key0, canon, mask), "key0": key0, "canon": canon, "mask": mask}
 
     def tactics(self, slots, max_chains=None):
         """Chains, liberties and ladders of the root positions of the listed holding sessions (sgo_session_tactics; include/sgo.h
         "chains and ladders"): a tactics.Tactics with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session;
         that row stays zero).  Boards and trees are only read."""
         from .tactics import Tactics
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n, mc = len(slots), int(max_chains or _lib.TACTICS_MAX_CHAINS)
         out = Tactics(self.S, np.zeros((n, self.S * self.S), np.uint8), np.zeros(n, np.int32), np.zeros((n, mc, 8), np.int32))
-        out.status = np.zeros(n, np.int32)
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_tactics(self.ctx, C.c_int(n), _lib.ptr(slots), C.c_int(mc), _lib.ptr(out.status),
-                                                    _lib.ptr(out.libs), _lib.ptr(out.n_chains), _lib.ptr(out.chains),
-                                                    self._stream_ptr()), "sgo_session_tactics")
+        out.status = self._analysis(self.lib.sgo_session_tactics, slots, (mc,), out.libs, out.n_chains, out.chains)
         return out
 
     def life(self, slots):
@@ -765,13 +765,9 @@ class SessionEngine(SelfPlayEngine):
         life"): a life.Life with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays zero).
         Boards and trees are only read."""
         from .life import Life
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n, NW = len(slots), self.lib.sgo_plane_words(self.S)
         out = Life(self.S, np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32))
-        out.status = np.zeros(n, np.int32)
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_life(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(out.status), _lib.ptr(out.sets),
-                                                 _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_life")
+        out.status = self._analysis(self.lib.sgo_session_life, slots, (), out.sets, out.counts)
         return out
 
     def influence(self, slots, dead="life", dilate=5, erode_moyo=10, erode_terr=21):
@@ -784,7 +780,6 @@ class SessionEngine(SelfPlayEngine):
         dilate, erode_moyo, erode_terr = check_params(dilate, erode_moyo, erode_terr)
         if isinstance(dead, str) and dead != "life":
             raise ValueError("influence: dead is None, \"life\" or an array of bitsets")
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n, NW = len(slots), self.lib.sgo_plane_words(self.S)
         if isinstance(dead, str):
             proved = self.life(slots).sets
@@ -793,12 +788,9 @@ class SessionEngine(SelfPlayEngine):
             dead = np.ascontiguousarray(dead, dtype=np.uint32)
             if dead.shape != (n, NW):
                 raise ValueError("influence: dead must be [n, NW] words, one row per slot")
-        out = Influence(self.S, np.zeros((n, self.S * self.S), np.int16), np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32),
-                        status=np.zeros(n, np.int32))
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_influence(self.ctx, C.c_int(n), _lib.ptr(slots), _lib.ptr(dead), C.c_int(dilate),
-                                                      C.c_int(erode_moyo), C.c_int(erode_terr), _lib.ptr(out.status), _lib.ptr(out.values),
-                                                      _lib.ptr(out.sets), _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_influence")
+        out = Influence(self.S, np.zeros((n, self.S * self.S), np.int16), np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32))
+        out.status = self._analysis(self.lib.sgo_session_influence, slots, (_lib.ptr(dead), dilate, erode_moyo, erode_terr),
+                                    out.values, out.sets, out.counts)
         return out
 
     def shapes(self, slots, shape):
@@ -806,16 +798,12 @@ class SessionEngine(SelfPlayEngine):
         "shape search"): a shapes.Shapes with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row
         stays {0, -1, 0, 0}).  Boards and trees are only read."""
         from .shapes import Shapes
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        n, NW = len(slots), self.lib.sgo_plane_words(self.S)
+        n = len(slots)
         hits = np.zeros((n, 4), np.int32)
         hits[:, 1] = -1
-        out = Shapes(self.S, hits, np.zeros((n, NW), np.uint32))
-        out.status = np.zeros(n, np.int32)
+        out = Shapes(self.S, hits, np.zeros((n, self.lib.sgo_plane_words(self.S)), np.uint32))
         s = shape.to_struct()
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_shapes(self.ctx, C.c_int(n), _lib.ptr(slots), C.byref(s), _lib.ptr(out.status),
-                                                   _lib.ptr(out.hits), _lib.ptr(out.cover_words), self._stream_ptr()), "sgo_session_shapes")
+        out.status = self._analysis(self.lib.sgo_session_shapes, slots, (C.byref(s),), out.hits, out.cover_words)
         return out
 
     def moves(self, slots, side=0):
@@ -823,12 +811,9 @@ class SessionEngine(SelfPlayEngine):
         include/sgo.h "move outcomes"): a moves.Moves with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding
         session; that row stays zero).  side 0: the side to move, 1: the other colour.  Boards and trees are only read."""
         from .moves import Moves
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
         n = len(slots)
-        out = Moves(self.S, np.zeros((n, self.S * self.S, 8), np.int16), np.zeros((n, 8), np.int32), status=np.zeros(n, np.int32))
-        with self._on_stream():
-            _lib.check(self.lib.sgo_session_moves(self.ctx, C.c_int(n), _lib.ptr(slots), C.c_int(int(side)), _lib.ptr(out.status),
-                                                  _lib.ptr(out.rows), _lib.ptr(out.counts), self._stream_ptr()), "sgo_session_moves")
+        out = Moves(self.S, np.zeros((n, self.S * self.S, 8), np.int16), np.zeros((n, 8), np.int32))
+        out.status = self._analysis(self.lib.sgo_session_moves, slots, (int(side),), out.rows, out.counts)
         return out
 
     # ------------------------------------------------------------------ policy rollouts: how the games ended

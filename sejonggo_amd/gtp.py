@@ -226,51 +226,43 @@ class DeviceSejongGoEngine(object):
         """engine.SessionEngine.report for this game: a dict of arrays with one row."""
         return self.engine.report([self.slot], top=top, depth=depth)
 
+    @staticmethod
+    def _held(v):
+        """v, the one-row result of a session analysis (or its status array), where the slot is a holding session"""
+        if int(getattr(v, "status", v)[0]):
+            raise ValueError("the slot is not a holding session")
+        return v
+
     def keys(self):
         """(canon, mask) of the position on the board (engine.SessionEngine.keys): what records.Book.moves takes."""
         k = self.engine.keys([self.slot])
-        if int(k["status"][0]):
-            raise ValueError("the slot is not a holding session")
+        self._held(k["status"])
         return int(k["canon"][0]), int(k["mask"][0])
 
     def tactics(self):
         """The chains with one or two liberties of the position on the board, read out (engine.SessionEngine.tactics): a list of
         tactics.Chain in ascending anchor order."""
-        t = self.engine.tactics([self.slot])
-        if int(t.status[0]):
-            raise ValueError("the slot is not a holding session")
-        return t.chains_of(0)
+        return self._held(self.engine.tactics([self.slot])).chains_of(0)
 
     def life(self):
         """Unconditional life of the position on the board (engine.SessionEngine.life): a life.Life with one row."""
-        v = self.engine.life([self.slot])
-        if int(v.status[0]):
-            raise ValueError("the slot is not a holding session")
-        return v
+        return self._held(self.engine.life([self.slot]))
 
     def influence(self, dead="life", **params):
         """Bouzy's influence map of the position on the board (engine.SessionEngine.influence): (an influence.Influence with one
         row, the stones int8 [S * S], +1 black).  dead "life": proved-dead stones are lifted first; None: none are."""
         from .rollout import real_board
-        v = self.engine.influence([self.slot], dead=dead, **params)
-        if int(v.status[0]):
-            raise ValueError("the slot is not a holding session")
+        v = self._held(self.engine.influence([self.slot], dead=dead, **params))
         return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
 
     def shapes(self, shape):
         """Where a shapes.Shape occurs in the position on the board (engine.SessionEngine.shapes): a shapes.Shapes with one row."""
-        v = self.engine.shapes([self.slot], shape)
-        if int(v.status[0]):
-            raise ValueError("the slot is not a holding session")
-        return v
+        return self._held(self.engine.shapes([self.slot], shape))
 
     def move_outcomes(self, side=0):
         """What one ply on every point of the position on the board would do (engine.SessionEngine.moves): a moves.Moves with one
         row.  side 0: the side to move, 1: the other colour.  (`moves` is this engine's move list.)"""
-        v = self.engine.moves([self.slot], side)
-        if int(v.status[0]):
-            raise ValueError("the slot is not a holding session")
-        return v
+        return self._held(self.engine.moves([self.slot], side))
 
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""

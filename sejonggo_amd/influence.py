@@ -14,6 +14,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._packed import device_records, points as _points
+
 MAX_DILATE, MAX_ERODE = 8, 31
 # the classical triples: territory / moyo at (5, 10, 21), area at (4, 0, 0)
 PRESETS = {"territory": {"dilate": 5, "erode_moyo": 10, "erode_terr": 21}, "area": {"dilate": 4, "erode_moyo": 0, "erode_terr": 0}}
@@ -31,11 +33,6 @@ def check_params(dilate, erode_moyo, erode_terr):
     if erode_moyo > erode_terr:
         raise ValueError("influence: erode_moyo > erode_terr")
     return int(dilate), int(erode_moyo), int(erode_terr)
-
-
-def _points(words, N):
-    bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")[:N]
-    return [int(a) for a in np.flatnonzero(bits)]
 
 
 class Influence(object):
@@ -82,19 +79,9 @@ def influence(size, records, index=None, dead=None, dilate=5, erode_moyo=10, ero
     per entry of `index` (None: every record in order); an index outside [0, R) gives the zero row.  dead: None, or uint32
     [n, NW] per ROW (host or device) -- the stones to lift."""
     dilate, erode_moyo, erode_terr = check_params(dilate, erode_moyo, erode_terr)
-    import torch
     from . import _lib
-    lib = _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not torch.is_tensor(records):
-        records = torch.from_numpy(np.ascontiguousarray(records).view(np.int32))
-    records = records.to(dev).contiguous()
-    R, NW = int(records.shape[0]), lib.sgo_plane_words(size)
-    if records.dim() != 2 or int(records.shape[1]) != lib.sgo_packed_words(size):
-        raise ValueError("influence: records must be [R, 16 * NW] words")
-    idx = None if index is None else torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
-    n = R if idx is None else int(idx.shape[0])
-    values, sets, counts = influence_dev(size, records, idx, n, dead, dilate, erode_moyo, erode_terr, lib)
+    records, _, idx, n = device_records(size, records, index, error=lambda text: ValueError("influence: " + text))
+    values, sets, counts = influence_dev(size, records, idx, n, dead, dilate, erode_moyo, erode_terr, _lib.load())
     return Influence(size, values.cpu().numpy(), sets.cpu().numpy().view(np.uint32), counts.cpu().numpy())
 
 

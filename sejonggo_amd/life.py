@@ -12,10 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-
-def _points(words, N):
-    bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")[:N]
-    return [int(a) for a in np.flatnonzero(bits)]
+from ._packed import device_records, points as _points
 
 
 class Life(object):
@@ -64,16 +61,9 @@ def life(size, records, index=None):
     of `index` (None: every record in order); an index outside [0, R) gives the zero row."""
     import torch
     from . import _lib
-    lib = _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not torch.is_tensor(records):
-        records = torch.from_numpy(np.ascontiguousarray(records).view(np.int32))
-    records = records.to(dev).contiguous()
-    R, NW = int(records.shape[0]), lib.sgo_plane_words(size)
-    assert records.dim() == 2 and int(records.shape[1]) == lib.sgo_packed_words(size), "records must be [R, 16 * NW] words"
-    idx = None if index is None else torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
-    n = R if idx is None else int(idx.shape[0])
-    sets = torch.zeros((n, 4, NW), dtype=torch.int32, device=dev)
+    records, R, idx, n = device_records(size, records, index)
+    lib, dev = _lib.load(), records.device
+    sets = torch.zeros((n, 4, lib.sgo_plane_words(size)), dtype=torch.int32, device=dev)
     counts = torch.zeros((n, 8), dtype=torch.int32, device=dev)
     _lib.check(lib.sgo_life_dev(C.c_int(size), C.c_int(n), _lib.ptr(records), C.c_int(R), _lib.ptr(idx), _lib.ptr(sets), _lib.ptr(counts),
                                 _lib.stream_ptr()), "sgo_life_dev")

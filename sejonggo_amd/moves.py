@@ -16,6 +16,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._packed import device_records
+
 ALLOWED, OCCUPIED, KO, SUICIDE = 1, 2, 4, 8
 COUNTS = ("allowed", "capturing", "max_captured", "max_capture_move", "self_atari", "atari_giving", "escapes", "forbidden_sound")
 KINDS = ("capture", "atari", "escape", "selfatari", "forbidden", "all")
@@ -113,16 +115,9 @@ def moves_dev(size, records, idx, side, lib):
 def moves(size, records, index=None, side=0):
     """sgo_moves_dev on packed records (a numpy array or a device tensor, [R, 16 * NW] 32-bit words): a Moves with one row per entry
     of `index` (None: every record in order); an index outside [0, R) gives the zero row.  side 0: the side to move, 1: the other."""
-    import torch
     from . import _lib
-    lib = _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not torch.is_tensor(records):
-        records = torch.from_numpy(np.ascontiguousarray(records).view(np.int32))
-    records = records.to(dev).contiguous()
-    assert records.dim() == 2 and int(records.shape[1]) == lib.sgo_packed_words(size), "records must be [R, 16 * NW] words"
-    idx = None if index is None else torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
-    rows, counts = moves_dev(size, records, idx, side, lib)
+    records, _, idx, _ = device_records(size, records, index)
+    rows, counts = moves_dev(size, records, idx, side, _lib.load())
     return Moves(size, rows.cpu().numpy(), counts.cpu().numpy())
 
 

@@ -328,16 +328,25 @@ class DeviceRecords(object):
                                                        P(value), int(k), P(rank), P(best), P(p_target), P(flags), P(counters),
                                                        self._lib.stream_ptr()), "sgo_records_score_dev")
 
+    def _index(self, index):
+        """a list of record indices (a tensor or an array) as a contiguous int32 tensor on the device"""
+        torch = self.torch
+        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
+        return index.contiguous()
+
+    def _rows(self, index, words=slice(None)):
+        """(the `words` of the listed records, ok): an index outside the object reads record 0 and is False in ok"""
+        ok = (index >= 0) & (index < self.cap)
+        return self.records[self.torch.where(ok, index, self.torch.zeros_like(index)).long(), words], ok
+
     def keys(self, index, target=None):
         """(key0, canon, mask, canon_action) device tensors of the listed records (sgo_keys_dev, one launch): the keys int64
         holding the uint64 bit patterns, mask / canon_action int32; canon_action is None without targets.  An index outside the
         object gives the zero row."""
         torch = self.torch
-        def dev(a):
-            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))).to(self.device, torch.int32)
-        index = dev(index).contiguous()
+        index = self._index(index)
         n = int(index.shape[0])
-        target = dev(target).contiguous() if target is not None else None
+        target = self._index(target) if target is not None else None
         assert target is None or int(target.shape[0]) == n
         key0, canon = torch.zeros(n, dtype=torch.int64, device=self.device), torch.zeros(n, dtype=torch.int64, device=self.device)
         mask = torch.zeros(n, dtype=torch.int32, device=self.device)
@@ -354,8 +363,7 @@ class DeviceRecords(object):
         (sgo_tactics_dev, two launches; include/sgo.h "chains and ladders").  Chain rows behind min(n_chains, max_chains) are zero;
         an index outside the object gives the zero row."""
         torch = self.torch
-        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
-        index = index.contiguous()
+        index = self._index(index)
         n, mc = int(index.shape[0]), int(max_chains)
         libs = torch.zeros((n, self.N), dtype=torch.uint8, device=self.device)
         n_chains = torch.zeros(n, dtype=torch.int32, device=self.device)
@@ -371,8 +379,7 @@ class DeviceRecords(object):
         """(sets int32 [n, 4, NW] holding the uint32 bit patterns, counts int32 [n, 8]) device tensors of the listed records
         (sgo_life_dev, one launch; include/sgo.h "unconditional life"); an index outside the object gives the zero row."""
         torch = self.torch
-        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
-        index = index.contiguous()
+        index = self._index(index)
         n = int(index.shape[0])
         sets = torch.zeros((n, 4, self.NW), dtype=torch.int32, device=self.device)
         counts = torch.zeros((n, 8), dtype=torch.int32, device=self.device)
@@ -391,14 +398,11 @@ class DeviceRecords(object):
         dilate, erode_moyo, erode_terr = check_params(dilate, erode_moyo, erode_terr)
         if isinstance(dead, str) and dead != "life":
             raise ValueError("influence: dead is None, \"life\" or an array of bitsets")
-        torch = self.torch
-        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
-        index = index.contiguous()
+        index = self._index(index)
         n = int(index.shape[0])
         if isinstance(dead, str):
             life_sets, _ = self.life(index)
-            ok = (index >= 0) & (index < self.cap)
-            planes = self.records[torch.where(ok, index, torch.zeros_like(index)).long(), :2 * self.NW]
+            planes, _ = self._rows(index, slice(0, 2 * self.NW))
             dead = dead_from_life(life_sets, planes[:, :self.NW], planes[:, self.NW:]).contiguous()
         return influence_dev(self.S, self.records, index, n, dead, dilate, erode_moyo, erode_terr, self.lib, self.rec_ptr, self.cap)
 
@@ -408,8 +412,7 @@ class DeviceRecords(object):
         outside the object gives {0, -1, 0, 0} and a zero cover."""
         from .shapes import compile_table
         torch = self.torch
-        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
-        index = index.contiguous()
+        index = self._index(index)
         n = int(index.shape[0])
         table = torch.from_numpy(compile_table(self.S, shape).view(np.int32)).to(self.device)
         hits = torch.zeros((n, 4), dtype=torch.int32, device=self.device)
@@ -429,8 +432,7 @@ class DeviceRecords(object):
         all True) is the colour side 0 moves for, i.e. the record's side to move."""
         from .moves import moves_dev
         torch = self.torch
-        index = (index if torch.is_tensor(index) else torch.from_numpy(np.ascontiguousarray(index, np.int32))).to(self.device, torch.int32)
-        index = index.contiguous()
+        index = self._index(index)
         n = int(index.shape[0])
         if action is None:
             if n == 0:
@@ -449,8 +451,8 @@ class DeviceRecords(object):
             counts[lo:hi] = c
         in_turn = torch.ones(n, dtype=torch.bool, device=self.device)
         if colour is not None and n:
-            ok = (index >= 0) & (index < self.cap)
-            flag = self.records[torch.where(ok, index, torch.zeros_like(index)).long(), self.NW - 1] < 0      # the top bit of plane 0's last word
+            last, ok = self._rows(index, self.NW - 1)
+            flag = last < 0                                              # the top bit of plane 0's last word
             col = torch.from_numpy(np.ascontiguousarray(colour, np.int32)).to(self.device)
             in_turn = ok & (torch.where(flag, -1, 1) == col)
         return played, counts, in_turn
@@ -458,11 +460,8 @@ class DeviceRecords(object):
     def stones(self, index):
         """int8 [n, N] (host): +1 black, -1 white on the listed records; an index outside the object gives the empty board."""
         from .tactics import stones_of
-        index = np.asarray(index, dtype=np.int64)
-        ok = (index >= 0) & (index < self.cap)
-        idx = self.torch.from_numpy(np.where(ok, index, 0)).to(self.device)
-        planes = self.records.index_select(0, idx)[:, :2 * self.NW].contiguous().cpu().numpy()
-        return stones_of(self.S, planes) * ok[:, None].astype(np.int8)
+        planes, ok = self._rows(self._index(index), slice(0, 2 * self.NW))
+        return stones_of(self.S, planes.contiguous().cpu().numpy()) * ok.cpu().numpy()[:, None].astype(np.int8)
 
 
 class Chunk(object):
@@ -473,6 +472,17 @@ class Chunk(object):
 
     def rows(self, mask):
         return {k: getattr(self, k)[mask] for k in self.FIELDS}
+
+    def walk(self):
+        """(i, g, base, off, n, played) per game of the chunk: its place in `games`, its index into RecordSet.records, its first
+        record and its first entry row, the number of its entries and how many of them were played.  Records base .. base +
+        played were written; entry row off + j stands between records base + j and base + j + 1."""
+        base = off = 0
+        for i, g in enumerate(self.games):
+            n = int(self.n_entries[i])
+            yield i, g, base, off, n, (int(self.fail_at[i]) if self.status[i] != 0 else n)
+            base += n + 1
+            off += n
 
 
 class RecordSet(object):
@@ -521,7 +531,7 @@ class RecordSet(object):
             off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
             total = int(n_entries.sum())
             ch = Chunk()
-            ch.games = games
+            ch.games, ch.n_entries = games, n_entries
             ch.action, ch.colour = np.zeros(total, np.int32), np.zeros(total, np.int32)
             ch.node, ch.game = np.zeros(total, np.int32), np.zeros(total, np.int32)
             ch.setup, ch.z, has = np.zeros(total, bool), np.zeros(total, np.int32), np.zeros(total, bool)
@@ -561,7 +571,24 @@ class RecordSet(object):
             ch.mask, ch.canon_action = _host(mask), _host(action)
             yield ch
 
-    # ------------------------------------------------------------------ chains and ladders
+    # ------------------------------------------------------------------ one row per record: tactics, life, influence, shapes
+    def _per_record(self, attr, call, wrap, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `attr` = wrap(*call(index)) over the records of the chunk (one
+        backend call per chunk) and, with stones=True, ch.stones int8 [records, N] (+1 black, -1 white) of the same rows."""
+        for ch in self.replay():
+            index = self._record_index(ch)
+            setattr(ch, attr, wrap(*call(index)))
+            if stones:
+                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
+            yield ch
+
+    def _record_index(self, ch):
+        """int32 [records of the chunk]: the record's own index where the replay wrote it, -1 behind a refused entry"""
+        index = np.full(len(ch.action) + len(ch.games), -1, np.int32)
+        for _, _, base, _, _, played in ch.walk():
+            index[base:base + played + 1] = np.arange(base, base + played + 1)
+        return index
+
     def tactics(self, max_chains=128, stones=False):
         """Generator of Chunks as `replay` gives them, each with `tactics`, a tactics.Tactics with one row per RECORD of the
         chunk (one backend call per chunk): row ch.index[e] is the position before entry e, row ch.index[e] + 1 the position
@@ -569,62 +596,32 @@ class RecordSet(object):
         [records, N] (+1 black, -1 white), rows as in `tactics`.  The chain table takes 32 * max_chains bytes per record: for a
         large collection give the set a smaller max_entries (the chunk size) or a smaller max_chains."""
         from .tactics import Tactics
-        for ch in self.replay():
-            index = self._record_index(ch)
-            libs, n_chains, chains = self.backend.tactics(index, max_chains)
-            ch.tactics = Tactics(self.S, _host(libs, np.uint8), _host(n_chains), _host(chains))
-            if stones:
-                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
-            yield ch
+        return self._per_record("tactics", lambda index: self.backend.tactics(index, max_chains),
+                                lambda libs, n_chains, chains: Tactics(self.S, _host(libs, np.uint8), _host(n_chains), _host(chains)), stones)
 
-    def _record_index(self, ch):
-        """int32 [records of the chunk]: the record's own index where the replay wrote it, -1 behind a refused entry"""
-        n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
-        base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int64) + np.arange(len(ch.games))
-        have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1
-        index = np.full(int(n_entries.sum()) + len(ch.games), -1, np.int32)
-        for b, h in zip(base, have):
-            index[int(b):int(b + h)] = np.arange(int(b), int(b + h))
-        return index
-
-    # ------------------------------------------------------------------ unconditional life
     def life(self, stones=False):
         """Generator of Chunks as `replay` gives them, each with `life`, a life.Life with one row per RECORD of the chunk (one
         backend call per chunk): row ch.index[e] is the position before entry e, row ch.index[e] + 1 the position after it.
         Records that were not written (behind a refused entry) give the zero row.  stones=True adds ch.stones as `tactics` does."""
         from .life import Life
-        for ch in self.replay():
-            index = self._record_index(ch)
-            sets, counts = self.backend.life(index)
-            ch.life = Life(self.S, _host(sets, np.uint32), _host(counts))
-            if stones:
-                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
-            yield ch
+        return self._per_record("life", self.backend.life, lambda sets, counts: Life(self.S, _host(sets, np.uint32), _host(counts)), stones)
 
-    # ------------------------------------------------------------------ influence and territory estimate
     def influence(self, dead="life", stones=False, dilate=5, erode_moyo=10, erode_terr=21):
         """Generator of Chunks as `replay` gives them, each with `influence`, an influence.Influence with one row per RECORD of the
         chunk (one backend call per chunk), rows as in `life`.  dead "life": the stones unconditional life proves dead are lifted
         first; None: nothing is lifted.  Records that were not written give the zero row.  stones=True adds ch.stones as `tactics`
         does."""
         from .influence import Influence
-        for ch in self.replay():
-            index = self._record_index(ch)
-            values, sets, counts = self.backend.influence(index, dead, dilate, erode_moyo, erode_terr)
-            ch.influence = Influence(self.S, _host(values, np.int16), _host(sets, np.uint32), _host(counts))
-            if stones:
-                ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
-            yield ch
+        return self._per_record("influence", lambda index: self.backend.influence(index, dead, dilate, erode_moyo, erode_terr),
+                                lambda values, sets, counts: Influence(self.S, _host(values, np.int16), _host(sets, np.uint32), _host(counts)),
+                                stones)
 
-    # ------------------------------------------------------------------ shape search
     def shapes(self, shape):
         """Generator of Chunks as `replay` gives them, each with `shapes`, a shapes.Shapes with one row per RECORD of the chunk
         (one backend call per chunk), rows as in `life`.  Records that were not written give {0, -1, 0, 0}."""
         from .shapes import Shapes
-        for ch in self.replay():
-            hits, cover = self.backend.shapes(self._record_index(ch), shape)
-            ch.shapes = Shapes(self.S, _host(hits), _host(cover, np.uint32))
-            yield ch
+        return self._per_record("shapes", lambda index: self.backend.shapes(index, shape),
+                                lambda hits, cover: Shapes(self.S, _host(hits), _host(cover, np.uint32)))
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -650,10 +647,8 @@ class RecordSet(object):
         from .shapes import continuation, continuation_label
         games, tally, searched = [], {}, 0
         for ch in self.shapes(shape):
-            v, base, off = ch.shapes, 0, 0
-            for i, g in enumerate(ch.games):
-                n = len(self.records[g].entries)
-                played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
+            v = ch.shapes
+            for _, g, base, off, _, played in ch.walk():
                 searched += 1
                 rows = np.flatnonzero(v.hits[base:base + played + 1, 0] > 0)
                 if len(rows):
@@ -668,8 +663,6 @@ class RecordSet(object):
                     if has_move:
                         t[1] += int(ch.z[e] > 0)
                         t[2] += int(ch.z[e] < 0)
-                base += n + 1
-                off += n
         rows = [{"key": k, "label": continuation_label(k), "count": t[0], "wins": t[1], "losses": t[2]} for k, t in tally.items()]
         rows.sort(key=lambda d: (-d["count"], d["label"]))
         return {"searched": searched, "matched": len(games), "games": games, "continuations": rows}
@@ -714,15 +707,13 @@ class RecordSet(object):
         found by a signature folded on the host, sig = sm(sig ^ canon_j) from sig = 0, and confirmed on the sequences."""
         seqs = {}
         for ch in self.replay():
-            n_entries = np.array([len(self.records[g].entries) for g in ch.games], np.int64)
-            base = np.concatenate([[0], np.cumsum(n_entries)[:-1]]) + np.arange(len(ch.games))
-            have = np.where(ch.status != 0, ch.fail_at.astype(np.int64), n_entries) + 1       # records base .. base + have - 1
-            index = np.concatenate([b + np.arange(h) for b, h in zip(base, have)]).astype(np.int32)
+            games = list(ch.walk())                                                            # records base .. base + played
+            index = np.concatenate([base + np.arange(played + 1) for _, _, base, _, _, played in games]).astype(np.int32)
             canon = _host(self.backend.keys(index, None)[1], np.uint64)
             at = 0
-            for g, h in zip(ch.games, have):
-                seqs[g] = canon[at:at + int(h)].copy()
-                at += int(h)
+            for _, g, _, _, _, played in games:
+                seqs[g] = canon[at:at + played + 1].copy()
+                at += played + 1
         games = sorted(seqs)
         sig = np.zeros(len(games), np.uint64)
         length = np.array([len(seqs[g]) for g in games], np.int64)
@@ -838,15 +829,11 @@ def life_lines(record_set):
     the position after the last played entry."""
     out = []
     for ch in record_set.life():
-        v, base = ch.life, 0
-        for i, g in enumerate(ch.games):
-            n = len(record_set.records[g].entries)
-            played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
-            rows = v.counts[base:base + played + 1]
+        for _, g, base, _, _, played in ch.walk():
+            rows = ch.life.counts[base:base + played + 1]
             alive = np.flatnonzero((rows[:, 0] + rows[:, 1]) > 0)
             out.append({"name": record_set.records[g].name, "plies": played, "first_alive": int(alive[0]) if len(alive) else None,
                         "unsettled": int(rows[-1, 6])})
-            base += n + 1
     return out
 
 
@@ -857,18 +844,14 @@ def influence_table(record_set, width=20, dead="life"):
     "margin"}]: the margin (the estimate before komi; a Record keeps no komi) of the position after the last played entry}."""
     sums, games = {}, []
     for ch in record_set.influence(dead=dead):
-        v, base = ch.influence, 0
-        for i, g in enumerate(ch.games):
-            n = len(record_set.records[g].entries)
-            played = int(ch.fail_at[i]) if ch.status[i] != 0 else n
-            rows = v.counts[base:base + played + 1].astype(np.int64)
+        for _, g, base, _, _, played in ch.walk():
+            rows = ch.influence.counts[base:base + played + 1].astype(np.int64)
             for k in range(0, played + 1, width):
                 part = rows[k:k + width]
                 s = sums.setdefault(k // width, np.zeros(5, np.int64))
                 s += [len(part), int(np.abs(part[:, 7]).sum()), int(part[:, 6].sum()), int((part[:, 2] - part[:, 0]).sum()),
                       int((part[:, 3] - part[:, 1]).sum())]
             games.append({"name": record_set.records[g].name, "plies": played, "margin": int(rows[-1, 7])})
-            base += n + 1
     buckets = [{"first_ply": b * width, "positions": int(s[0]), "abs_margin": float(s[1]) / int(s[0]), "neutral": float(s[2]) / int(s[0]),
                 "moyo_beyond_black": float(s[3]) / int(s[0]), "moyo_beyond_white": float(s[4]) / int(s[0])} for b, s in sorted(sums.items())]
     return {"buckets": buckets, "games": games}

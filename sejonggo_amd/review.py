@@ -31,6 +31,7 @@ that margin across the move in the mover's favour), and a last line names the th
 lowest gain.  An estimate, and numbers, not verdicts.  Given without --sims, --net and --rollouts it searches nothing and loads no
 net: the lines then hold the move and the two figures only.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
+import contextlib
 import json
 import string
 import sys
@@ -142,37 +143,49 @@ def _search(engine, slots, sims):
         engine.raise_on_error = keep
 
 
+@contextlib.contextmanager
+def _record_set_of(game, record_set):
+    """the record set given, or a device RecordSet that holds the game as its only record and is closed on exit"""
+    if record_set is not None:
+        yield record_set
+        return
+    from .records import Record, RecordSet
+    entries = [(int(a), int(c)) for a, c in game.moves]
+    record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
+    try:
+        yield record_set
+    finally:
+        record_set.close()
+
+
+def played_moves(game, ch):
+    """(m, e, r, action, colour) of the B / W moves of `game` that chunk `ch` of a one-record set played: the move number (set-up
+    entries are not counted), the entry's row, the record of the position before it (r + 1: after it) and the move."""
+    m = 0
+    for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
+        if is_setup:
+            continue
+        m += 1
+        if ch.valid[e]:
+            yield m, e, int(ch.index[e]), int(action), int(colour)
+
+
 def move_flags(game, record_set):
     """{move number: ["ladder", "missed"]} of the B / W moves of `game` (tactics.review_flags) from one RecordSet.tactics pass over
     a set that holds the game as its only record."""
     from .tactics import review_flags
     out = {}
     for ch in record_set.tactics(stones=True):
-        t, m = ch.tactics, 0
-        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
-            if is_setup:
-                continue
-            m += 1
-            if not ch.valid[e]:
-                continue
-            r = int(ch.index[e])
-            out[m] = review_flags(game.size, int(action), int(colour), ch.stones[r], t.chains_of(r), ch.stones[r + 1], t.chains_of(r + 1),
-                                  t.libs[r + 1])
+        t = ch.tactics
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = review_flags(game.size, action, colour, ch.stones[r], t.chains_of(r), ch.stones[r + 1], t.chains_of(r + 1), t.libs[r + 1])
     return out
 
 
 def add_tactics(rows, game, record_set=None):
     """Adds `tactics` (the flag list of move_flags) to every row of a review.  record_set None: a device RecordSet of the game."""
-    from .records import Record, RecordSet
-    own = record_set is None
-    if own:
-        entries = [(int(a), int(c)) for a, c in game.moves]
-        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
-    try:
-        flags = move_flags(game, record_set)
-    finally:
-        if own:
-            record_set.close()
+    with _record_set_of(game, record_set) as rs:
+        flags = move_flags(game, rs)
     for row in rows:
         row["tactics"] = flags.get(row["move_number"], [])
     return rows
@@ -184,16 +197,10 @@ def life_rows(game, record_set):
     from .life import review_flags
     out = {}
     for ch in record_set.life():
-        v, m, decided = ch.life, 0, False
-        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
-            if is_setup:
-                continue
-            m += 1
-            if not ch.valid[e]:
-                continue
-            r = int(ch.index[e])
+        v, decided = ch.life, False
+        for m, _, r, action, _ in played_moves(game, ch):
             c = v.counts[r]
-            flags = review_flags(game.size, int(action), v, r, decided)
+            flags = review_flags(game.size, action, v, r, decided)
             decided = decided or v.settled(r)
             out[m] = {"settled": game.size * game.size - int(c[6]), "black": int(c[0]) + int(c[2]), "white": int(c[1]) + int(c[3]),
                       "flags": flags}
@@ -203,16 +210,8 @@ def life_rows(game, record_set):
 def add_life(rows, game, record_set=None):
     """Adds `life` ({settled, black, white}) and `life_flags` to every row of a review.  record_set None: a device RecordSet of
     the game."""
-    from .records import Record, RecordSet
-    own = record_set is None
-    if own:
-        entries = [(int(a), int(c)) for a, c in game.moves]
-        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
-    try:
-        found = life_rows(game, record_set)
-    finally:
-        if own:
-            record_set.close()
+    with _record_set_of(game, record_set) as rs:
+        found = life_rows(game, rs)
     for row in rows:
         d = found.get(row["move_number"])
         if d is not None:
@@ -228,14 +227,8 @@ def find_rows(game, record_set, shape):
     from .shapes import review_flags
     out = {}
     for ch in record_set.shapes(shape):
-        v, m, seen, gone = ch.shapes, 0, False, False
-        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
-            if is_setup:
-                continue
-            m += 1
-            if not ch.valid[e]:
-                continue
-            r = int(ch.index[e])
+        v, seen, gone = ch.shapes, False, False
+        for m, _, r, _, _ in played_moves(game, ch):
             before, after = v.n_hits(r) > 0, v.n_hits(r + 1) > 0
             flags = [f for f in review_flags(before, after) if not (seen if f == "appears" else gone)]
             seen, gone = seen or before or after, gone or "disappears" in flags
@@ -246,16 +239,8 @@ def find_rows(game, record_set, shape):
 def add_find(rows, game, shape, record_set=None):
     """Adds `find` (n_hits of the position after the move) and `find_flags` to every row of a review.  record_set None: a device
     RecordSet of the game."""
-    from .records import Record, RecordSet
-    own = record_set is None
-    if own:
-        entries = [(int(a), int(c)) for a, c in game.moves]
-        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
-    try:
-        found = find_rows(game, record_set, shape)
-    finally:
-        if own:
-            record_set.close()
+    with _record_set_of(game, record_set) as rs:
+        found = find_rows(game, rs, shape)
     for row in rows:
         d = found.get(row["move_number"])
         if d is not None:
@@ -271,29 +256,15 @@ def moves_rows(game, record_set):
     from .moves import review_flags
     out = {}
     for ch in record_set.moves():
-        m = 0
-        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
-            if is_setup:
-                continue
-            m += 1
-            if not ch.valid[e]:
-                continue
-            out[m] = review_flags(game.size, int(action), ch.played[e], ch.move_counts[e], lambda a: vertex(a, game.size)) if ch.in_turn[e] else []
+        for m, e, _, action, _ in played_moves(game, ch):
+            out[m] = review_flags(game.size, action, ch.played[e], ch.move_counts[e], lambda a: vertex(a, game.size)) if ch.in_turn[e] else []
     return out
 
 
 def add_moves(rows, game, record_set=None):
     """Adds `moves_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
-    from .records import Record, RecordSet
-    own = record_set is None
-    if own:
-        entries = [(int(a), int(c)) for a, c in game.moves]
-        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
-    try:
-        found = moves_rows(game, record_set)
-    finally:
-        if own:
-            record_set.close()
+    with _record_set_of(game, record_set) as rs:
+        found = moves_rows(game, rs)
     for row in rows:
         row["moves_flags"] = list(found.get(row["move_number"], []))
     return rows
@@ -305,15 +276,8 @@ def influence_rows(game, record_set, komi=0.0, dead="life"):
     from .influence import review_fields
     out = {}
     for ch in record_set.influence(dead=dead):
-        v, m = ch.influence, 0
-        for e, ((action, colour), is_setup) in enumerate(zip(game.moves, game.setup)):
-            if is_setup:
-                continue
-            m += 1
-            if not ch.valid[e]:
-                continue
-            r = int(ch.index[e])
-            out[m] = review_fields(v, r, r + 1, int(colour), komi)
+        for m, _, r, _, colour in played_moves(game, ch):
+            out[m] = review_fields(ch.influence, r, r + 1, colour, komi)
     return out
 
 
@@ -321,18 +285,10 @@ def add_influence(rows, game, record_set=None, komi=None):
     """Adds `estimate` (Bouzy's area-score estimate of the position in front of the move, proved-dead stones lifted, minus komi;
     positive = black) and `gain` (the change of the margin across the move in the mover's favour) to every row of a review.
     komi None: the record's, 0 when it has none.  record_set None: a device RecordSet of the game.  Numbers, not verdicts."""
-    from .records import Record, RecordSet
-    own = record_set is None
-    if own:
-        entries = [(int(a), int(c)) for a, c in game.moves]
-        record_set = RecordSet([Record("game", game.size, entries, list(game.setup), list(range(1, len(entries) + 1)), None)], game.size)
     if komi is None:
         komi = game.komi if game.komi is not None else 0.0
-    try:
-        found = influence_rows(game, record_set, komi)
-    finally:
-        if own:
-            record_set.close()
+    with _record_set_of(game, record_set) as rs:
+        found = influence_rows(game, rs, komi)
     for row in rows:
         d = found.get(row["move_number"])
         if d is not None:

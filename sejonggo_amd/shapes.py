@@ -20,6 +20,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._packed import device_records, points as _points
+
 DC, X, O, E = 0, 1, 2, 3
 L, T, R, B = 1, 2, 4, 8
 _CHARS = {"X": X, "O": O, ".": E, "*": DC, "?": DC}
@@ -139,11 +141,6 @@ def compile_table(size, shape):
     return table
 
 
-def _points(words, N):
-    bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")[:N]
-    return [int(a) for a in np.flatnonzero(bits)]
-
-
 class Shapes(object):
     """hits int32 [n, 4] (n_hits, first, vmask, n_cover), cover uint32 [n, NW]"""
 
@@ -177,18 +174,11 @@ def shapes(size, records, shape, index=None):
     entry of `index` (None: every record in order); an index outside [0, R) gives {0, -1, 0, 0} and an empty cover."""
     import torch
     from . import _lib
-    lib = _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not torch.is_tensor(records):
-        records = torch.from_numpy(np.ascontiguousarray(records).view(np.int32))
-    records = records.to(dev).contiguous()
-    Rn, NW = int(records.shape[0]), lib.sgo_plane_words(size)
-    assert records.dim() == 2 and int(records.shape[1]) == lib.sgo_packed_words(size), "records must be [R, 16 * NW] words"
+    records, Rn, idx, n = device_records(size, records, index)
+    lib, dev = _lib.load(), records.device
     table = torch.from_numpy(compile_table(size, shape).view(np.int32)).to(dev)
-    idx = None if index is None else torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
-    n = Rn if idx is None else int(idx.shape[0])
     hits = torch.zeros((n, 4), dtype=torch.int32, device=dev)
-    cover = torch.zeros((n, NW), dtype=torch.int32, device=dev)
+    cover = torch.zeros((n, lib.sgo_plane_words(size)), dtype=torch.int32, device=dev)
     _lib.check(lib.sgo_shapes_dev(C.c_int(size), C.c_int(n), _lib.ptr(records), C.c_int(Rn), _lib.ptr(idx), _lib.ptr(table), _lib.ptr(hits),
                                   _lib.ptr(cover), _lib.stream_ptr()), "sgo_shapes_dev")
     return Shapes(size, hits.cpu().numpy(), cover.cpu().numpy().view(np.uint32))

@@ -13,6 +13,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._packed import device_records
+
 A_CAPTURED, D_CAPTURED, A_UNKNOWN, D_UNKNOWN, D_RAN = 1, 2, 4, 8, 16
 
 
@@ -53,16 +55,9 @@ def tactics(size, records, index=None, max_chains=128):
     entry of `index` (None: every record in order); an index outside [0, R) gives the zero row."""
     import torch
     from . import _lib
-    lib = _lib.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not torch.is_tensor(records):
-        records = torch.from_numpy(np.ascontiguousarray(records).view(np.int32))
-    records = records.to(dev).contiguous()
-    R, N = int(records.shape[0]), size * size
-    assert records.dim() == 2 and int(records.shape[1]) == lib.sgo_packed_words(size), "records must be [R, 16 * NW] words"
-    idx = None if index is None else torch.from_numpy(np.ascontiguousarray(index, np.int32)).to(dev)
-    n = R if idx is None else int(idx.shape[0])
-    libs = torch.zeros((n, N), dtype=torch.uint8, device=dev)
+    records, R, idx, n = device_records(size, records, index)
+    lib, dev = _lib.load(), records.device
+    libs = torch.zeros((n, size * size), dtype=torch.uint8, device=dev)
     n_chains = torch.zeros(n, dtype=torch.int32, device=dev)
     chains = torch.zeros((n, int(max_chains), 8), dtype=torch.int32, device=dev)
     _lib.check(lib.sgo_tactics_dev(C.c_int(size), C.c_int(n), _lib.ptr(records), C.c_int(R), _lib.ptr(idx), C.c_int(int(max_chains)),

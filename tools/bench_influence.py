@@ -14,38 +14,14 @@ with the model (tests/influence_model.py).
 import argparse
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-S = 19
+from bench_chunk import S, load_games, resources, stats, timed  # noqa: E402
 TERRITORY, AREA = (5, 10, 21), (4, 0, 0)
-
-
-def stats(ms):
-    s = sorted(ms)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]          # noqa: E731
-    return {"median_us": 1e3 * q(0.5), "min_us": 1e3 * s[0], "p10_us": 1e3 * q(0.1), "p90_us": 1e3 * q(0.9), "reps": len(s)}
-
-
-def resources():
-    """{"vgprs" / "sgprs" / "lds_bytes" / "scratch": {size: value}} of k_influence<S> from the device listing; None without hipcc"""
-    import vmcnt_isa_check
-    asm = vmcnt_isa_check.device_asm(source="sgo_influence.hip")
-    if asm is None:
-        return None
-    out = {"vgprs": {}, "sgprs": {}, "lds_bytes": {}, "scratch": {}}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+_ZN3sgo11k_influenceILi(\d+)EE\S*\n(.*?)^\s*\.end_amdhsa_kernel", asm, re.M | re.S):
-        d = dict(re.findall(r"^\s*(\.amdhsa_\w+)\s+(\S+)", m.group(2), re.M))
-        size = m.group(1)
-        out["vgprs"][size] = int(d[".amdhsa_next_free_vgpr"])
-        out["sgprs"][size] = int(d[".amdhsa_next_free_sgpr"])
-        out["lds_bytes"][size] = int(d[".amdhsa_group_segment_fixed_size"])
-        out["scratch"][size] = int(d[".amdhsa_private_segment_fixed_size"])
-    return out
 
 
 def sign_agreement(margins, lengths, width=20):
@@ -75,32 +51,12 @@ def main():
     from sejonggo_amd.records import DeviceRecords
     from tests import influence_model
     lib = L.require_gpu()
-    z = np.load(os.path.join(ROOT, "tests", "golden", "sgf_S19.npz"))
-    games = []
-    for gi in range(5):
-        mv = z["g%02d_moves" % gi]
-        games.append(([S * S if y >= S else int(y) * S + int(x) for x, y, _ in mv], [int(c) for _, _, c in mv]))
-    lengths = [len(g[0]) for g in games]
-    first = sum(lengths) + len(games)                          # the records of the first copy
-    games = games * a.copies
-    n_entries = np.array([len(g[0]) for g in games], np.int32)
-    off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
-    acts = np.concatenate([g[0] for g in games]).astype(np.int32)
-    cols = np.concatenate([g[1] for g in games]).astype(np.int32)
+    n_entries, off, acts, cols, first = load_games(a.copies)
+    lengths = n_entries[:5].tolist()                           # the games of the first copy
     total = int(n_entries.sum())
-    R = total + len(games)
-    be = DeviceRecords(S, len(games), total)
+    R = total + len(n_entries)
+    be = DeviceRecords(S, len(n_entries), total)
     dev = be.device
-    ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
-
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     n = R                                                      # rows: every record of the chunk
     index = torch.arange(n, dtype=torch.int32, device=dev)
     values = torch.zeros((n, S * S), dtype=torch.int16, device=dev)
@@ -147,10 +103,10 @@ def main():
     out = {"what": "sgo_influence_dev (k_influence) at (5, 10, 21) and (4, 0, 0) beside sgo_records_replay, sgo_keys_dev and sgo_life_dev "
                    "(k_life) on one 19x19 chunk, one MI355X; HIP events around every call, arms interleaved; every eighth device row of "
                    "the first copy equals the model's",
-           "board": S, "games": len(games), "rows": n,
+           "board": S, "games": len(n_entries), "rows": n,
            "sign_of_final_margin_share": sign_agreement(c[:, 7], lengths),
            "neutral_mean": float(c[:, 6].mean()), "abs_margin_mean": float(np.abs(c[:, 7]).mean()),
-           "resources_gfx950": {"k_influence": resources()}, "arms": {}}
+           "resources_gfx950": {"k_influence": resources("sgo_influence.hip", "k_influence")}, "arms": {}}
     for k, v in ms.items():
         st = stats(v)
         st["rows_per_s"] = (1 if k == "influence_one_row" else n) / (st["median_us"] * 1e-6)

@@ -17,15 +17,9 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-S = 19
+from bench_chunk import S, load_games, stats, timed  # noqa: E402
 CHUNK = 1 << 18
 BYTES_PER_RECORD = 2 * 48 + 4 + 4 + 8 + 8 + 4 + 4
-
-
-def stats(ms):
-    s = sorted(ms)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]          # noqa: E731
-    return {"median_us": 1e3 * q(0.5), "min_us": 1e3 * s[0], "p10_us": 1e3 * q(0.1), "p90_us": 1e3 * q(0.9), "reps": len(s)}
 
 
 def main():
@@ -38,34 +32,14 @@ def main():
     from sejonggo_amd import _lib as L
     from sejonggo_amd.records import DeviceRecords
     lib = L.require_gpu()
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "sgf_S19.npz"))
-    games = []
-    for gi in range(5):
-        mv = z["g%02d_moves" % gi]
-        games.append(([S * S if y >= S else int(y) * S + int(x) for x, y, _ in mv], [int(c) for _, _, c in mv]))
-    per_set = sum(len(g[0]) + 1 for g in games)
-    copies = CHUNK // per_set
-    games = games * copies
-    n_entries = np.array([len(g[0]) for g in games], np.int32)
-    off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
-    acts = np.concatenate([g[0] for g in games]).astype(np.int32)
-    cols = np.concatenate([g[1] for g in games]).astype(np.int32)
+    copies = CHUNK // load_games(1)[4]
+    n_entries, off, acts, cols, _ = load_games(copies)
     total = int(n_entries.sum())
-    R = total + len(games)
-    be = DeviceRecords(S, len(games), total)
+    R = total + len(n_entries)
+    be = DeviceRecords(S, len(n_entries), total)
     dev = be.device
-    ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
-
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     # rows: every entry, the record before it and the recorded move
-    index = torch.from_numpy((np.arange(total) + np.repeat(np.arange(len(games)), n_entries)).astype(np.int32)).to(dev)
+    index = torch.from_numpy((np.arange(total) + np.repeat(np.arange(len(n_entries)), n_entries)).astype(np.int32)).to(dev)
     target = torch.from_numpy(acts).to(dev)
     n = total
     key0, canon = torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
@@ -112,7 +86,7 @@ def main():
     lib.sgo_keys_mode(0)
     out = {"what": "sgo_keys_dev (k_keys) beside sgo_records_replay and sgo_records_score_dev on one 19x19 chunk, one MI355X; HIP events "
                    "around every call, arms interleaved",
-           "board": S, "games": len(games), "records": R, "rows": n, "bytes_needed_per_record": BYTES_PER_RECORD,
+           "board": S, "games": len(n_entries), "records": R, "rows": n, "bytes_needed_per_record": BYTES_PER_RECORD,
            "forms_bit_identical": same, "arms": {}}
     for k, v in ms.items():
         st = stats(v)

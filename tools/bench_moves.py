@@ -14,37 +14,13 @@ replay wrote for the same records.
 import argparse
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-S = 19
-
-
-def stats(ms):
-    s = sorted(ms)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]          # noqa: E731
-    return {"median_us": 1e3 * q(0.5), "min_us": 1e3 * s[0], "p10_us": 1e3 * q(0.1), "p90_us": 1e3 * q(0.9), "reps": len(s)}
-
-
-def resources():
-    """{"vgprs" / "sgprs" / "lds_bytes" / "scratch": {size: value}} of k_moves<S> from the device listing; None without hipcc"""
-    import vmcnt_isa_check
-    asm = vmcnt_isa_check.device_asm(source="sgo_moves.hip")
-    if asm is None:
-        return None
-    out = {"vgprs": {}, "sgprs": {}, "lds_bytes": {}, "scratch": {}}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+_ZN3sgo7k_movesILi(\d+)EE\S*\n(.*?)^\s*\.end_amdhsa_kernel", asm, re.M | re.S):
-        d = dict(re.findall(r"^\s*(\.amdhsa_\w+)\s+(\S+)", m.group(2), re.M))
-        size = m.group(1)
-        out["vgprs"][size] = int(d[".amdhsa_next_free_vgpr"])
-        out["sgprs"][size] = int(d[".amdhsa_next_free_sgpr"])
-        out["lds_bytes"][size] = int(d[".amdhsa_group_segment_fixed_size"])
-        out["scratch"][size] = int(d[".amdhsa_private_segment_fixed_size"])
-    return out
+from bench_chunk import S, load_games, resources, stats, timed  # noqa: E402
 
 
 def contact_points(records, np):
@@ -72,31 +48,12 @@ def main():
     from sejonggo_amd import _lib as L
     from sejonggo_amd.records import DeviceRecords
     lib = L.require_gpu()
-    z = np.load(os.path.join(ROOT, "tests", "golden", "sgf_S19.npz"))
-    games = []
-    for gi in range(5):
-        mv = z["g%02d_moves" % gi]
-        games.append(([S * S if y >= S else int(y) * S + int(x) for x, y, _ in mv], [int(c) for _, _, c in mv]))
-    middle = len(games[0][0]) // 2                             # a record of the first game, half way through
-    games = games * a.copies
-    n_entries = np.array([len(g[0]) for g in games], np.int32)
-    off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
-    acts = np.concatenate([g[0] for g in games]).astype(np.int32)
-    cols = np.concatenate([g[1] for g in games]).astype(np.int32)
+    n_entries, off, acts, cols, _ = load_games(a.copies)
+    middle = int(n_entries[0]) // 2                            # a record of the first game, half way through
     total = int(n_entries.sum())
-    R = total + len(games)
-    be = DeviceRecords(S, len(games), total)
+    R = total + len(n_entries)
+    be = DeviceRecords(S, len(n_entries), total)
     dev = be.device
-    ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
-
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     n, mc = R, 128                                             # rows: every record of the chunk
     index = torch.arange(n, dtype=torch.int32, device=dev)
     one = torch.tensor([middle], dtype=torch.int32, device=dev)
@@ -152,12 +109,12 @@ def main():
     out = {"what": "sgo_moves_dev (k_moves, side 0) beside sgo_records_replay, k_tactics_chains and sgo_life_dev on one 19x19 chunk, and "
                    "one call with n = 1 on a middle-game position; one MI355X; HIP events around every call, arms interleaved; the "
                    "device's ALLOWED bits equal the legal sets the replay wrote for the same records",
-           "board": S, "games": len(games), "rows": n,
+           "board": S, "games": len(n_entries), "rows": n,
            "contact_points_per_row_mean": float(contact.mean()), "contact_points_per_row_max": int(contact.max()),
            "loop_trips_per_wave_mean": float(pairs.mean()), "loop_trips_per_wave_max": int(pairs.max()),
            "n1_position": {"record": int(middle), "contact_points": int(contact[middle]), "allowed": int(got[middle, 0])},
            "forbidden_sound_points": int(got[:, 7].sum()), "rows_with_forbidden_sound": int((got[:, 7] > 0).sum()),
-           "resources_gfx950": {"k_moves": resources()}, "arms": {}}
+           "resources_gfx950": {"k_moves": resources("sgo_moves.hip", "k_moves")}, "arms": {}}
     for k, v in ms.items():
         st = stats(v)
         st["rows_per_s"] = (1 if k == "moves_n1" else n) / (st["median_us"] * 1e-6)

@@ -17,39 +17,15 @@ the model's, tests/shapes_model.py), and the compiler's resource figures of k_sh
 import argparse
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-S = 19
+from bench_chunk import S, load_games, resources, stats, timed  # noqa: E402
 SIDE = "+-------------------\n|..*..X..*....O..*..|\n|.*.X.O.......X.O.*.|\n|*.....*..........*.|"
 CORNER = "+-----\n|.....\n|.....\n|...X.\n|.*...\n|....."        # a lone stone on the 3-4 point: the opening of some of the games
-
-
-def stats(ms):
-    s = sorted(ms)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]          # noqa: E731
-    return {"median_us": 1e3 * q(0.5), "min_us": 1e3 * s[0], "p10_us": 1e3 * q(0.1), "p90_us": 1e3 * q(0.9), "reps": len(s)}
-
-
-def resources():
-    """{"vgprs" / "sgprs" / "lds_bytes" / "scratch": {size: value}} of k_shapes<S> from the device listing; None without hipcc"""
-    import vmcnt_isa_check
-    asm = vmcnt_isa_check.device_asm(source="sgo_shapes.hip")
-    if asm is None:
-        return None
-    out = {"vgprs": {}, "sgprs": {}, "lds_bytes": {}, "scratch": {}}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+_ZN3sgo8k_shapesILi(\d+)EE\S*\n(.*?)^\s*\.end_amdhsa_kernel", asm, re.M | re.S):
-        d = dict(re.findall(r"^\s*(\.amdhsa_\w+)\s+(\S+)", m.group(2), re.M))
-        size = m.group(1)
-        out["vgprs"][size] = int(d[".amdhsa_next_free_vgpr"])
-        out["sgprs"][size] = int(d[".amdhsa_next_free_sgpr"])
-        out["lds_bytes"][size] = int(d[".amdhsa_group_segment_fixed_size"])
-        out["scratch"][size] = int(d[".amdhsa_private_segment_fixed_size"])
-    return out
 
 
 def main():
@@ -65,33 +41,13 @@ def main():
     from sejonggo_amd.shapes import Shape, compile_table
     from tests import shapes_model
     lib = L.require_gpu()
-    z = np.load(os.path.join(ROOT, "tests", "golden", "sgf_S19.npz"))
-    games = []
-    for gi in range(5):
-        mv = z["g%02d_moves" % gi]
-        games.append(([S * S if y >= S else int(y) * S + int(x) for x, y, _ in mv], [int(c) for _, _, c in mv]))
-    first = sum(len(g[0]) + 1 for g in games)                  # the records of the first copy
-    games = games * a.copies
-    n_entries = np.array([len(g[0]) for g in games], np.int32)
-    off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
-    acts = np.concatenate([g[0] for g in games]).astype(np.int32)
-    cols = np.concatenate([g[1] for g in games]).astype(np.int32)
+    n_entries, off, acts, cols, first = load_games(a.copies)
     total = int(n_entries.sum())
-    R = total + len(games)
-    be = DeviceRecords(S, len(games), total)
+    R = total + len(n_entries)
+    be = DeviceRecords(S, len(n_entries), total)
     dev = be.device
     status, _ = be.replay(n_entries, off, acts, cols)
     assert not status.any()
-    ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
-
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     n = R                                                      # rows: every record of the chunk
     index = torch.arange(n, dtype=torch.int32, device=dev)
     shapes = {"side": Shape.parse(SIDE), "corner": Shape.parse(CORNER)}
@@ -144,8 +100,8 @@ def main():
     share["side_v0"] = float((got1[:, 0] > 0).mean())
     out = {"what": "sgo_shapes_dev (k_shapes) beside sgo_keys_dev (k_keys) and sgo_life_dev (k_life) on one 19x19 chunk, one MI355X; HIP "
                    "events around every call, arms interleaved; the device rows of the first copy equal the model's",
-           "board": S, "games": len(games), "rows": n, "shapes": {"side": SIDE.split("\n"), "corner": CORNER.split("\n")},
-           "rows_hit_share": share, "resources_gfx950": {"k_shapes": resources()}, "arms": {}}
+           "board": S, "games": len(n_entries), "rows": n, "shapes": {"side": SIDE.split("\n"), "corner": CORNER.split("\n")},
+           "rows_hit_share": share, "resources_gfx950": {"k_shapes": resources("sgo_shapes.hip", "k_shapes")}, "arms": {}}
     for k, v in ms.items():
         st = stats(v)
         st["rows_per_s"] = n / (st["median_us"] * 1e-6)

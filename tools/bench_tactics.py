@@ -15,13 +15,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-S = 19
-
-
-def stats(ms):
-    s = sorted(ms)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]          # noqa: E731
-    return {"median_us": 1e3 * q(0.5), "min_us": 1e3 * s[0], "p10_us": 1e3 * q(0.1), "p90_us": 1e3 * q(0.9), "reps": len(s)}
+from bench_chunk import S, load_games, stats, timed  # noqa: E402
 
 
 def main():
@@ -36,30 +30,11 @@ def main():
     from sejonggo_amd import _lib as L
     from sejonggo_amd.records import DeviceRecords
     lib = L.require_gpu()
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "sgf_S19.npz"))
-    games = []
-    for gi in range(5):
-        mv = z["g%02d_moves" % gi]
-        games.append(([S * S if y >= S else int(y) * S + int(x) for x, y, _ in mv], [int(c) for _, _, c in mv]))
-    games = games * a.copies
-    n_entries = np.array([len(g[0]) for g in games], np.int32)
-    off = np.concatenate([[0], np.cumsum(n_entries)[:-1]]).astype(np.int32)
-    acts = np.concatenate([g[0] for g in games]).astype(np.int32)
-    cols = np.concatenate([g[1] for g in games]).astype(np.int32)
+    n_entries, off, acts, cols, _ = load_games(a.copies)
     total = int(n_entries.sum())
-    R = total + len(games)
-    be = DeviceRecords(S, len(games), total)
+    R = total + len(n_entries)
+    be = DeviceRecords(S, len(n_entries), total)
     dev = be.device
-    ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
-
-    def timed(fn):
-        e0, e1 = ev(), ev()
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     n, mc = R, a.max_chains                                    # rows: every record of the chunk
     index = torch.arange(n, dtype=torch.int32, device=dev)
     libs = torch.zeros((n, S * S), dtype=torch.uint8, device=dev)
@@ -102,7 +77,7 @@ def main():
     listed = np.concatenate([rows[i, :stored[i]] for i in range(0, n, max(1, a.copies))]) if n else np.zeros((0, 8), np.int32)
     out = {"what": "sgo_tactics_dev (k_tactics_chains, k_tactics_read) beside sgo_records_replay and sgo_keys_dev on one 19x19 chunk, "
                    "one MI355X; HIP events around every call, arms interleaved",
-           "board": S, "games": len(games), "rows": n, "max_chains": mc,
+           "board": S, "games": len(n_entries), "rows": n, "max_chains": mc,
            "listed_chains_per_row_mean": float(nc.mean()), "listed_chains_per_row_max": int(nc.max()),
            "read_work_items": int(n) * mc, "read_work_items_idle_share": 1.0 - float(stored.sum()) / (float(n) * mc),
            "read_waves_with_work_share": float(np.ceil(stored / 2.0).sum()) / (float(n) * ((mc + 1) // 2)),
