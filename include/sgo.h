@@ -52,7 +52,8 @@ extern "C" {
  *   the "policy rollouts" section (sgo_rollout_*), the "game records" section (sgo_records_*), the "position keys" section
  *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics), the "unconditional life" section
  *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes), the "move
- *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence). */
+ *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
+ *   section (sgo_secure*, sgo_session_secure). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -808,6 +809,62 @@ int sgo_moves(int S, int n, const uint32_t *records, int side, int16_t *moves, i
  * rows are copied out of it.  SGO_ERR_ARG: side outside {0, 1}, a slot outside the context, a NULL argument. */
 int sgo_session_moves(sgo_ctx *ctx, int n, const int32_t *slots, int side, int32_t *status, int16_t *moves, int32_t *counts,
                       void *stream);
+
+/* ---- securing moves: what does one more stone make pass-alive? ----------------------------------------------------------------------- */
+/* Per packed record and per point of the board: the unconditional life of the position after ONE ply by a chosen side on that point,
+ * and a per-record summary with the life sets before and after the best such ply (csrc/sgo_secure.hip).  The question a player asks
+ * of a group -- is it safe, and if not, which move makes it safe -- in its exact one-ply form: play the stone, then prove what can
+ * never be captured.  Everything is integer; there are no search caps and no "unknown".  N = S * S.
+ * Inputs of a record and `side` are read exactly as sgo_moves_dev reads them ("move outcomes" above): black / white = the bits a < N
+ * of planes 0 / 1; the to-play flag is the top bit of the last word of plane 0 (NOT a stone); planes 2 / 3 = black / white one ply
+ * ago, bits a < N, used only for the ko test; padding bits and planes 4..15 are never read.  side = 0: the MOVER M is the record's
+ * side to move (white iff the flag is set), and `prev` = M's stones one ply ago.  side = 1: M is the other colour; there is no `prev`
+ * and so no ko restriction.  "own" = M's stones, "opp" = the other colour's.
+ * alive_X, terr_X and safe_X of a position are those of the "unconditional life" section above, with X = M and O = the other colour;
+ * the position's side to move plays no part in them.
+ * PER POINT a (index y * S + x) a row int16[4] = {flags, alive, terr, dead}:
+ *   flags: SGO_MOVES_OCCUPIED, SGO_MOVES_KO, SGO_MOVES_ALLOWED and SGO_MOVES_SUICIDE with the meanings of the "move outcomes" section
+ *     (the same constants).  On an OCCUPIED point words 1..3 are 0, and ALLOWED and SUICIDE are never set.
+ *   For an EMPTY a let P' be the position after one ply of sgo_make_play by M on a (captures first, then suicide is executed); the
+ *   ply is played whether or not it is ALLOWED.
+ *   alive = |alive_M(P')|;  terr = |terr_M(P')|;  dead = the number of opp stones of P' inside terr_M(P').
+ *   These are literally the life definitions on P': there are no special cases for a suicide (P' then lacks the stone and the
+ *   mover's chain it killed) or for an illegal record.
+ * PER RECORD counts int32[8], with P the record's position, base = |alive_M(P)| + |terr_M(P)| and gain(a) = alive + terr - base:
+ *   0 base_alive   |alive_M(P)|
+ *   1 base_terr    |terr_M(P)|
+ *   2 base_dead    the opp stones of P inside terr_M(P)
+ *   3 allowed      the number of ALLOWED points
+ *   4 securing     ALLOWED points with gain > 0
+ *   5 best_gain    the largest gain over the ALLOWED points; 0 when there are none; may be negative
+ *   6 best_move    the lowest ALLOWED a that reaches best_gain; -1 when allowed == 0
+ *   7 harmful      ALLOWED points with gain < 0
+ * PER RECORD sets uint32 [4][sgo_plane_words(S)] = alive_M(P), terr_M(P), alive_M(P*), terr_M(P*), where P* is P' of best_move, or P
+ *   itself when best_move is -1; bit order as the life sets; all bits a >= N are zero.
+ *
+ * sgo_secure_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_table int16 [n][N][4] (8-byte aligned: a point's row is one store), d_sets uint32 [n][4][sgo_plane_words(S)], d_counts int32
+ * [n][8].  A row whose record index is outside [0, n_records) gets all-zero table rows, sets and counts (best_move 0 too).  TWO
+ * launches on `stream` (a half-wavefront per row and empty point, then a wavefront per row), no allocation, no synchronisation,
+ * capturable; n == 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, side outside
+ * {0, 1}, a NULL d_records or output, a d_table that is not 8-byte aligned. */
+int sgo_secure_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_table,
+                   uint32_t *d_sets, int32_t *d_counts, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests.
+ * No alignment is asked of host buffers. */
+int sgo_secure(int S, int n, const uint32_t *records, int side, int16_t *table, uint32_t *sets, int32_t *counts);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], table [n][N][4], sets [n][4][sgo_plane_words(S)], counts [n][8].  status[i] = SGO_OK, or SGO_ERR_STATE
+ * for a slot that is not a holding session: that row's outputs are left as the caller filled them.  The context is only read; a
+ * slot may be listed repeatedly.  No alignment is asked of the host arrays.  SGO_ERR_ARG: side outside {0, 1}, a slot outside the
+ * context, a NULL argument. */
+int sgo_session_secure(sgo_ctx *ctx, int n, const int32_t *slots, int side, int32_t *status, int16_t *table, uint32_t *sets,
+                       int32_t *counts, void *stream);
+/* How the first launch deals a row's empty points to workgroups, for A/B timing; the words written are the same.  Bits 0..15: the
+ * workgroups per row (0 = chosen from n, the default; capped at ceil(N / 2)).  Bit 16: 0 = half h of pair k takes the (2k + h)-th
+ * EMPTY point (default), 1 = it takes point 2k + h and idles on a stone.  Returns the previous mode; a negative value, or one with
+ * other bits set or more than 1024 workgroups, only queries. */
+int sgo_secure_mode(int mode);
 
 /* ---- influence: who holds what right now, and by how much?  (an ESTIMATE, not a proof) --------------------------------------------- */
 /* Per packed record: Bouzy's dilation / erosion map of the stones, the territory and moyo sets read off it, and an area-score

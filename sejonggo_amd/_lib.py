@@ -42,6 +42,7 @@ SYMBOLS = [
     "sgo_shape_compile", "sgo_shapes_dev", "sgo_shapes", "sgo_session_shapes",
     "sgo_moves_dev", "sgo_moves", "sgo_session_moves",
     "sgo_influence_dev", "sgo_influence", "sgo_session_influence",
+    "sgo_secure_dev", "sgo_secure", "sgo_session_secure", "sgo_secure_mode",
 ]
 
 
@@ -201,7 +202,11 @@ def load():
     lib.sgo_moves_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
     lib.sgo_moves.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 2
     lib.sgo_session_moves.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    lib.sgo_influence_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
+    lib.sgo_secure_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_secure.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_session_secure.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_secure_mode.argtypes = [C.c_int]
+    lib.sgo_influence_dev.argtypes =[C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
     lib.sgo_influence.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3
     lib.sgo_session_influence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5
     _lib = lib

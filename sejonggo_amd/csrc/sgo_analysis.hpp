@@ -1,4 +1,4 @@
-// sgo_analysis.hpp -- what the six position analyses (keys, tactics, life, shapes, moves, influence) share on the host: the record
+// sgo_analysis.hpp -- what the seven position analyses (keys, tactics, life, shapes, moves, influence, secure) share on the host: the record
 // launchers of their translation units, which sgo_session.hip runs over the context's root records, and the one body of their
 // host entries sgo_X.  Host code only; every kernel stays in its own file.
 #pragma once
@@ -19,6 +19,8 @@ int launch_moves(int S, int n, const uint32_t *d_records, int n_records, const i
                  int32_t *d_counts, hipStream_t st);
 int launch_influence(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const uint32_t *d_dead, int dilate,
                      int erode_moyo, int erode_terr, int16_t *d_values, uint32_t *d_sets, int32_t *d_counts, hipStream_t st);
+int launch_secure(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int side, int16_t *d_table,
+                  uint32_t *d_sets, int32_t *d_counts, hipStream_t st);
 
 // The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
 // (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip).

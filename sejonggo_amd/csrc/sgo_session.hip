@@ -1,9 +1,9 @@
 // sgo_session.hip -- interactive (session) slots of the self-play engine: sgo_session_play, _genmove, _analyze, _setup, _report, the
 // "interactive games" section of include/sgo.h, and the host side of sgo_session_keys ("position keys"; its kernel is in
 // sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
-// sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip) and of
-// sgo_session_influence ("influence"; sgo_influence.hip).
-// Those six (session_rows below, over the launchers of sgo_analysis.hpp) and sgo_rollout_start_sessions (sgo_rollout.hip) find
+// sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip), of
+// sgo_session_influence ("influence"; sgo_influence.hip) and of sgo_session_secure ("securing moves"; sgo_secure.hip).
+// Those seven (session_rows below, over the launchers of sgo_analysis.hpp) and sgo_rollout_start_sessions (sgo_rollout.hip) find
 // the root records of the listed slots with launch_session_roots below and run their ordinary record kernels over the context's
 // blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
 // kernels are in sgo_session.hpp.  What it replaces of the reference (drsagitn/sejonggo): sejonggo_nomodel.py:20-100, the
@@ -106,7 +106,7 @@ struct RowCol {
     std::function<size_t(int)> stored;
 };
 
-// The body of the six session analyses (keys, tactics, life, shapes, moves, influence).  The session buffer is laid out as
+// The body of the seven session analyses (keys, tactics, life, shapes, moves, influence, secure).  The session buffer is laid out as
 //     slots | input | record index | status | columns
 // the slots (and `input`, where there is one: a shape table, the dead sets) go up, k_session_roots names the root records,
 // launch(d_index, d_input, d_cols) runs the ordinary record launcher over the context's blocks, and everything behind the index
@@ -354,6 +354,23 @@ int sgo_session_moves(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t
     const RowCol cols[] = {{counts, sizeof(int32_t) * 8, 4}, {moves, sizeof(int16_t) * 8 * c.S * c.S, 16}};     // k_moves stores 16 bytes at a time
     return session_rows(x, "sgo_session_moves", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
         return launch_moves(c.S, n, c.pos, ctx_records(c), d_index, side, reinterpret_cast<int16_t *>(d[1]), reinterpret_cast<int32_t *>(d[0]), st);
+    });
+}
+
+int sgo_session_secure(sgo_ctx *x, int n, const int32_t *slots, int side, int32_t *status, int16_t *table, uint32_t *sets, int32_t *counts,
+                       void *stream) {
+    if (!x || n < 0 || (side != 0 && side != 1) || (n && (!slots || !status || !table || !sets || !counts))) {
+        set_error("sgo_session_secure: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    const Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    const RowCol cols[] = {{counts, sizeof(int32_t) * 8, 4}, {sets, sizeof(uint32_t) * 4 * sgo_plane_words(c.S), 4},
+                           {table, sizeof(int16_t) * 4 * c.S * c.S, 8}};                                        // k_secure stores 8 bytes at a time
+    return session_rows(x, "sgo_session_secure", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_secure(c.S, n, c.pos, ctx_records(c), d_index, side, reinterpret_cast<int16_t *>(d[2]), reinterpret_cast<uint32_t *>(d[1]),
+                             reinterpret_cast<int32_t *>(d[0]), st);
     });
 }
 

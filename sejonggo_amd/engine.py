@@ -816,6 +816,17 @@ class SessionEngine(SelfPlayEngine):
         out.status = self._analysis(self.lib.sgo_session_moves, slots, (int(side),), out.rows, out.counts)
         return out
 
+    def secure(self, slots, side=0):
+        """What one more stone on every empty point makes pass-alive in the root positions of the listed holding sessions
+        (sgo_session_secure; include/sgo.h "securing moves"): a secure.Secure with status int32 [n] beside its arrays
+        (SGO_ERR_STATE: not a holding session; that row stays zero).  side 0: the side to move, 1: the other colour.  Boards and
+        trees are only read."""
+        from .secure import Secure
+        n, NW = len(slots), self.lib.sgo_plane_words(self.S)
+        out = Secure(self.S, np.zeros((n, self.S * self.S, 4), np.int16), np.zeros((n, 4, NW), np.uint32), np.zeros((n, 8), np.int32))
+        out.status = self._analysis(self.lib.sgo_session_secure, slots, (int(side),), out.table, out.sets, out.counts)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

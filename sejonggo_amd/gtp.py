@@ -264,6 +264,13 @@ class DeviceSejongGoEngine(object):
         row.  side 0: the side to move, 1: the other colour.  (`moves` is this engine's move list.)"""
         return self._held(self.engine.moves([self.slot], side))
 
+    def secure(self, side=0):
+        """What one more stone on every empty point of the position on the board makes pass-alive (engine.SessionEngine.secure):
+        (a secure.Secure with one row, the stones int8 [S * S], +1 black).  side 0: the side to move, 1: the other colour."""
+        from .rollout import real_board
+        v = self._held(self.engine.secure([self.slot], side))
+        return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -315,7 +322,7 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "quit"])
+                          "sgo-estimate", "sgo-secure", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -519,6 +526,26 @@ class GTPEngine(object):
                 raise GTPFailure("syntax error")
         return format_kind(self._engine_method("move_outcomes")(side), 0, kind, self._vertex)
 
+    def sgo_secure(self, *words):
+        """Private extension `sgo-secure [opponent] [min K]`: what one more stone makes pass-alive (include/sgo.h "securing moves")
+        -- the board from the top row down, one cell per point: X / O a stone, the gain (stones and points that become safe beyond
+        those that are) on every allowed point whose gain is at least K (default 2: a stone that merely extends a living chain
+        gains 1), - on an allowed point that loses some, . anything else; then `base B allowed A securing N harmful H` and `best V
+        gain G secures ...` with the points the best move makes safe, or `best none`.  The mover is the side to move; with
+        `opponent` the other colour.  A proof about one ply: the opponent's answer is not read."""
+        from .secure import MIN_GAIN, format_board
+        side, k, words = 0, None, list(words)
+        while words:
+            w = words.pop(0)
+            if w == "opponent" and side == 0:
+                side = 1
+            elif w == "min" and k is None and words and words[0].lstrip("-").isdigit():
+                k = int(words.pop(0))
+            else:
+                raise GTPFailure("syntax error")
+        v, stones = self._engine_method("secure")(side)
+        return format_board(v, 0, stones, self._vertex, MIN_GAIN if k is None else k)
+
     def _influence(self, words):
         from .influence import PRESETS
         preset, dead = None, "life"
@@ -550,7 +577,7 @@ class GTPEngine(object):
 
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
-               "sgo-estimate": "sgo_estimate"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

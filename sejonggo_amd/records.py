@@ -423,6 +423,27 @@ class DeviceRecords(object):
                                                     P(table), P(hits), P(cover), self._lib.stream_ptr()), "sgo_shapes_dev")
         return hits, cover
 
+    def to_play(self, index):
+        """int8 [n] device tensor: the side to move of the listed records (+1 black, -1 white; 0 for an index outside the object)"""
+        torch = self.torch
+        index = self._index(index)
+        if int(index.shape[0]) == 0:
+            return torch.zeros(0, dtype=torch.int8, device=self.device)
+        last, ok = self._rows(index, self.NW - 1)                        # the top bit of plane 0's last word
+        return (torch.where(last < 0, -1, 1) * ok).to(torch.int8)
+
+    def secure(self, index, side=0):
+        """(table int16 [n, N, 4], sets int32 [n, 4, NW] holding the uint32 bit patterns, counts int32 [n, 8]) device tensors of the
+        listed records (sgo_secure_dev, two launches; include/sgo.h "securing moves"); an index outside the object gives the zero
+        row."""
+        from .secure import secure_dev
+        torch = self.torch
+        index = self._index(index)
+        if int(index.shape[0]) == 0:
+            return (torch.zeros((0, self.N, 4), dtype=torch.int16, device=self.device),
+                    torch.zeros((0, 4, self.NW), dtype=torch.int32, device=self.device), torch.zeros((0, 8), dtype=torch.int32, device=self.device))
+        return secure_dev(self.S, self.records, index, side, self.lib)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -622,6 +643,17 @@ class RecordSet(object):
         from .shapes import Shapes
         return self._per_record("shapes", lambda index: self.backend.shapes(index, shape),
                                 lambda hits, cover: Shapes(self.S, _host(hits), _host(cover, np.uint32)))
+
+    def secure(self, side=0):
+        """Generator of Chunks as `replay` gives them, each with `secure`, a secure.Secure with one row per RECORD of the chunk (one
+        backend call per chunk), rows as in `life`: what one more stone of the side to move (side 1: of the other colour) makes
+        pass-alive.  Records that were not written give the zero row.  The table takes 8 * N bytes per record.  ch.to_play int8
+        [records] is the side to move of each record (+1 black, -1 white; 0 for a record that was not written)."""
+        from .secure import Secure
+        for ch in self._per_record("secure", lambda index: self.backend.secure(index, side),
+                                   lambda table, sets, counts: Secure(self.S, _host(table, np.int16), _host(sets, np.uint32), _host(counts))):
+            ch.to_play = _host(self.backend.to_play(self._record_index(ch)), np.int8)
+            yield ch
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -880,6 +912,30 @@ def moves_table(record_set, width=20):
     return bucket_table(np.concatenate(ply), np.concatenate(action), np.concatenate(played), np.concatenate(counts), record_set.S, width)
 
 
+def secure_table(record_set, width=20):
+    """The table of `--secure` (secure.bucket_table) from one RecordSet.secure pass: per bucket of `width` moves the positions in
+    which something is proved already, the positions that offer a securing move of gain >= 2, how often the recorded move took the
+    best one or any, and the harmful moves played.  Set-up stones and moves out of turn are left out."""
+    from .secure import bucket_table
+    ply, action, played, counts = [], [], [], []
+    for ch in record_set.secure():
+        v = ch.secure
+        first = {}
+        for e in np.flatnonzero(ch.valid & ~ch.setup):
+            g, r, a = int(ch.game[e]), int(ch.index[e]), int(ch.action[e])
+            number = first.get(g, 0)
+            first[g] = number + 1
+            if int(ch.to_play[r]) != int(ch.colour[e]):
+                continue
+            ply.append(number)
+            action.append(a)
+            played.append(v.table[r, a] if 0 <= a < v.N else np.zeros(4, np.int16))
+            counts.append(v.counts[r])
+    if not ply:
+        return []
+    return bucket_table(np.array(ply), np.array(action), np.stack(played), np.stack(counts), record_set.S, width)
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -925,6 +981,9 @@ def main(argv=None, out=sys.stdout):
                     help="per 20-move bucket: the share of the played moves that capture / give atari / escape / are self-atari beside "
                          "the mean share of the allowed moves of the same positions that do, and the points the inherited legal-move "
                          "rule forbids although the stone would stand")
+    ap.add_argument("--secure", action="store_true",
+                    help="per 20-move bucket: the positions that offer a securing move (one more stone that makes at least 2 more stones "
+                         "and points pass-alive), how often the recorded move took the best one or any, and the harmful moves played")
     ap.add_argument("--influence", action="store_true",
                     help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
                          "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
@@ -985,6 +1044,14 @@ def main(argv=None, out=sys.stdout):
             doc["find"] = {"matched": found["matched"], "searched": found["searched"],
                            "games": [dict(d, next=list(d["next"])) for d in found["games"]],
                            "continuations": [dict(d, key=list(d["key"])) for d in found["continuations"]]}
+        if a.secure:
+            from .secure import format_bucket_table as format_secure_table
+            doc["secure"] = secure_table(rs, a.bucket)
+            if doc["secure"]:
+                out.write(format_secure_table(doc["secure"]) + "\n")
+            out.write("secure: %d of %d positions offer a securing move; the recorded move took the best %d times, any %d times; harmful moves played %d\n" % (
+                sum(r["offered"] for r in doc["secure"]), sum(r["plies"] for r in doc["secure"]), sum(r["took_best"] for r in doc["secure"]),
+                sum(r["took_any"] for r in doc["secure"]), sum(r["harmful_played"] for r in doc["secure"])))
         if a.moves:
             from .moves import format_bucket_table
             doc["moves"] = moves_table(rs, a.bucket)
