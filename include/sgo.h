@@ -866,6 +866,99 @@ int sgo_session_secure(sgo_ctx *ctx, int n, const int32_t *slots, int side, int3
  * other bits set or more than 1024 workgroups, only queries. */
 int sgo_secure_mode(int mode);
 
+/* ---- life and death: can an enclosed chain be killed when both sides play? ---------------------------------------------------------- */
+/* Per packed record: the table of the enclosed chains (or the one chain asked for), the region each is read in, and for each the
+ * verdict of an exhaustive reader bounded by that region in which BOTH sides play, with unconditional life as the terminal for
+ * "lives" (csrc/sgo_solve.hip).  Everything is integer.  N = S * S.
+ * Inputs of a record: as sgo_tactics_dev reads them ("chains and ladders" above): black / white = the bits a < N of planes 0 / 1; the
+ * to-play flag is the top bit of the last word of plane 0 (NOT a stone); planes 2 / 3 = black / white one ply ago, bits a < N, used
+ * only for the ko test at the root; padding bits and planes 4..15 are never read.
+ * TARGET: a chain (a maximal 4-connected set of stones of one colour), named by any of its points.  Its ANCHOR t is its lowest point
+ * index.  The DEFENDER is its colour X, the ATTACKER the other colour O.
+ * DEFAULT REGION M of a target: R = the maximal 4-connected set of points that are NOT O stones and that contains the target (the
+ * REGION of O of the "unconditional life" section that holds it: X stones and empty points together).  M = R plus every O chain that
+ * has at least one liberty and whose EVERY liberty lies in R.  (Without these the points of attacker stones captured inside an eye
+ * would become unplayable, and every nakade would be misread.  An O chain without a liberty occurs only in an illegal record and is
+ * not added.)  A caller may give M explicitly instead; it is masked to the board and otherwise taken as it is.  Moves of both
+ * sides are confined to the points of M that are empty at the time of the move.  region_empty = the empty points of M at the root.
+ * ALLOWED, for the side to move with `prev` = that side's stones one ply ago:  rules = 0: exactly the ALLOWED of the "chains and
+ * ladders" section (sgo_legal_moves).  rules = 1 ("sound"): additionally the points the "move outcomes" section calls
+ * forbidden_sound: EMPTY points that are not the KO point (prev & ~own is exactly one point, and it is that point) and on which the
+ * stone stands after one ply of sgo_make_play.  The inherited rule forbids a point without an empty neighbour that captures nothing
+ * even when it joins a chain that keeps a liberty, and that is otherwise the connecting move that saves a group.  EVERY VERDICT HOLDS
+ * FOR THE CHOSEN RULE SET.
+ * THE READER: read(pos, mover, prev, depth) -> DEAD | ALIVE; the root has depth 0, a child depth + 1.  On entry: nodes += 1; if nodes >
+ * max_nodes or depth > SGO_SOLVE_MAX_DEPTH the WHOLE QUERY ends unknown at once, whatever the branches above had found.  Then, if
+ * the stone on t belongs to alive_X(pos) of the "unconditional life" section (computed on the whole board of pos): ALIVE.
+ *   Attacker to move:  for every ALLOWED empty point a of M in ascending index order: play it (one ply of sgo_make_play); the stone on
+ *     t is gone: DEAD; else the stone just played is gone: next point; else recurse with the defender to move: DEAD if that returns
+ *     DEAD.  Then, ONLY while the ko test forbids the attacker an empty point of M (prev & ~own is exactly one point, and that point
+ *     is an empty point of M), the WAIT, encoded as move N: the same stones, the defender to move, depth + 1: DEAD if that returns
+ *     DEAD.  Otherwise ALIVE.  The attacker never passes otherwise (a pass could only be answered by a pass).  The wait is not a
+ *     convenience: the ko test forbids the replay on a point where exactly ONE stone was just captured whether or not that is a ko,
+ *     and the kill of a straight three, a bulky five or a square four ends with such a replay when no other point of M is left.
+ *   Defender to move:  for every ALLOWED empty point a of M in ascending index order: play it; the stone on t or the stone just played
+ *     is gone: next point; else recurse with the attacker to move: ALIVE if that returns ALIVE.  Then the PASS, encoded as move N: the
+ *     same stones, the attacker to move, depth + 1: ALIVE if that returns ALIVE.  Otherwise DEAD.  The pass is what reads a seki as
+ *     "not killable".
+ *   `prev` of a child = the child's mover's stones BEFORE the parent's move, and `prev` at the root = plane 2 (black) / 3 (white) of the
+ *   record when the root's mover is the record's side to move, otherwise no ko restriction: exactly as the tactics reader.  After a pass
+ *   the child's `prev` equals its stones, so the formula leaves no ko restriction.
+ * WHAT IS LEFT OUT.  No transposition table and no move-ordering heuristics: the traversal order is fixed, so the node counts pin it,
+ * and a region of a dozen empty points is about what the budgets reach.  Ko is the one-ply approximation: the defender may pass and
+ * retake, and the attacker has no ko threats -- its wait is no threat: the defender may use that ply to settle the ko, and only a
+ * defender that passes too lets the ban lapse.  A chain is judged ALONE, not its group: a neighbour chain of the same colour may die
+ * while the target lives.  An ALIVE verdict means "the attacker cannot capture it inside M"; it does not mean "two eyes" -- an
+ * attacker move outside M is not read, so M must be closed for the verdict to say something about the game.
+ * QUERIES per row:  A = the attacker moves first, always run;  D = the defender moves first, run only when A returned DEAD.  The node
+ * counter restarts per query, and a query that ends unknown reports its count at the moment it ended.
+ * RESULT ROW int32[8] = {anchor, colour (+1 black, -1 white), region_empty, status, kill_move, live_move, nodes_A, nodes_D}.
+ *   kill_move = the first root move by which A kills (N = the wait), -1 otherwise and when A is unknown.
+ *   live_move = the first root candidate by which
+ *   D lives (N = the pass), -1 otherwise.  status bits: 1 = A returned DEAD, 2 = D ran and returned DEAD, 4 = A unknown, 8 = D unknown,
+ *   16 = D ran, 32 = SGO_SOLVE_OPEN: region_empty is 0 or greater than max_region, no query runs (moves -1, nodes 0),
+ *   64 = SGO_SOLVE_NO_STONE: an asked point is empty or outside the board; anchor and moves are -1, the other words 0, the region empty.
+ *
+ * sgo_solve_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_n_targets int32 [n], d_rows int32 [n][max_targets][8], d_regions uint32 [n][max_targets][sgo_plane_words(S)]: the M used, in the
+ * bit order of the legal bitsets, bits a >= N zero.  Of a row's table rows and region sets only the first min(n_targets, max_targets)
+ * are written.  d_ask NULL, or d_ask[i] < 0: ENUMERATE for that row: the table lists, in ascending anchor order, the chains of either
+ * colour that are not in alive_X of the record and whose default region has 1..max_region empty points; n_targets = their true number.
+ * d_ask[i] >= 0: exactly one table row, for the chain on that point (n_targets = 1), read in row i of d_region [n][sgo_plane_words(S)]
+ * when d_region is not NULL, otherwise in its default region.  A row whose record index is outside [0, n_records) gives n_targets = 0
+ * and untouched rows.  TWO launches on `stream` (k_solve_targets, k_solve_read), no allocation, no synchronisation, capturable; n ==
+ * 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, rules outside {0, 1}, max_region
+ * outside [1, SGO_SOLVE_MAX_REGION], max_nodes outside [1, SGO_SOLVE_MAX_NODES], max_targets outside [1, SGO_SOLVE_MAX_TARGETS], a NULL
+ * d_records or output.  SGO_SOLVE_MAX_NODES bounds the longest launch a single query can cause: measured on one MI355X
+ * (profiles/solve_ab.json) a node takes 4.4 us at 19x19, a query that spends all 65 536 nodes 0.29 s, so the cap stands as it is. */
+#define SGO_SOLVE_MAX_REGION 32
+#define SGO_SOLVE_MAX_NODES 65536
+#define SGO_SOLVE_MAX_TARGETS 64
+#define SGO_SOLVE_MAX_DEPTH 80
+#define SGO_SOLVE_A_DEAD 1
+#define SGO_SOLVE_D_DEAD 2
+#define SGO_SOLVE_A_UNKNOWN 4
+#define SGO_SOLVE_D_UNKNOWN 8
+#define SGO_SOLVE_D_RAN 16
+#define SGO_SOLVE_OPEN 32
+#define SGO_SOLVE_NO_STONE 64
+int sgo_solve_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask,
+                  const uint32_t *d_region, int rules, int max_region, int max_nodes, int max_targets, int32_t *d_n_targets,
+                  int32_t *d_rows, uint32_t *d_regions, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests.
+ * ask (or NULL) int32 [n], region (or NULL) uint32 [n][sgo_plane_words(S)].  Table rows and region sets beyond min(n_targets,
+ * max_targets) come back as the caller filled them. */
+int sgo_solve(int S, int n, const uint32_t *records, const int32_t *ask, const uint32_t *region, int rules, int max_region, int max_nodes,
+              int max_targets, int32_t *n_targets, int32_t *rows, uint32_t *regions);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: ask (or NULL) [n], region (or NULL) [n][sgo_plane_words(S)], status [n], n_targets [n], rows [n][max_targets][8],
+ * regions [n][max_targets][sgo_plane_words(S)].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: that
+ * row's outputs are left as the caller filled them, as are the table rows beyond min(n_targets, max_targets) of every row.  The
+ * context is only read; a slot may be listed repeatedly.  SGO_ERR_ARG: the bounds of sgo_solve_dev, a slot outside the context, a
+ * NULL slot list or output. */
+int sgo_session_solve(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int max_region,
+                      int max_nodes, int max_targets, int32_t *status, int32_t *n_targets, int32_t *rows, uint32_t *regions, void *stream);
+
 /* ---- influence: who holds what right now, and by how much?  (an ESTIMATE, not a proof) --------------------------------------------- */
 /* Per packed record: Bouzy's dilation / erosion map of the stones, the territory and moyo sets read off it, and an area-score
  * estimate (csrc/sgo_influence.hip).  The heuristic counterpart of the "unconditional life" section: that one is proved and says

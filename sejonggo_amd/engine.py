@@ -827,6 +827,20 @@ class SessionEngine(SelfPlayEngine):
         out.status = self._analysis(self.lib.sgo_session_secure, slots, (int(side),), out.table, out.sets, out.counts)
         return out
 
+    def solve(self, slots, ask=None, region=None, rules=1, max_region=12, max_nodes=4096, max_targets=None):
+        """Life and death in the root positions of the listed holding sessions (sgo_session_solve; include/sgo.h "life and
+        death"): a solve.Solve with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays
+        zero).  ask None: every enclosed chain; else one point per slot (-1: enumerate), read in row i of `region` (uint32 [n, NW])
+        when given.  A bounded reader, not a proof about the game.  Boards and trees are only read."""
+        from .solve import MAX_TARGETS, Solve, check_args, host_inputs
+        n, NW, mt = len(slots), self.lib.sgo_plane_words(self.S), int(max_targets or MAX_TARGETS)
+        check_args(rules, max_region, max_nodes, mt)
+        ask, region = host_inputs(self.S, n, ask, region)
+        out = Solve(self.S, np.zeros(n, np.int32), np.zeros((n, mt, 8), np.int32), np.zeros((n, mt, NW), np.uint32))
+        out.status = self._analysis(self.lib.sgo_session_solve, slots, (_lib.ptr(ask), _lib.ptr(region), int(rules), int(max_region), int(max_nodes), mt),
+                                    out.n_targets, out.rows, out.regions)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

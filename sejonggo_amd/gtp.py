@@ -271,6 +271,16 @@ class DeviceSejongGoEngine(object):
         v = self._held(self.engine.secure([self.slot], side))
         return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
 
+    def solve(self, ask=None, region=None, rules=1, max_nodes=4096, max_region=12):
+        """Life and death in the position on the board (engine.SessionEngine.solve): (a solve.Solve with one row, the stones int8
+        [S * S], +1 black).  ask None: every enclosed chain; else the chain on that point, read in `region` (a list of points)
+        when given."""
+        from .rollout import real_board
+        from .solve import region_words
+        v = self._held(self.engine.solve([self.slot], None if ask is None else [ask], None if region is None else region_words(self.size, region)[None],
+                                         rules=rules, max_region=max_region, max_nodes=max_nodes))
+        return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -322,7 +332,7 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "sgo-secure", "quit"])
+                          "sgo-estimate", "sgo-secure", "sgo-solve", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -546,6 +556,40 @@ class GTPEngine(object):
         v, stones = self._engine_method("secure")(side)
         return format_board(v, 0, stones, self._vertex, MIN_GAIN if k is None else k)
 
+    def sgo_solve(self, *words):
+        """Private extension `sgo-solve [VERTEX [REGION-VERTEX ...]] [nodes K] [inherited]`: can the chain on VERTEX be killed when
+        both sides play (include/sgo.h "life and death")?  One line `V colour empty E verdict kill K live L nodes A D` -- verdict
+        alive / unsettled / dead / unknown / open, kill the attacker's first killing move, live the defender's first saving move
+        (`pass`: it need not answer), the node counts of the two queries -- then the board from the top row down: X / O a stone, * an
+        empty point of the region M the reader is confined to, K / L the kill / live move (! where they are one point), . anything
+        else.  Further vertices give M explicitly; `nodes K` sets the budget per query (default 4096); `inherited` reads under the
+        legal-move rule as inherited (rules = 0) instead of the sound one.  Without a vertex: one line per enclosed chain.  The
+        verdict of a bounded reader inside M, not a proof about the game."""
+        from .solve import MAX_NODES, format_board, format_target
+        pts, nodes, rules, words = [], None, 1, list(words)
+        while words:
+            w = words.pop(0)
+            if w == "inherited" and rules == 1:
+                rules = 0
+            elif w == "nodes" and nodes is None and words and words[0].isdigit() and 1 <= int(words[0]) <= MAX_NODES:
+                nodes = int(words.pop(0))
+            else:
+                try:
+                    x, y = self.parse_move(w)
+                except Exception:
+                    raise GTPFailure("syntax error")
+                if not (0 <= x < self.size and 0 <= y < self.size):
+                    raise GTPFailure("syntax error")
+                pts.append(y * self.size + x)
+        N = self.size * self.size
+        v, stones = self._engine_method("solve")(pts[0] if pts else None, pts[1:] or None, rules=rules, max_nodes=nodes or 4096)
+        targets = v.targets_of(0)
+        if not pts:
+            return "\n".join(format_target(t, self._vertex, N) for t in targets)
+        if targets[0].verdict is None:
+            raise GTPFailure("no stone on %s" % self._vertex(pts[0]))
+        return format_target(targets[0], self._vertex, N) + "\n" + format_board(self.size, stones, v.region(0, 0), targets[0])
+
     def _influence(self, words):
         from .influence import PRESETS
         preset, dead = None, "life"
@@ -577,7 +621,7 @@ class GTPEngine(object):
 
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
-               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -444,6 +444,18 @@ class DeviceRecords(object):
                     torch.zeros((0, 4, self.NW), dtype=torch.int32, device=self.device), torch.zeros((0, 8), dtype=torch.int32, device=self.device))
         return secure_dev(self.S, self.records, index, side, self.lib)
 
+    def solve(self, index, rules=1, max_region=12, max_nodes=4096, max_targets=16):
+        """(n_targets int32 [n], rows int32 [n, max_targets, 8], regions int32 [n, max_targets, NW] holding the uint32 bit patterns)
+        device tensors of the listed records, every enclosed chain enumerated (sgo_solve_dev, two launches; include/sgo.h "life and
+        death").  Rows behind min(n_targets, max_targets) are zero; an index outside the object gives n_targets 0."""
+        from .solve import solve_dev
+        torch = self.torch
+        index = self._index(index)
+        if int(index.shape[0]) == 0:
+            return (torch.zeros(0, dtype=torch.int32, device=self.device), torch.zeros((0, int(max_targets), 8), dtype=torch.int32, device=self.device),
+                    torch.zeros((0, int(max_targets), self.NW), dtype=torch.int32, device=self.device))
+        return solve_dev(self.S, self.records, index, None, None, rules, max_region, max_nodes, max_targets, self.lib)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -654,6 +666,14 @@ class RecordSet(object):
                                    lambda table, sets, counts: Secure(self.S, _host(table, np.int16), _host(sets, np.uint32), _host(counts))):
             ch.to_play = _host(self.backend.to_play(self._record_index(ch)), np.int8)
             yield ch
+
+    def solve(self, rules=1, max_region=12, max_nodes=4096, max_targets=16, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `solve`, a solve.Solve with one row per RECORD of the chunk (one
+        backend call per chunk), rows as in `life`: the enclosed chains of every position and what a bounded reader says of each.
+        Records that were not written give n_targets 0.  stones=True adds ch.stones as `tactics` does."""
+        from .solve import Solve
+        return self._per_record("solve", lambda index: self.backend.solve(index, rules, max_region, max_nodes, max_targets),
+                                lambda n_targets, rows, regions: Solve(self.S, _host(n_targets), _host(rows), _host(regions, np.uint32)), stones)
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -936,6 +956,28 @@ def secure_table(record_set, width=20):
     return bucket_table(np.array(ply), np.array(action), np.stack(played), np.stack(counts), record_set.S, width)
 
 
+def solve_table(record_set, width=20, **kw):
+    """The table of `--solve` (solve.bucket_table) from one RecordSet.solve pass: per bucket of `width` moves the positions that
+    hold an unsettled enclosed chain, how often the recorded move was its kill or live move, and the share of unknown rows.  Set-up
+    stones are left out."""
+    from .solve import bucket_table
+    ply, action, rows, n_targets = [], [], [], []
+    for ch in record_set.solve(**kw):
+        v = ch.solve
+        first = {}
+        for e in np.flatnonzero(ch.valid & ~ch.setup):
+            g, r = int(ch.game[e]), int(ch.index[e])
+            number = first.get(g, 0)
+            first[g] = number + 1
+            ply.append(number)
+            action.append(int(ch.action[e]))
+            rows.append(v.rows[r])
+            n_targets.append(v.n_targets[r])
+    if not ply:
+        return []
+    return bucket_table(np.array(ply), np.array(action), np.stack(rows), np.array(n_targets), width)
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -984,6 +1026,9 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--secure", action="store_true",
                     help="per 20-move bucket: the positions that offer a securing move (one more stone that makes at least 2 more stones "
                          "and points pass-alive), how often the recorded move took the best one or any, and the harmful moves played")
+    ap.add_argument("--solve", action="store_true",
+                    help="life and death by a bounded reader: per 20-move bucket the positions that hold an unsettled enclosed chain, how "
+                         "often the recorded move was its kill or live move, and the share of rows that ended unknown")
     ap.add_argument("--influence", action="store_true",
                     help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
                          "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
@@ -1052,6 +1097,14 @@ def main(argv=None, out=sys.stdout):
             out.write("secure: %d of %d positions offer a securing move; the recorded move took the best %d times, any %d times; harmful moves played %d\n" % (
                 sum(r["offered"] for r in doc["secure"]), sum(r["plies"] for r in doc["secure"]), sum(r["took_best"] for r in doc["secure"]),
                 sum(r["took_any"] for r in doc["secure"]), sum(r["harmful_played"] for r in doc["secure"])))
+        if a.solve:
+            from .solve import format_bucket_table as format_solve_table
+            doc["solve"] = solve_table(rs, a.bucket)
+            if doc["solve"]:
+                out.write(format_solve_table(doc["solve"]) + "\n")
+            out.write("solve: %d of %d positions hold an unsettled enclosed chain; the recorded move was its kill or live move %d times; unknown rows %d of %d\n" % (
+                sum(r["unsettled"] for r in doc["solve"]), sum(r["plies"] for r in doc["solve"]), sum(r["took"] for r in doc["solve"]),
+                sum(r["unknown"] for r in doc["solve"]), sum(r["rows"] for r in doc["solve"])))
         if a.moves:
             from .moves import format_bucket_table
             doc["moves"] = moves_table(rs, a.bucket)

@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt] [--moves] [--influence] [--secure]
+                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -293,6 +293,28 @@ def add_secure(rows, game, record_set=None):
     return rows
 
 
+def solve_rows(game, record_set):
+    """{move number: flags} of the B / W moves of `game` (solve.review_flags) from one RecordSet.solve pass over a set that holds
+    the game as its only record: the verdicts of the same chain in the position before and after the move."""
+    from .solve import review_flags
+    out = {}
+    for ch in record_set.solve(stones=True):
+        v = ch.solve
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = review_flags(game.size, action, colour, ch.stones[r], v.targets_of(r), ch.stones[r + 1], v.targets_of(r + 1),
+                                  lambda a: vertex(a, game.size))
+    return out
+
+
+def add_solve(rows, game, record_set=None):
+    """Adds `solve_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = solve_rows(game, rs)
+    for row in rows:
+        row["solve_flags"] = list(found.get(row["move_number"], []))
+    return rows
+
+
 def influence_rows(game, record_set, komi=0.0, dead="life"):
     """{move number: {"estimate", "gain"}} of the B / W moves of `game` (influence.review_fields) from one RecordSet.influence pass
     over a set that holds the game as its only record: the estimate in front of the move, and what the move did to the margin."""
@@ -340,7 +362,7 @@ def format_row(row):
         from .influence import score_text
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
-        list(row.get("moves_flags") or []) + list(row.get("secure_flags") or [])
+        list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -408,13 +430,17 @@ def main(argv=None, out=sys.stdout):
                     help="flag what each played move proved in one ply: secures K (stones and points made pass-alive), missed-secure K "
                          "at V, destroys K (flags from a proof about one ply, not verdicts: the answer is not read).  Like "
                          "--influence it loads no net when nothing else asks for one")
+    ap.add_argument("--solve", action="store_true",
+                    help="flag what each played move did to the enclosed chains a bounded life-and-death reader decides: kills V, saves "
+                         "V, missed-kill V at K, missed-save V at K (flags from a bounded reader, not verdicts).  Like --influence it "
+                         "loads no net when nothing else asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -444,6 +470,8 @@ def main(argv=None, out=sys.stdout):
         add_moves(rows, game)
     if a.secure:
         add_secure(rows, game)
+    if a.solve:
+        add_solve(rows, game)
     if a.influence:
         add_influence(rows, game)
     for row in rows:
