@@ -53,7 +53,8 @@ extern "C" {
  *   (sgo_keys*, sgo_session_keys), the "chains and ladders" section (sgo_tactics*, sgo_session_tactics), the "unconditional life" section
  *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes), the "move
  *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
- *   section (sgo_secure*, sgo_session_secure). */
+ *   section (sgo_secure*, sgo_session_secure), the "life and death" section (sgo_solve*, sgo_session_solve), the "capturing races"
+ *   section (sgo_race*, sgo_session_race). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -958,6 +959,101 @@ int sgo_solve(int S, int n, const uint32_t *records, const int32_t *ask, const u
  * NULL slot list or output. */
 int sgo_session_solve(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int max_region,
                       int max_nodes, int max_targets, int32_t *status, int32_t *n_targets, int32_t *rows, uint32_t *regions, void *stream);
+
+/* ---- capturing races: which of two chains in contact falls first? ------------------------------------------------------------------ */
+/* Per packed record: the table of the pairs of a black and a white chain that lean on each other short of liberties (or the one pair
+ * asked for), the region each pair is read in, and for EACH of the two chains the verdict of an exhaustive reader bounded by that
+ * region in which both sides play and the other chain can be captured back (csrc/sgo_race.hip).  Everything is integer.  N = S * S.
+ * Inputs of a record: exactly as sgo_solve_dev reads them ("life and death" above): black / white = the bits a < N of planes 0 / 1;
+ * the to-play flag is NOT a stone; planes 2 / 3 are used only for the ko test at the root; padding bits and planes 4..15 are never
+ * read.  rules in {0, 1} and ALLOWED have the meaning of the "life and death" section.
+ * PAIR: a black chain B and a white chain W (maximal 4-connected sets of stones of one colour).  Their ANCHORS are the lowest point
+ * index of each; lib(B), lib(W) are their liberties (the empty points 4-adjacent to a stone of the chain).  They are IN CONTACT when a
+ * stone of one is 4-adjacent to a stone of the other, or when lib(B) & lib(W) is not empty (a race across a shared liberty without
+ * touching stones is a race too).
+ * DEFAULT REGION M of a pair: M0 = lib(B) | lib(W).  M1 = M0 plus every empty point 4-adjacent to a point of M0 (the second-order
+ * liberties, so that an extension along a corridor stays readable).  M = M1 plus every chain other than B and W, of either colour,
+ * that has at least one liberty and whose EVERY liberty lies in M1 (the rule of the "life and death" section, for its reason: without
+ * it the points of stones captured inside an eye become unplayable and every nakade race is misread; the test is against M1, in one
+ * pass, not iterated).  A caller may give M explicitly instead; it is masked to the board and otherwise taken as it is.
+ * region_empty = the empty points of M at the root.  Moves of both sides are confined to the points of M that are empty at the time
+ * of the move.
+ * THE READER: read(pos, mover, prev, depth) -> CAUGHT | SAFE, for one DEFENDER racer, the stone on point tD (the anchor of its chain at
+ * the root); the ATTACKER's racer is the stone on point tA (the other anchor).  Node counting, the rule that ends the WHOLE QUERY
+ * unknown (nodes > max_nodes or depth > SGO_RACE_MAX_DEPTH), the ascending candidate order, the `prev` of a child and of the root and
+ * the pass after which no ko restriction is left are word for word those of the "life and death" reader.  On entry, after the node
+ * is counted: L = the liberties of the chain on tD on the whole board.  If L has a point outside M, or |L| > max_libs: SAFE (the
+ * racer has escaped).  The unconditional-life test of the "life and death" reader is NOT made here.
+ *   Attacker to move:  for every ALLOWED empty point a of M in ascending index order: play it; the stone on tD is gone: CAUGHT; else
+ *     the stone just played is gone: next point; else recurse with the defender to move: CAUGHT if that returns CAUGHT.  Then the WAIT
+ *     (move N) under exactly the condition of the "life and death" reader (the ko test forbids the attacker an empty point of M):
+ *     CAUGHT if that returns CAUGHT.  Otherwise SAFE.  The attacker never passes otherwise.
+ *   Defender to move:  for every ALLOWED empty point a of M in ascending index order: play it; the stone on tD or the stone just played
+ *     is gone: next point; else the stone on tA is gone (the defender captured the attacker's racer): SAFE with move a; else recurse
+ *     with the attacker to move: SAFE if that returns SAFE.  Then the PASS (move N): SAFE if that returns SAFE; this is what reads a
+ *     seki as SAFE for both.  Otherwise CAUGHT.
+ * WHAT IS LEFT OUT.  No transposition table and no move ordering: the traversal is fixed and the node counts pin it.  Ko is the
+ * one-ply approximation.  A racer whose stone on tA is captured has lost: a snapback under the captured stones is not read.  Moves
+ * outside M are not read.  Helper chains matter only through the inner-chain rule.  A verdict is about the two CHAINS, not their groups.
+ * QUERIES per pair, for each racer as the defender:  A = the attacker moves first, always run;  D = the defender moves first, run only
+ * when A returned CAUGHT.  The node counter restarts per query; a pair costs up to four queries.
+ * RESULT ROW int32[16] = {anchor_b, anchor_w, |lib(B)|, |lib(W)|, |lib(B) & lib(W)|, region_empty, status, 0 (reserved, written),
+ *   catch_b, save_b, catch_w, save_w, nodes of A and of D for the black racer, nodes of A and of D for the white racer}.
+ *   catch_b = the first root move by which white, moving first, catches the black racer (N = the wait); save_b = the first root
+ *   candidate by which black, moving first, saves it (N = the pass); catch_w / save_w the same with the colours exchanged.  Moves are
+ *   -1 and nodes 0 under the conditions of the solve row (no such move, the query unknown or not run).
+ *   status: for the black racer SGO_RACE_A_CAUGHT 1, SGO_RACE_D_CAUGHT 2, SGO_RACE_A_UNKNOWN 4, SGO_RACE_D_UNKNOWN 8, SGO_RACE_D_RAN 16;
+ *   for the white racer the same five shifted left by SGO_RACE_WHITE_SHIFT = 8.  SGO_RACE_OPEN: region_empty is 0 or above max_region,
+ *   no query runs.  SGO_RACE_NO_PAIR: an asked point is empty or off the board, or the two asked stones have one colour; anchors and
+ *   moves are -1, the other words 0, the region empty.
+ *   A racer is `safe` when A is not CAUGHT, `unsettled` when A is CAUGHT and D is not, `caught` when both are, `unknown` when a query
+ *   of it ended unknown.
+ *
+ * sgo_race_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_n_pairs int32 [n], d_rows int32 [n][max_pairs][16], d_regions uint32 [n][max_pairs][sgo_plane_words(S)]: the M used, bits a >= N
+ * zero.  d_ask NULL, or d_ask[i][0] < 0 (d_ask int32 [n][2]): ENUMERATE: every pair in contact with 1 <= |lib(B)| <= max_libs, 1 <=
+ * |lib(W)| <= max_libs and region_empty in 1..max_region, in ascending (anchor_b, anchor_w) order; n_pairs = their true number; only
+ * min(n_pairs, max_pairs) rows and region sets are written and everything behind them stays untouched.  d_ask[i] = {p, q} with p >=
+ * 0: exactly one row (n_pairs = 1), for the chains on p and q in either colour order; contact and the liberty bounds are not required
+ * (the reader's own terminal speaks when a racer has more than max_libs liberties); read in row i of d_region
+ * [n][sgo_plane_words(S)] when that is not NULL.  A row whose record index is outside [0, n_records) gives n_pairs = 0 and untouched
+ * rows.  TWO launches on `stream` (k_race_pairs, k_race_read), no allocation, no synchronisation, capturable; n == 0 is a no-op; rows
+ * >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, rules outside {0, 1}, max_libs outside [1,
+ * SGO_RACE_MAX_LIBS], max_region outside [1, SGO_RACE_MAX_REGION], max_nodes outside [1, SGO_RACE_MAX_NODES], max_pairs outside [1,
+ * SGO_RACE_MAX_PAIRS], a NULL d_records or output.  SGO_RACE_MAX_NODES bounds the longest launch a single query can cause: measured on
+ * one MI355X (profiles/race_ab.json) a node takes 3.7 us at 19x19 with one racer of the pair reading and 5.2 us at 9x9 with both, and
+ * a query that spends 65 536 nodes took 0.32 s there, longer than the 0.29 s the "life and death" cap allows; so the cap is HALF of
+ * that section's, 32 768 nodes. */
+#define SGO_RACE_MAX_LIBS 8
+#define SGO_RACE_MAX_REGION 32
+#define SGO_RACE_MAX_NODES 32768
+#define SGO_RACE_MAX_PAIRS 64
+#define SGO_RACE_MAX_DEPTH 80
+#define SGO_RACE_A_CAUGHT 1
+#define SGO_RACE_D_CAUGHT 2
+#define SGO_RACE_A_UNKNOWN 4
+#define SGO_RACE_D_UNKNOWN 8
+#define SGO_RACE_D_RAN 16
+#define SGO_RACE_WHITE_SHIFT 8
+#define SGO_RACE_OPEN (1 << 16)
+#define SGO_RACE_NO_PAIR (1 << 17)
+int sgo_race_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask,
+                 const uint32_t *d_region, int rules, int max_libs, int max_region, int max_nodes, int max_pairs, int32_t *d_n_pairs,
+                 int32_t *d_rows, uint32_t *d_regions, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests.
+ * ask (or NULL) int32 [n][2], region (or NULL) uint32 [n][sgo_plane_words(S)].  Table rows and region sets beyond min(n_pairs,
+ * max_pairs) come back as the caller filled them. */
+int sgo_race(int S, int n, const uint32_t *records, const int32_t *ask, const uint32_t *region, int rules, int max_libs, int max_region,
+             int max_nodes, int max_pairs, int32_t *n_pairs, int32_t *rows, uint32_t *regions);
+/* The root positions of the listed HOLDING session slots of `ctx`, read in place; waits for `stream`.  HOST arrays: ask (or NULL)
+ * [n][2], region (or NULL) [n][sgo_plane_words(S)], status [n], n_pairs [n], rows [n][max_pairs][16], regions
+ * [n][max_pairs][sgo_plane_words(S)].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: that row's
+ * outputs are left as the caller filled them, as are the table rows beyond min(n_pairs, max_pairs) of every row.  The context is only
+ * read; a slot may be listed repeatedly.  SGO_ERR_ARG: the bounds of sgo_race_dev, a slot outside the context, a NULL slot list or
+ * output. */
+int sgo_session_race(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int max_libs,
+                     int max_region, int max_nodes, int max_pairs, int32_t *status, int32_t *n_pairs, int32_t *rows, uint32_t *regions,
+                     void *stream);
 
 /* ---- influence: who holds what right now, and by how much?  (an ESTIMATE, not a proof) --------------------------------------------- */
 /* Per packed record: Bouzy's dilation / erosion map of the stones, the territory and moyo sets read off it, and an area-score

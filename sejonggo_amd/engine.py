@@ -841,6 +841,21 @@ class SessionEngine(SelfPlayEngine):
                                     out.n_targets, out.rows, out.regions)
         return out
 
+    def race(self, slots, ask=None, region=None, rules=1, max_libs=4, max_region=8, max_nodes=1024, max_pairs=None):
+        """Capturing races in the root positions of the listed holding sessions (sgo_session_race; include/sgo.h "capturing
+        races"): a race.Race with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays zero).
+        ask None: every pair in contact; else two points per slot ((-1, -1): enumerate), read in row i of `region` (uint32 [n, NW])
+        when given.  A bounded reader, not a proof about the game.  Boards and trees are only read."""
+        from .race import MAX_PAIRS, Race, check_args, host_inputs
+        n, NW, mp = len(slots), self.lib.sgo_plane_words(self.S), int(max_pairs or MAX_PAIRS)
+        check_args(rules, max_libs, max_region, max_nodes, mp)
+        ask, region = host_inputs(self.S, n, ask, region)
+        out = Race(self.S, np.zeros(n, np.int32), np.zeros((n, mp, 16), np.int32), np.zeros((n, mp, NW), np.uint32))
+        out.status = self._analysis(self.lib.sgo_session_race, slots,
+                                    (_lib.ptr(ask), _lib.ptr(region), int(rules), int(max_libs), int(max_region), int(max_nodes), mp),
+                                    out.n_pairs, out.rows, out.regions)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

@@ -281,6 +281,12 @@ class DeviceSejongGoEngine(object):
                                          rules=rules, max_region=max_region, max_nodes=max_nodes))
         return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
 
+    def race(self, ask=None, rules=1, max_libs=4, max_nodes=1024, max_region=8):
+        """Capturing races in the position on the board (engine.SessionEngine.race): a race.Race with one row.  ask None: every
+        pair in contact; else the pair on those two points."""
+        return self._held(self.engine.race([self.slot], None if ask is None else [ask], None, rules=rules, max_libs=max_libs,
+                                           max_region=max_region, max_nodes=max_nodes))
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -332,7 +338,7 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "sgo-secure", "sgo-solve", "quit"])
+                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -590,6 +596,42 @@ class GTPEngine(object):
             raise GTPFailure("no stone on %s" % self._vertex(pts[0]))
         return format_target(targets[0], self._vertex, N) + "\n" + format_board(self.size, stones, v.region(0, 0), targets[0])
 
+    def sgo_race(self, *words):
+        """Private extension `sgo-race [VERTEX VERTEX] [libs K] [nodes K] [inherited]`: which of two chains in contact falls first
+        (include/sgo.h "capturing races")?  One line per pair `B W libs b w shared s empty E outcome black catch C save S white
+        catch C save S nodes Ab Db Aw Dw` -- B / W the lowest point of the black / white chain, outcome `black wins`, `white wins`,
+        `first to move wins`, `standoff`, `open` or the two racer words (safe / unsettled / caught / unknown), catch the other
+        side's first catching move (`wait`: it waits out a ko ban), save the racer's own first saving move (`pass`: it need not
+        answer).  With two vertices: that pair only; without: every pair in contact whose chains have at most `libs K` liberties
+        (default 4).  `nodes K` sets the budget per query (default 1024); `inherited` reads under the legal-move rule as inherited
+        (rules = 0).  The verdict of a bounded reader inside the pair's region, not a proof about the game."""
+        from .race import MAX_LIBS, MAX_NODES, format_pair
+        pts, nodes, libs, rules, words = [], None, None, 1, list(words)
+        while words:
+            w = words.pop(0)
+            if w == "inherited" and rules == 1:
+                rules = 0
+            elif w == "nodes" and nodes is None and words and words[0].isdigit() and 1 <= int(words[0]) <= MAX_NODES:
+                nodes = int(words.pop(0))
+            elif w == "libs" and libs is None and words and words[0].isdigit() and 1 <= int(words[0]) <= MAX_LIBS:
+                libs = int(words.pop(0))
+            else:
+                try:
+                    x, y = self.parse_move(w)
+                except Exception:
+                    raise GTPFailure("syntax error")
+                if not (0 <= x < self.size and 0 <= y < self.size):
+                    raise GTPFailure("syntax error")
+                pts.append(y * self.size + x)
+        if len(pts) not in (0, 2):
+            raise GTPFailure("syntax error")
+        N = self.size * self.size
+        v = self._engine_method("race")(tuple(pts) if pts else None, rules=rules, max_libs=libs or 4, max_nodes=nodes or 1024)
+        pairs = v.pairs_of(0)
+        if pts and pairs[0].no_pair:
+            raise GTPFailure("no pair on %s %s" % (self._vertex(pts[0]), self._vertex(pts[1])))
+        return "\n".join(format_pair(p, self._vertex, N) for p in pairs)
+
     def _influence(self, words):
         from .influence import PRESETS
         preset, dead = None, "life"
@@ -621,7 +663,7 @@ class GTPEngine(object):
 
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
-               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

@@ -456,6 +456,18 @@ class DeviceRecords(object):
                     torch.zeros((0, int(max_targets), self.NW), dtype=torch.int32, device=self.device))
         return solve_dev(self.S, self.records, index, None, None, rules, max_region, max_nodes, max_targets, self.lib)
 
+    def race(self, index, rules=1, max_libs=4, max_region=8, max_nodes=1024, max_pairs=64):
+        """(n_pairs int32 [n], rows int32 [n, max_pairs, 16], regions int32 [n, max_pairs, NW] holding the uint32 bit patterns)
+        device tensors of the listed records, every pair in contact enumerated (sgo_race_dev, two launches; include/sgo.h "capturing
+        races").  Rows behind min(n_pairs, max_pairs) are zero; an index outside the object gives n_pairs 0."""
+        from .race import race_dev
+        torch = self.torch
+        index = self._index(index)
+        if int(index.shape[0]) == 0:
+            return (torch.zeros(0, dtype=torch.int32, device=self.device), torch.zeros((0, int(max_pairs), 16), dtype=torch.int32, device=self.device),
+                    torch.zeros((0, int(max_pairs), self.NW), dtype=torch.int32, device=self.device))
+        return race_dev(self.S, self.records, index, None, None, rules, max_libs, max_region, max_nodes, max_pairs, self.lib)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -674,6 +686,14 @@ class RecordSet(object):
         from .solve import Solve
         return self._per_record("solve", lambda index: self.backend.solve(index, rules, max_region, max_nodes, max_targets),
                                 lambda n_targets, rows, regions: Solve(self.S, _host(n_targets), _host(rows), _host(regions, np.uint32)), stones)
+
+    def race(self, rules=1, max_libs=4, max_region=8, max_nodes=1024, max_pairs=64, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `race`, a race.Race with one row per RECORD of the chunk (one backend
+        call per chunk), rows as in `life`: the pairs of chains in contact of every position and what a bounded reader says of each
+        racer.  Records that were not written give n_pairs 0.  stones=True adds ch.stones as `tactics` does."""
+        from .race import Race
+        return self._per_record("race", lambda index: self.backend.race(index, rules, max_libs, max_region, max_nodes, max_pairs),
+                                lambda n_pairs, rows, regions: Race(self.S, _host(n_pairs), _host(rows), _host(regions, np.uint32)), stones)
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -978,6 +998,29 @@ def solve_table(record_set, width=20, **kw):
     return bucket_table(np.array(ply), np.array(action), np.stack(rows), np.array(n_targets), width)
 
 
+def race_table(record_set, width=20, **kw):
+    """The table of `--race` (race.bucket_table) from one RecordSet.race pass: per bucket of `width` moves the pairs per position,
+    the share of racers of each verdict, and how often the recorded move was a listed catching or saving move of the mover.  Set-up
+    stones are left out."""
+    from .race import bucket_table
+    ply, action, colour, rows, n_pairs = [], [], [], [], []
+    for ch in record_set.race(**kw):
+        v = ch.race
+        first = {}
+        for e in np.flatnonzero(ch.valid & ~ch.setup):
+            g, r = int(ch.game[e]), int(ch.index[e])
+            number = first.get(g, 0)
+            first[g] = number + 1
+            ply.append(number)
+            action.append(int(ch.action[e]))
+            colour.append(int(ch.colour[e]))
+            rows.append(v.rows[r])
+            n_pairs.append(v.n_pairs[r])
+    if not ply:
+        return []
+    return bucket_table(np.array(ply), np.array(action), np.array(colour), np.stack(rows), np.array(n_pairs), record_set.S * record_set.S, width)
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -1029,6 +1072,10 @@ def main(argv=None, out=sys.stdout):
     ap.add_argument("--solve", action="store_true",
                     help="life and death by a bounded reader: per 20-move bucket the positions that hold an unsettled enclosed chain, how "
                          "often the recorded move was its kill or live move, and the share of rows that ended unknown")
+    ap.add_argument("--race", action="store_true",
+                    help="capturing races by a bounded reader: per 20-move bucket the pairs of chains in contact per position, the share of "
+                         "racers that are safe / unsettled / caught / unknown, and how often the recorded move was a listed catching or "
+                         "saving move")
     ap.add_argument("--influence", action="store_true",
                     help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
                          "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
@@ -1105,6 +1152,14 @@ def main(argv=None, out=sys.stdout):
             out.write("solve: %d of %d positions hold an unsettled enclosed chain; the recorded move was its kill or live move %d times; unknown rows %d of %d\n" % (
                 sum(r["unsettled"] for r in doc["solve"]), sum(r["plies"] for r in doc["solve"]), sum(r["took"] for r in doc["solve"]),
                 sum(r["unknown"] for r in doc["solve"]), sum(r["rows"] for r in doc["solve"])))
+        if a.race:
+            from .race import format_bucket_table as format_race_table
+            doc["race"] = race_table(rs, a.bucket)
+            if doc["race"]:
+                out.write(format_race_table(doc["race"]) + "\n")
+            out.write("race: %d pairs in %d positions; %d positions offered the mover a catching or saving move; the recorded move was one %d times; unknown racers %d of %d\n" % (
+                sum(r["pairs"] for r in doc["race"]), sum(r["plies"] for r in doc["race"]), sum(r["chances"] for r in doc["race"]),
+                sum(r["took"] for r in doc["race"]), sum(r["unknown"] for r in doc["race"]), sum(r["racers"] for r in doc["race"])))
         if a.moves:
             from .moves import format_bucket_table
             doc["moves"] = moves_table(rs, a.bucket)

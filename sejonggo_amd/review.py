@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve]
+                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -315,6 +315,27 @@ def add_solve(rows, game, record_set=None):
     return rows
 
 
+def race_rows(game, record_set):
+    """{move number: flags} of the B / W moves of `game` (race.review_flags) from one RecordSet.race pass over a set that holds the
+    game as its only record: each played move against the pairs of the position in front of it."""
+    from .race import review_flags
+    out = {}
+    for ch in record_set.race():
+        v = ch.race
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = review_flags(game.size, action, colour, v.pairs_of(r), lambda a: vertex(a, game.size))
+    return out
+
+
+def add_race(rows, game, record_set=None):
+    """Adds `race_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = race_rows(game, rs)
+    for row in rows:
+        row["race_flags"] = list(found.get(row["move_number"], []))
+    return rows
+
+
 def influence_rows(game, record_set, komi=0.0, dead="life"):
     """{move number: {"estimate", "gain"}} of the B / W moves of `game` (influence.review_fields) from one RecordSet.influence pass
     over a set that holds the game as its only record: the estimate in front of the move, and what the move did to the margin."""
@@ -362,7 +383,8 @@ def format_row(row):
         from .influence import score_text
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
-        list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or [])
+        list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or []) + \
+        list(row.get("race_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -434,13 +456,17 @@ def main(argv=None, out=sys.stdout):
                     help="flag what each played move did to the enclosed chains a bounded life-and-death reader decides: kills V, saves "
                          "V, missed-kill V at K, missed-save V at K (flags from a bounded reader, not verdicts).  Like --influence it "
                          "loads no net when nothing else asks for one")
+    ap.add_argument("--race", action="store_true",
+                    help="flag each played move against the capturing races a bounded reader decides in the position in front of it: "
+                         "wins-race V (the catching or saving move of an unsettled racer V), missed-race V at K (flags from a bounded "
+                         "reader, not verdicts).  Like --influence it loads no net when nothing else asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure or a.solve) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve or a.race) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -472,6 +498,8 @@ def main(argv=None, out=sys.stdout):
         add_secure(rows, game)
     if a.solve:
         add_solve(rows, game)
+    if a.race:
+        add_race(rows, game)
     if a.influence:
         add_influence(rows, game)
     for row in rows:
