@@ -356,13 +356,17 @@ def device_identities():
 
 
 def net_tensors(net):
-    """The weight tensors of a resident net (net.FusedInferenceNet or a torch module), in a fixed order."""
+    """The weight tensors of a resident net (net.FusedInferenceNet or a torch module), in a fixed order.  The packed route's form
+    of the stem (stem_w10, stem_wcol) is a weight tensor like the others: stem_wcol is summed from fp32 weights that only the
+    rank that built the net has, so it travels, it is not re-derived.  What IS re-derived is named in FusedInferenceNet.DERIVED."""
     import torch
     if hasattr(net, "parameters"):
         return [p.data for p in net.parameters()] + [b.data for b in net.buffers()]
     out = []
     for name in ("stem_w", "stem_b"):
         out.append(getattr(net, name))
+    for name in ("stem_w10", "stem_wcol"):
+        out.append(getattr(net, name, None))
     for blk in getattr(net, "blocks", []):
         out.extend(blk)
     for name in ("head_w", "head_b", "p_fc_w", "p_fc_b", "v_fc1_w", "v_fc1_b", "v_fc2_w", "v_fc2_b"):
@@ -381,7 +385,8 @@ def _checksum(tensors):
 
 def broadcast_net(net, src=0):
     """the replicas' weights come from rank `src` (one broadcast per tensor, ~47 MB for the 20-block
-    net), then every rank's checksum is compared so the replicas are provably identical.  Returns
+    net), then net.refresh() where the net has one (the tensors were written in place: its banks and library copies are re-made
+    from them), then every rank's checksum is compared so the replicas are provably identical.  Returns
     {"bytes", "tensors", "checksum", "identical"}; without a process group nothing is sent."""
     import torch
     import torch.distributed as dist
@@ -397,6 +402,10 @@ def broadcast_net(net, src=0):
             t.copy_(c)
         else:
             dist.broadcast(t, src=src)
+    # the net's derived copies (filter banks, a library's own weights) follow the tensors that have just been written -- on the
+    # source rank too, so that every rank has gone through the same calls before the checksums say "identical"
+    if hasattr(net, "refresh"):
+        net.refresh()
     cs = _checksum(ts)
     mine = torch.tensor([cs], dtype=torch.int64, device=_comm_device())
     alls = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]

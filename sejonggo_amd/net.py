@@ -137,6 +137,9 @@ class FusedInferenceNet(object):
     * both 1x1 head convolutions are one [n*t*t, C] x [C, 4] GEMM on the channels-last view.
     """
     in_channels = 32
+    # attributes that hold device copies DERIVED from the weight tensors (distributed.net_tensors lists those): whoever changes
+    # the weights in place calls refresh(), which rewrites these.  Every other device tensor of the object is a weight tensor.
+    DERIVED = ("_banks", "_heads_bank")
 
     def __init__(self, net, dtype=torch.float16, device="cuda"):
         from . import _lib
@@ -203,14 +206,29 @@ class FusedInferenceNet(object):
         per layer (sgo_conv3x3_tower_prepack_dev), not on the evaluation path."""
         if on and self.channels == 256 and self.t <= 19 and not self._banks:
             nbytes = self.lib.sgo_conv3x3_tower_packed_bytes()
-            st = torch.cuda.current_stream().cuda_stream
             for (w1, _, w2, _) in self.blocks:
                 for w in (w1, w2):
-                    bank = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                    self._lib.check(self.lib.sgo_conv3x3_tower_prepack_dev(w.data_ptr(), bank.data_ptr(), st), "sgo_conv3x3_tower_prepack_dev")
-                    self._banks[w.data_ptr()] = bank
+                    self._banks[w.data_ptr()] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._pack_tower()
         self.packed_tower = bool(on) and bool(self._banks)
         return self.packed_tower
+
+    def _pack_tower(self):
+        """Writes every existing filter bank from the current weights of its layer, in place."""
+        st = torch.cuda.current_stream().cuda_stream
+        for (w1, _, w2, _) in self.blocks:
+            for w in (w1, w2):
+                bank = self._banks.get(w.data_ptr())
+                if bank is not None:
+                    self._lib.check(self.lib.sgo_conv3x3_tower_prepack_dev(w.data_ptr(), bank.data_ptr(), st), "sgo_conv3x3_tower_prepack_dev")
+
+    def refresh(self):
+        """After the weight tensors were changed IN PLACE (distributed.broadcast_net, a loaded checkpoint copied into them): re-packs
+        every existing tower bank and the heads bank from them, into the same buffers -- captured engine rounds hold those
+        addresses.  Banks that were never built stay unbuilt."""
+        self._pack_tower()
+        if self._heads_bank is not None:
+            self._pack_heads()
 
     def heads_kernel_ok(self):
         """True for the shapes k_heads is written for: the reference's 256 channels on a supported board size."""
@@ -416,8 +434,10 @@ class NativeNet(FusedInferenceNet):
             pass
 
     def refresh(self):
-        """Re-upload this object's weight tensors into the library's net (and re-pack its banks)."""
+        """Re-upload this object's weight tensors into the library's net (which re-packs its banks), and re-pack this object's own
+        banks (FusedInferenceNet.refresh: the tensor route reads them)."""
         import ctypes as C
+        super().refresh()
         L = self._lib
         nb = len(self.blocks)
         arr = [(C.c_void_p * nb)(*[b[i].data_ptr() for b in self.blocks]) for i in range(4)]
@@ -427,8 +447,6 @@ class NativeNet(FusedInferenceNet):
                          p_fc_b=self.p_fc_b.data_ptr(), v_fc1_w=self.v_fc1_w.data_ptr(), v_fc1_b=self.v_fc1_b.data_ptr(),
                          v_fc2_w=self.v_fc2_w.data_ptr(), v_fc2_b=self.v_fc2_b.data_ptr())
         L.check(self.lib.sgo_net_set_weights(self._net, C.byref(w), torch.cuda.current_stream().cuda_stream), "sgo_net_set_weights")
-        if self._heads_bank is not None:
-            self._pack_heads()
 
     def use_packed_tower(self, on=True):
         on = super().use_packed_tower(on)

@@ -82,6 +82,52 @@ def test_rccl_one_rank_on_the_device(tmp_path):
     _check(_launch(1, tmp_path, backend="nccl"), 1)
 
 
+def _launch_net_worker(mode, tmp_path, world=2, extra=()):
+    import json
+    from sejonggo_amd.distributed import launch_ranks
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    rc = launch_ranks([os.path.join(HERE, "dist_net_worker.py"), mode, str(tmp_path)] + list(extra), world, env=env, timeout=300)
+    assert rc == 0
+    res = [json.load(open(os.path.join(str(tmp_path), "rank%d.json" % r))) for r in range(world)]
+    assert all(x["failed"] == [] for x in res)
+    return res
+
+
+def test_broadcast_reaches_the_packed_stem_and_refreshes_once(tmp_path):
+    """broadcast_net into an object with FusedInferenceNet's tensor attributes, two gloo ranks on the CPU: stem_w10 and stem_wcol
+    travel with the rest (channels-last views included), refresh() runs once per rank, after the last tensor has arrived and
+    before the checksums are compared; a torch module (no refresh) goes the way it went.  The worker checks, this compares ranks."""
+    from sejonggo_amd.distributed import _checksum, net_tensors
+    from tests.dist_net_worker import StandIn
+    res = _launch_net_worker("standin", tmp_path)
+    final = res[0]["checksum"]
+    assert final == _checksum(net_tensors(StandIn(100))) != _checksum(net_tensors(StandIn(101)))
+    for x in res:
+        assert x["refreshed"] == [final] and x["checksum"] == final        # once, on the source too, seeing rank 0's final tensors
+        assert x["tensors"] == len(net_tensors(StandIn(100))) == 2 + 2 + 4 * 2 + 8
+    assert res[0]["module_checksum"] == res[1]["module_checksum"]
+
+
+def test_broadcast_without_a_process_group_sends_and_refreshes_nothing():
+    from sejonggo_amd.distributed import _checksum, broadcast_net, net_tensors
+    from tests.dist_net_worker import StandIn
+    net = StandIn(7)
+    info = broadcast_net(net)
+    assert net.refreshed == [] and info["identical"] and info["tensors"] == 20 and info["checksum"] == _checksum(net_tensors(StandIn(7)))
+
+
+@pytest.mark.gpu
+def test_replicas_evaluate_alike_after_the_broadcast(tmp_path):
+    """Two ranks on one device (gloo lets them share it; with this process three hold the GPU): rank r builds a FusedInferenceNet
+    and a NativeNet from seed 100 + r with every route on, broadcast_net brings rank 0's weights, and every route of
+    tests/test_gpu_net_replicas.py then gives, on both ranks, the bits of a net built from seed 100 on the spot (rank 1 differed
+    in every row before, rank 0 is unchanged) -- all asserted in the worker.  Then both play the same engine game on their
+    replica: replicas with equal seeds play equal games."""
+    res = _launch_net_worker("device", tmp_path, extra=("6",))
+    assert res[0]["n_moves"] == res[1]["n_moves"] > 0 and res[0]["n_steps"] == res[1]["n_steps"]
+    assert res[0]["game"] == res[1]["game"]
+
+
 def test_external_launcher_rendezvous_over_tcp(tmp_path):
     """The driver's way: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P script`.
     No SGO_RDZV_PORT in the environment, so init_from_env must take the launcher's MASTER_ADDR / MASTER_PORT."""
