@@ -12,6 +12,9 @@ its edge, 65504 < f <= 65520), subnormals, zeros and signs (and a -0 among the a
 Layouts: x, skip and y are views into larger buffers (`GUARD_ROWS` pixel rows of NaN before and after x and skip, `Y_FRONT` /
 `Y_BACK` rows of CANARY around y); the expected output covers y's whole buffer.  Tracer launches put non-finite values on the four
 corners and an edge of the middle sample and into skip at pixel M - 1 of a ragged launch; their twin without the tracer is `clean`.
+
+Shapes: the tower at 17x17, 7x7, 19x19 and 1x1 and at the tower shapes of board sizes 5, 7 and 13 (3x3, 5x5, 11x11); k_stem and the
+packed stem at board sizes 5, 7, 13 and 19.
 """
 import functools
 
@@ -270,15 +273,22 @@ def launches(group):
         out.append(tower_launch(2, 19, 19, 4, sk, mixed_taps=True, tracer=True))
         out.append(tower_launch(9, 1, 1, 4, sk, poison=True))
         out.append(tower_launch(1, 17, 17, 5, sk, mixed_taps=True, poison="all"))       # a non-finite bias or weight in every channel
+        # the tower shapes of board sizes 5, 7 and 13: 28.4, 10.2 and 2.1 samples per tile, one tile and 5 / 19 / 107 pixels
+        out.append(tower_launch(29, 3, 3, 6, sk, mixed_taps=True))
+        out.append(tower_launch(11, 5, 5, 0, sk, tracer=True))
+        out.append(tower_launch(3, 11, 11, 1, sk, mixed_taps=True, tracer=True))
     elif group == "stem":
         for r in range(NK):
             out.append(stem_launch(29, 5, 5, r) if r % 2 == 0 else stem_launch(1, 19, 19, r))
         out += [stem_launch(29, 5, 5, 1, poison=True), stem_launch(1, 19, 19, 2, poison=True), stem_launch(29, 5, 5, 3, poison="all")]
+        out += [stem_launch(11, 7, 7, 4), stem_launch(5, 13, 13, 5)]                    # board sizes 7 and 13: 275 and 605 outputs
     elif group == "packed":
         for r in range(8):
             S, n = ((5, 29), (19, 1))[r % 2]
             out.append(packed_launch(S, n, r, (0, 5)[(r // 2) % 2], (1, -1)[(r // 4) % 2]))
         out += [packed_launch(19, 1, 9, 5, 1), packed_launch(19, 1, 20, 0, -1), packed_launch(5, 29, 17, 5, -1)]
+        out += [packed_launch(7, 13, 3, 0, 1), packed_launch(7, 13, 12, 5, -1),         # board sizes 7 and 13, each under both symmetries
+                packed_launch(13, 3, 6, 5, 1), packed_launch(13, 3, 21, 0, -1)]
     else:
         assert group == "bias_act", group
         out = [bias_act_launch(C, 37, sk) for C in (8, 256) for sk in (True, False)]

@@ -82,7 +82,7 @@ def test_rounding_classes_really_round(group):
 def test_tracers_sit_on_corners_and_an_edge_of_the_middle_sample():
     for group in ("tower_skip", "tower_noskip"):
         tr = [L for L in C.launches(group) if L.clean is not None]
-        assert len(tr) == 2 and any(L.M % 256 for L in tr)
+        assert [(L.n, L.h, L.w) for L in tr] == [(3, 7, 7), (2, 19, 19), (11, 5, 5), (3, 11, 11)] and all(L.M % 256 for L in tr)
         for L in tr:
             assert L.n >= 2 and all(i == L.n // 2 for i, _, _ in L.marks)
             assert {(0, 0), (0, L.w - 1), (L.h - 1, 0), (L.h - 1, L.w - 1), (L.h // 2, 0)} == set((y, x) for _, y, x in L.marks)
@@ -97,6 +97,17 @@ def test_tracers_sit_on_corners_and_an_edge_of_the_middle_sample():
                 assert not np.isfinite(L.skip[L.M - 1].astype(np.float64)).all() and not M.same_bits(a[L.M - 1], b[L.M - 1]).all()
                 out[L.M - 1] = False
             assert M.same_bits(a[out], b[out]).all() and not M.same_bits(a[~out], b[~out]).all()
+
+
+def test_every_board_size_has_its_launches():
+    """the tower shapes of board sizes 5, 7, 13 and 19 (S - 2) in both tower groups, k_stem and the packed stem at the boards
+    themselves: each at least once, and at 3x3, 5x5 and 11x11 with more than one tile"""
+    for group in ("tower_skip", "tower_noskip"):
+        shapes = set((L.h, L.w) for L in C.launches(group))
+        assert {(3, 3), (5, 5), (11, 11), (17, 17)} <= shapes, (group, shapes)
+        assert all(any(L.h == t and L.M > 256 and L.M % 256 for L in C.launches(group)) for t in (3, 5, 11)), group
+    assert {(5, 5), (7, 7), (13, 13), (19, 19)} <= set((L.h, L.w) for L in C.launches("stem"))
+    assert {(S, k) for S in (5, 7, 13, 19) for k in (0, 5)} <= set((L.S, L.sym) for L in C.launches("packed"))
 
 
 def test_rounding_helpers_by_hand():

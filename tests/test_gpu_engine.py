@@ -1136,7 +1136,7 @@ def test_stem_conv_kernel(L):
     lib = L.load()
     st = torch.cuda.current_stream().cuda_stream
     torch.manual_seed(3)
-    for (n, h, wd) in [(1, 19, 19), (2, 9, 9), (7, 5, 5), (64, 19, 19), (333, 19, 19), (100, 13, 7)]:
+    for (n, h, wd) in [(1, 19, 19), (2, 9, 9), (7, 5, 5), (64, 19, 19), (333, 19, 19), (100, 13, 7), (37, 7, 7), (9, 13, 13)]:
         x = torch.zeros(n, h, wd, 32, device="cuda", dtype=torch.float16)
         x[..., :16] = (torch.rand(n, h, wd, 16, device="cuda") < 0.3).half()
         x[..., 16] = torch.where(torch.rand(n, 1, 1, device="cuda") < 0.5, 1.0, -1.0).half()
@@ -1281,6 +1281,16 @@ def test_stem_packed_kernel_at_the_headline_batch(L):
         del y
 
 
+# The tower shapes of board sizes 5, 7 and 13 (3x3, 5x5, 11x11), with and without skip.  A 256-pixel tile holds 28.4, 10.2 or 2.1
+# samples of them, so the kernels' split of a pixel index by h * w (its magic-number division by 9, 25 or 121), the sample
+# boundaries inside a tile and the clamped halo rows, which lie in other samples, are exercised as the product launches them:
+# 9 pixels (a sample smaller than its own halo), 261 (one tile and 5 pixels), 275, 525, 363 and 2 057 (9 tiles: tiles % 8 == 1
+# on the XCD walk).
+PRODUCT_TOWER_SHAPES = [(n, h, h, sk) for (n, h) in [(1, 3), (29, 3), (11, 5), (21, 5), (3, 11), (17, 11)] for sk in (True, False)]
+# one exact-integer case per tower size: the three above and 17x17 (19x19 boards; last, its tensors serve the argument checks)
+EXACT_TOWER_SHAPES = [(29, 3, 3), (11, 5, 5), (3, 11, 11), (4, 17, 17)]
+
+
 @pytest.fixture(params=[0, 1], ids=["k_conv8w", "k_conv4w"])
 def tower_kernel(request, L):
     """Both hand-written tower kernels (sgo_conv8w.hpp: one 512-thread workgroup per CU; sgo_conv4w.hpp: two 256-thread
@@ -1296,7 +1306,8 @@ def test_tower_kernels_agree_bit_for_bit(L):
     lib = L.load()
     st = torch.cuda.current_stream().cuda_stream
     torch.manual_seed(11)
-    for (n, h, wd, with_skip) in [(3, 17, 17, True), (64, 7, 7, False), (7, 5, 19, True), (1500, 17, 17, True), (2, 19, 19, False)]:
+    for (n, h, wd, with_skip) in [(3, 17, 17, True), (64, 7, 7, False), (7, 5, 19, True), (1500, 17, 17, True),
+                                  (2, 19, 19, False)] + PRODUCT_TOWER_SHAPES:
         x = torch.relu(torch.randn(n, h, wd, 256, device="cuda") * 0.5).half()
         w = (torch.randn(256, 3, 3, 256, device="cuda") * 0.03).half()
         b = torch.randn(256, device="cuda").half()
@@ -1334,7 +1345,7 @@ def test_packed_tower_kernel(L):
 
     for (n, h, wd, with_skip) in [(1, 7, 7, True), (1, 17, 17, False), (3, 17, 17, True), (5, 17, 17, False), (64, 7, 7, True),
                                   (7, 5, 19, True), (2, 19, 19, False), (333, 17, 17, True), (1024, 17, 17, True),
-                                  (300, 11, 1, False), (9, 1, 1, True), (40, 1, 13, True), (77, 2, 2, False), (700, 9, 9, True)]:
+                                  (300, 11, 1, False), (9, 1, 1, True), (40, 1, 13, True), (77, 2, 2, False), (700, 9, 9, True)] + PRODUCT_TOWER_SHAPES:
         x = (torch.randn(n, h, wd, 256, device="cuda") * 0.5).half()
         w = (torch.randn(256, 3, 3, 256, device="cuda") * 0.03).half()
         b = torch.randn(256, device="cuda").half()
@@ -1386,15 +1397,15 @@ def test_packed_tower_kernel(L):
         assert torch.equal(y, y0)
     del x, skip, y, y0
     # exact integer data
-    n, h, wd = 4, 17, 17
-    x = torch.randint(-2, 3, (n, h, wd, 256), device="cuda").half()
-    w = torch.randint(-1, 2, (256, 3, 3, 256), device="cuda").half()
-    b = torch.randint(-3, 4, (256,), device="cuda").half()
-    y = torch.empty(n, h, wd, 256, device="cuda", dtype=torch.float16)
-    bank = bank_of(w)
-    L.check(lib.sgo_conv3x3_tower_packed_dev(n, h, wd, x.data_ptr(), bank.data_ptr(), b.data_ptr(), None, y.data_ptr(), st))
-    ref = torch.relu(F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b.float(), padding=1)).permute(0, 2, 3, 1)
-    assert float(ref.max()) < 2048 and torch.equal(y.float(), ref)
+    for (n, h, wd) in EXACT_TOWER_SHAPES:
+        x = torch.randint(-2, 3, (n, h, wd, 256), device="cuda").half()
+        w = torch.randint(-1, 2, (256, 3, 3, 256), device="cuda").half()
+        b = torch.randint(-3, 4, (256,), device="cuda").half()
+        y = torch.empty(n, h, wd, 256, device="cuda", dtype=torch.float16)
+        bank = bank_of(w)
+        L.check(lib.sgo_conv3x3_tower_packed_dev(n, h, wd, x.data_ptr(), bank.data_ptr(), b.data_ptr(), None, y.data_ptr(), st))
+        ref = torch.relu(F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b.float(), padding=1)).permute(0, 2, 3, 1)
+        assert float(ref.max()) < 2048 and torch.equal(y.float(), ref), (n, h, wd)
     # errors, not fall-backs
     assert lib.sgo_conv3x3_tower_packed_dev(1, 21, 21, x.data_ptr(), bank.data_ptr(), b.data_ptr(), None, y.data_ptr(), st) < 0
     assert lib.sgo_conv3x3_tower_packed_dev(n, h, wd, x.data_ptr(), None, b.data_ptr(), None, y.data_ptr(), st) < 0
@@ -1484,7 +1495,8 @@ def test_tower_conv_kernel(L, tower_kernel):
     st = torch.cuda.current_stream().cuda_stream
     for (n, h, wd, with_skip) in [(1, 7, 7, True), (1, 17, 17, False), (3, 17, 17, True), (5, 17, 17, True), (5, 17, 17, False),
                                   (64, 7, 7, True), (7, 5, 19, True), (2, 19, 19, False), (333, 17, 17, True), (1024, 17, 17, True),
-                                  (300, 11, 1, False), (9, 1, 1, True), (40, 1, 13, True), (77, 2, 2, False)]:   # degenerate boards: a divisor of 1
+                                  (300, 11, 1, False), (9, 1, 1, True), (40, 1, 13, True), (77, 2, 2, False)   # degenerate boards: a divisor of 1
+                                  ] + PRODUCT_TOWER_SHAPES:
         x = (torch.randn(n, h, wd, 256, device="cuda") * 0.5).half()
         w = (torch.randn(256, 3, 3, 256, device="cuda") * 0.03).half()
         b = torch.randn(256, device="cuda").half()
@@ -1523,13 +1535,13 @@ def test_tower_conv_kernel(L, tower_kernel):
     del x, skip, y, y0
     # exact integer data: every product and sum is representable, so the result must be exact (catches a wrong tap,
     # channel or swizzle that random data could hide inside the tolerance)
-    n, h, wd = 4, 17, 17
-    x = torch.randint(-2, 3, (n, h, wd, 256), device="cuda").half()
-    w = torch.randint(-1, 2, (256, 3, 3, 256), device="cuda").half()
-    b = torch.randint(-3, 4, (256,), device="cuda").half()
-    y = torch.empty(n, h, wd, 256, device="cuda", dtype=torch.float16)
-    L.check(lib.sgo_conv3x3_tower_dev(n, h, wd, x.data_ptr(), w.data_ptr(), b.data_ptr(), None, y.data_ptr(), st))
-    ref = torch.relu(F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b.float(), padding=1)).permute(0, 2, 3, 1)
-    assert float(ref.max()) < 2048 and torch.equal(y.float(), ref)
+    for (n, h, wd) in EXACT_TOWER_SHAPES:
+        x = torch.randint(-2, 3, (n, h, wd, 256), device="cuda").half()
+        w = torch.randint(-1, 2, (256, 3, 3, 256), device="cuda").half()
+        b = torch.randint(-3, 4, (256,), device="cuda").half()
+        y = torch.empty(n, h, wd, 256, device="cuda", dtype=torch.float16)
+        L.check(lib.sgo_conv3x3_tower_dev(n, h, wd, x.data_ptr(), w.data_ptr(), b.data_ptr(), None, y.data_ptr(), st))
+        ref = torch.relu(F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), b.float(), padding=1)).permute(0, 2, 3, 1)
+        assert float(ref.max()) < 2048 and torch.equal(y.float(), ref), (n, h, wd)
     # unsupported shapes are errors, not silent fall-backs
     assert lib.sgo_conv3x3_tower_dev(1, 21, 21, x.data_ptr(), w.data_ptr(), b.data_ptr(), None, y.data_ptr(), st) < 0

@@ -5,13 +5,16 @@
    16-position tile, guard rows behind the outputs;
 2. calibrated nets (tests/netcal.py): the kernel and the framework route on the SAME tower output against the float64 heads --
    the kernel's error within 1.25 x the framework route's (tests/test_heads_rounding_model.py shows on CPU that its rounding model
-   is the better one: 0.22 .. 0.95 of the framework's there; the quarter is for accumulation order and the maximum over more rows),
+   is the better one: 0.12 .. 0.95 of the framework's there, 0.12 .. 0.43 on the 4-block nets of 5x5, 7x7 and 13x13; the quarter
+   is for accumulation order and the maximum over more rows), at every board size,
    a channels-first flatten as the negative control, and a logit bias of 3e4;
-3. the whole net on the engine's route with the fused heads against netcal.forward in float64, as tests/test_gpu_net_parity.py.
+3. the whole net on the engine's route with the fused heads against netcal.forward in float64, as tests/test_gpu_net_parity.py,
+   at 9x9 and, with all four head channels alive (netcal.CALIBRATION), at 5x5, 7x7 and 13x13.
 
 Measured on MI355X (logit / value error): 9x9 x 4 blocks: torch route 1.87e-3 / 1.98e-3, k_heads 4.34e-4 / 1.10e-3; 19x19 x 2
-blocks: torch route 3.53e-3 / 1.50e-3, k_heads 2.29e-3 / 1.14e-3; channels-first reference 3.5 / 9.2; exact-integer cases: policy
-within 2.0e-7 relative, value within 1.3e-8.
+blocks: torch route 3.53e-3 / 1.50e-3, k_heads 2.29e-3 / 1.14e-3; channels-first reference 3.5 / 9.2; 5x5, 7x7, 13x13 x 4 blocks:
+torch route 1.72e-3 / 2.87e-3, 1.82e-3 / 1.56e-3, 2.34e-3 / 3.70e-4, k_heads 4.04e-4 / 3.91e-4, 4.82e-4 / 3.94e-4, 1.10e-3 / 1.52e-4,
+channels-first reference 1.8 / 2.4 / 5.5; exact-integer cases: policy within 2.0e-7 relative, value within 1.3e-8.
 """
 import numpy as np
 import pytest
@@ -151,12 +154,15 @@ def torch_heads(fnet, y):
         fnet.blocks, fnet.fused_heads = saved, was
 
 
-@pytest.mark.parametrize("S,blocks,plies", [(9, 4, (0, 10, 30, 60)), (19, 2, (0, 30, 120, 250))], ids=["9x9_4block", "19x19_2block"])
+HEADS_CONFIGS = [(9, 4, (0, 10, 30, 60)), (19, 2, (0, 30, 120, 250)), (5, 4, (0, 4, 10, 16)), (7, 4, (0, 6, 16, 32)), (13, 4, (0, 20, 60, 110))]
+
+
+@pytest.mark.parametrize("S,blocks,plies", HEADS_CONFIGS, ids=["%dx%d_%dblock" % (c[0], c[0], c[1]) for c in HEADS_CONFIGS])
 def test_calibrated_heads_against_float64_and_the_torch_route(L, S, blocks, plies):
     import torch
     from tests.test_gpu_baseline_nets import _playout_records
     from tests.test_heads_rounding_model import heads
-    net = netcal.build_calibrated_net(S, blocks)
+    net = netcal.calibrated(S, blocks)
     fnet = netcal.fused_net(net)
     W = netcal.Weights(net, device="cuda")
     recs = torch.cat([_playout_records(L, S, 16, ply, seed=3000 + ply) for ply in plies])          # 64 rows
@@ -192,13 +198,13 @@ def test_calibrated_heads_against_float64_and_the_torch_route(L, S, blocks, plie
 
 
 # ---------------------------------------------------------------------------------------------------------- 3. whole net
-def test_whole_net_with_fused_heads_matches_the_float64_reference(L):
-    """predict_packed with use_fused_heads(True) at 9x9 x 4 blocks: 64 / 37 / 1 rows (the last two through an index list) of
-    every ply under every symmetry, within the bounds of tests/test_gpu_net_parity.py."""
+@pytest.mark.parametrize("S,blocks", [(9, 4), (5, 4), (7, 4), (13, 4)], ids=["9x9_4block", "5x5_4block", "7x7_4block", "13x13_4block"])
+def test_whole_net_with_fused_heads_matches_the_float64_reference(L, S, blocks):
+    """predict_packed with use_fused_heads(True) on the 4-block nets of tests/test_gpu_net_parity.py: 64 / 37 / 1 rows (the last
+    two through an index list) of every ply under every symmetry, within the bounds of that module."""
     import torch
     from tests import test_gpu_net_parity as tp
-    S, blocks, plies = 9, 4, (0, 10, 30, 60)
-    case = tp._CASES.get((S, blocks)) or tp._Case(L, S, blocks, plies)
+    case = tp.shared_case(L, S, blocks)
     fnet = case.fnet
     g = torch.Generator().manual_seed(S)
     worst = tp._Worst()

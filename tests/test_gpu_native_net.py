@@ -38,7 +38,8 @@ def _expected(L, nn, recs, idx, n, kdev):
 
 
 # ---------------------------------------------------------------------------------------------------------- 4. composition
-@pytest.mark.parametrize("S,blocks,ply", [(19, 2, 120), (9, 4, 30)], ids=["19x19_2block", "9x9_4block"])
+@pytest.mark.parametrize("S,blocks,ply", [(19, 2, 120), (9, 4, 30), (5, 4, 8), (7, 4, 16), (13, 4, 60)],
+                         ids=["19x19_2block", "9x9_4block", "5x5_4block", "7x7_4block", "13x13_4block"])
 def test_composition_is_bit_exact(L, S, blocks, ply):
     import torch
     from sejonggo_amd.net import NativeNet

@@ -2,8 +2,10 @@
 the same fp16 weights, with bounds that a wrong kernel cannot pass (tests/test_net_parity_power.py shows, on CPU, that every
 fault of netcal.MUTATIONS moves the logit metric by >= 2 * LOGIT_TOL while the fp16 rounding model stays within LOGIT_TOL / 2).
 
-* engine route (predict_packed: packed records -> sgo_stem_packed_dev -> tower -> heads) at 19x19 x 20 blocks and 9x9 x 4
-  blocks, on positions board_advance itself played from the opening to a nearly full board, all 8 symmetries, ragged batches
+* engine route (predict_packed: packed records -> sgo_stem_packed_dev -> tower -> heads) at 19x19 x 20 blocks and at 9x9, 5x5,
+  7x7 and 13x13 x 4 blocks (every size size_ok() accepts; the last three calibrated with centred heads, so that all four head
+  channels are alive), on positions board_advance itself played from the opening to a nearly full board (a playout passes
+  when nothing else is legal, so the late 5x5 plies are valid), all 8 symmetries, ragged batches
   (1 and 37 rows through an index list, 64 rows whole) and the headline 8 192 at 19x19 (sampled rows, first and last
   included), on each tower kernel: k_conv4w (the default), k_conv8w and k_conv4r;
 * tensor route (predict_on_batch on the channel-padded tensor: k_stem -> tower -> heads) on the same positions;
@@ -20,7 +22,8 @@ from tests.test_gpu_baseline_nets import _playout_records
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = [(19, 20, (0, 30, 120, 250)), (9, 4, (0, 10, 30, 60))]
+CONFIGS = [(19, 20, (0, 30, 120, 250)), (9, 4, (0, 10, 30, 60)),
+           (5, 4, (0, 4, 10, 16)), (7, 4, (0, 6, 16, 32)), (13, 4, (0, 20, 60, 110))]     # tower shapes 3x3, 5x5 and 11x11
 KERNELS = ("k_conv4w", "k_conv8w", "k_conv4r")
 N = 64
 P_STATED = 2e-3          # SURVEY.md 8c's probability bound, which the calibrated nets meet as well
@@ -42,7 +45,7 @@ class _Case(object):
         self.L, self.lib = L, L.load()
         self.S, self.blocks, self.plies = S, blocks, plies
         self.key = (S, blocks)
-        self.net = netcal.build_calibrated_net(S, blocks)
+        self.net = netcal.calibrated(S, blocks)
         self.fnet = netcal.fused_net(self.net)
         assert self.fnet.packed_ok
         self.W = netcal.Weights(self.net, device="cuda")
@@ -82,7 +85,7 @@ def shared_case(L, S, blocks):
     return _CASES[(S, blocks)]
 
 
-@pytest.fixture(scope="module", params=CONFIGS, ids=["19x19_20block", "9x9_4block"])
+@pytest.fixture(scope="module", params=CONFIGS, ids=["%dx%d_%dblock" % (c[0], c[0], c[1]) for c in CONFIGS])
 def case(request, L):
     S, blocks, plies = request.param
     return shared_case(L, S, blocks)

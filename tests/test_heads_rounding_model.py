@@ -23,8 +23,10 @@ from tests import netcal
 # their largest term (the rounding of h), so the value ratio is noisy where it is close to 1: over six seeds of 64 positions at
 # 13x13 it ranged 0.65 .. 1.05 (above 1 for two of them: 713 and 11), which is why the GPU bound is 1.25 and not 1.
 CALIB_SEED = 12
-# (board size, residual blocks, rows)
-CASES = [(9, 4, 128), (5, 2, 96), (13, 2, 64), (19, 2, 32)]
+# (board size, residual blocks, rows); the last three are the nets with centred heads (netcal.CALIBRATION) that
+# tests/test_gpu_heads.py also runs on the device: the fused model's error is 0.12 .. 0.43 of the framework route's there, so the
+# 1.25 of the GPU bound holds for them unchanged
+CASES = [(9, 4, 128), (5, 2, 96), (13, 2, 64), (19, 2, 32), (5, 4, 96), (7, 4, 96), (13, 4, 64)]
 
 
 @torch.no_grad()
@@ -66,7 +68,7 @@ def heads(W, y, model, channels_first=False):
 
 @pytest.mark.parametrize("S,blocks,rows", CASES, ids=["%dx%d_%dblock" % (c[0], c[0], c[1]) for c in CASES])
 def test_fused_rounding_model_is_not_the_worse_one(S, blocks, rows):
-    net = netcal.build_calibrated_net(S, blocks)
+    net = netcal.calibrated(S, blocks)
     W = netcal.Weights(net)
     X = netcal.playout_boards(S, (0, S * S // 8, S * S // 3, S * S * 2 // 3), rows // 4, seed=CALIB_SEED)
     y = emulated_tower(W, X)
