@@ -54,7 +54,7 @@ extern "C" {
  *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes), the "move
  *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
  *   section (sgo_secure*, sgo_session_secure), the "life and death" section (sgo_solve*, sgo_session_solve), the "capturing races"
- *   section (sgo_race*, sgo_session_race). */
+ *   section (sgo_race*, sgo_session_race), the "connections" section (sgo_connect*, sgo_session_connect). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -1054,6 +1054,102 @@ int sgo_race(int S, int n, const uint32_t *records, const int32_t *ask, const ui
 int sgo_session_race(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int max_libs,
                      int max_region, int max_nodes, int max_pairs, int32_t *status, int32_t *n_pairs, int32_t *rows, uint32_t *regions,
                      void *stream);
+
+/* ---- connections: can two chains of one colour be cut apart? ------------------------------------------------------------------------ */
+/* Per packed record: the table of the pairs of two chains of ONE colour that are near each other (or the one pair asked for), the
+ * region each pair is read in, the verdict of an exhaustive reader bounded by that region on whether the other colour can keep the two
+ * from becoming one chain, and the map of the GROUPS the connected pairs tie the chains into (csrc/sgo_connect.hip).  This is what
+ * turns the chains of the three sections above into groups.  Everything is integer.  N = S * S.
+ * Inputs of a record, rules in {0, 1}, ALLOWED, `prev` and the ko test: word for word those of the "life and death" and "capturing
+ * races" sections: black / white = the bits a < N of planes 0 / 1; the to-play flag is NOT a stone; planes 2 / 3 are used only for the
+ * ko test at the root; padding bits and planes 4..15 are never read.  Node counting, the rule that ends the WHOLE QUERY unknown (nodes
+ * > max_nodes or depth > SGO_CONNECT_MAX_DEPTH) and the ascending candidate order are those sections' too.
+ * PAIR: two different chains X and Y of the SAME colour C; their ANCHORS are their lowest points, anchor_x < anchor_y.  The DEFENDER
+ * is C and wants to make them one chain; the ATTACKER is the other colour.  lib(X), lib(Y) are their liberties; nbr(s) is the set of
+ * points 4-adjacent to a point of s.
+ * LINK POINTS K = (lib(X) & lib(Y)) | (lib(X) & nbr(lib(Y))) | (lib(Y) & nbr(lib(X))): the common liberties, and the liberties of one
+ * chain that are 4-adjacent to a liberty of the other.  That covers the diagonal, the one-point jump, the bamboo joint, the knight's
+ * move and the two-point jump.  A CUTTING CHAIN is an attacker chain Z that is 4-adjacent to a stone of X and to a stone of Y with 1
+ * <= |lib(Z)| <= cut_libs; its liberties join K, and Z itself joins M, so that the points it leaves when captured are playable.  The
+ * pair is NEAR when K is not empty.
+ * DEFAULT REGION M: M1 = K plus the empty points 4-adjacent to K.  M = M1 plus the cutting chains plus every chain other than X, Y and
+ * the cutting chains, of either colour, that has at least one liberty and whose EVERY liberty lies in M1 (the inner-chain rule of the
+ * two sections above: one pass, tested against M1).  A caller may give M explicitly instead; it is masked to the board and otherwise
+ * taken as it is.  region_empty = the empty points of M at the root.  Moves of both sides are confined to the points of M that are
+ * empty at the time of the move.
+ * THE READER: read(pos, mover, prev, depth) -> JOINED | CUT, for the stones on tx and ty (the two anchors at the root).  On entry,
+ * after the node is counted: if the chain on tx holds ty: JOINED.
+ *   Attacker to move:  for every ALLOWED empty point a of M in ascending index order: play it; the stone on tx or on ty is gone: CUT
+ *     with move a; else the stone just played is gone: next point; else recurse with the defender to move: CUT if that returns CUT.
+ *     Then the attacker's PASS (move N), ALWAYS tried, last: the same stones, the defender to move, `prev` as after a pass: CUT if that
+ *     returns CUT.  Otherwise JOINED.  The pass is always allowed, not only under a ko ban: a cutter must not be forced into a
+ *     self-atari that the defender captures to connect.  The wait of the "life and death" reader is the special case of this pass.
+ *   Defender to move:  for every ALLOWED empty point a of M in ascending index order: play it; the stone on tx, on ty or on a is gone:
+ *     next point; else recurse with the attacker to move: JOINED if that returns JOINED.  Otherwise CUT.  The defender never passes:
+ *     its pass could be answered by a pass, and two chains that are not one chain are not joined.
+ *   So JOINED means "the defender can force ONE standing chain inside M whatever the attacker plays there, a tenuki included".
+ * QUERIES per pair:  A = the attacker moves first, always run;  D = the defender moves first, run only when A returned CUT.  The node
+ * counter restarts per query.  A pair is `connected` when A is JOINED, `unsettled` when A is CUT and D is JOINED, `cut` when both are
+ * CUT, `unknown` when a query ended unknown, `open` when region_empty is 0 or above max_region (no query runs), `no_pair` see below.
+ * RESULT ROW int32[12] = {anchor_x, anchor_y, colour (+1 black, -1 white), |lib(X) & lib(Y)|, |K|, region_empty, status,
+ *   n_cutting_chains, cut_move, join_move, nodes_A, nodes_D}.  cut_move = the first root move by which A cuts (N = the pass);
+ *   join_move = the first root candidate by which D joins.  Moves are -1 and nodes 0 under the conditions of the solve row (no such
+ *   move, the query unknown or not run).  status bits: SGO_CONNECT_A_CUT 1, SGO_CONNECT_D_CUT 2, SGO_CONNECT_A_UNKNOWN 4,
+ *   SGO_CONNECT_D_UNKNOWN 8, SGO_CONNECT_D_RAN 16, SGO_CONNECT_OPEN, SGO_CONNECT_NO_PAIR: an asked point is empty or off the board, the
+ *   two stones differ in colour, or they are one chain already; anchors and moves are then -1, the other words 0, the region empty.
+ * GROUPS: d_groups int16 [n][N]: for a stone the lowest anchor among the chains its chain is tied to through `connected` pairs -- the
+ *   transitive closure over the WRITTEN table rows of that row; for an empty point -1.  Both colours stand in the one map.
+ *   d_group_counts int32 [n][4] = {chains, groups, connected pairs among the written rows, flags}; flag 1: n_pairs > max_pairs, the table
+ *   was cut, so the partition may be too fine; flag 2: some written pair is `unknown` or `open`; such pairs do NOT tie.
+ * WHAT IS LEFT OUT.  No transposition table and no move ordering: the traversal is fixed and the node counts pin it.  Ko is the
+ * one-ply approximation.  Moves outside M are not read, so a cut that works only through a ladder running out of M reads `unsettled`
+ * or `cut`, not `connected`.  Connection by capturing a cutting chain with more than cut_libs liberties is not seen.  `connected` is
+ * about making one chain inside M; it is not about whether the joined chain lives.  The knight's move and the two-point jump usually
+ * have region_empty above the default max_region of the Python layer (8) and read `open`.
+ *
+ * sgo_connect_dev: row i reads record d_index[i] (d_index NULL: record i) of d_records [n_records][sgo_packed_words(S)], in place.
+ * d_n_pairs int32 [n], d_rows int32 [n][max_pairs][12], d_regions uint32 [n][max_pairs][sgo_plane_words(S)]: the M used, bits a >= N
+ * zero.  d_ask NULL, or d_ask[i][0] < 0 (d_ask int32 [n][2]): ENUMERATE: the NEAR pairs of either colour whose region_empty lies in
+ * 1..max_region, in ascending (anchor_x, anchor_y) order; n_pairs = their true number; only min(n_pairs, max_pairs) rows and region
+ * sets are written and everything behind them stays untouched.  d_ask[i] = {p, q} with p >= 0: exactly one row (n_pairs = 1), for the
+ * chains on p and q in either order; the pair need not be NEAR (K empty: region_empty 0, `open`); read in row i of d_region
+ * [n][sgo_plane_words(S)] when that is not NULL.  A row whose record index is outside [0, n_records) gives n_pairs = 0, untouched rows,
+ * an untouched group map and untouched counts.  THREE launches on `stream` (k_connect_pairs, k_connect_read, k_connect_groups), no
+ * allocation, no synchronisation, capturable; n == 0 is a no-op; rows >= n are not written.  SGO_ERR_ARG: an unsupported S, n < 0,
+ * n_records < 0, rules outside {0, 1}, cut_libs outside [0, SGO_CONNECT_MAX_CUT_LIBS], max_region outside [1, SGO_CONNECT_MAX_REGION],
+ * max_nodes outside [1, SGO_CONNECT_MAX_NODES], max_pairs outside [1, SGO_CONNECT_MAX_PAIRS], a NULL d_records or output.
+ * SGO_CONNECT_MAX_NODES bounds the longest launch a single query can cause: measured on one MI355X (profiles/connect_ab.json) a node
+ * takes 1.9 us with one half of the wave reading and 2.1 us with both, at 9x9 and at 19x19 alike, and a query that spends all 32 768
+ * nodes 62 to 70 ms, under the 0.29 s the "life and death" cap allows; so the cap stands at that of the "capturing races" section. */
+#define SGO_CONNECT_MAX_CUT_LIBS 4
+#define SGO_CONNECT_MAX_REGION 32
+#define SGO_CONNECT_MAX_NODES 32768
+#define SGO_CONNECT_MAX_PAIRS 64
+#define SGO_CONNECT_MAX_DEPTH 80
+#define SGO_CONNECT_A_CUT 1
+#define SGO_CONNECT_D_CUT 2
+#define SGO_CONNECT_A_UNKNOWN 4
+#define SGO_CONNECT_D_UNKNOWN 8
+#define SGO_CONNECT_D_RAN 16
+#define SGO_CONNECT_OPEN (1 << 16)
+#define SGO_CONNECT_NO_PAIR (1 << 17)
+int sgo_connect_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask,
+                    const uint32_t *d_region, int rules, int cut_libs, int max_region, int max_nodes, int max_pairs, int32_t *d_n_pairs,
+                    int32_t *d_rows, uint32_t *d_regions, int16_t *d_groups, int32_t *d_group_counts, void *stream);
+/* The same for HOST buffers, records [n][sgo_packed_words(S)] in order (copy in, run, copy back): for drop-in use and parity tests.
+ * ask (or NULL) int32 [n][2], region (or NULL) uint32 [n][sgo_plane_words(S)].  Table rows and region sets beyond min(n_pairs,
+ * max_pairs) come back as the caller filled them. */
+int sgo_connect(int S, int n, const uint32_t *records, const int32_t *ask, const uint32_t *region, int rules, int cut_libs, int max_region,
+                int max_nodes, int max_pairs, int32_t *n_pairs, int32_t *rows, uint32_t *regions, int16_t *groups, int32_t *group_counts);
+/* The root positions of the listed HOLDING session slots of `ctx`, read in place; waits for `stream`.  HOST arrays: ask (or NULL)
+ * [n][2], region (or NULL) [n][sgo_plane_words(S)], status [n], n_pairs [n], rows [n][max_pairs][12], regions
+ * [n][max_pairs][sgo_plane_words(S)], groups int16 [n][N], group_counts [n][4].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that
+ * is not a holding session: that row's outputs are left as the caller filled them, as are the table rows beyond min(n_pairs,
+ * max_pairs) of every row.  The context is only read; a slot may be listed repeatedly.  SGO_ERR_ARG: the bounds of sgo_connect_dev, a
+ * slot outside the context, a NULL slot list or output. */
+int sgo_session_connect(sgo_ctx *ctx, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int cut_libs,
+                        int max_region, int max_nodes, int max_pairs, int32_t *status, int32_t *n_pairs, int32_t *rows, uint32_t *regions,
+                        int16_t *groups, int32_t *group_counts, void *stream);
 
 /* ---- influence: who holds what right now, and by how much?  (an ESTIMATE, not a proof) --------------------------------------------- */
 /* Per packed record: Bouzy's dilation / erosion map of the stones, the territory and moyo sets read off it, and an area-score

@@ -45,6 +45,7 @@ SYMBOLS = [
     "sgo_secure_dev", "sgo_secure", "sgo_session_secure", "sgo_secure_mode",
     "sgo_solve_dev", "sgo_solve", "sgo_session_solve",
     "sgo_race_dev", "sgo_race", "sgo_session_race",
+    "sgo_connect_dev", "sgo_connect", "sgo_session_connect",
 ]
 
 
@@ -214,6 +215,9 @@ def load():
     lib.sgo_race_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 4
     lib.sgo_race.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 3
     lib.sgo_session_race.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 5
+    lib.sgo_connect_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 6
+    lib.sgo_connect.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 5
+    lib.sgo_session_connect.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 7
     lib.sgo_influence_dev.argtypes =[C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
     lib.sgo_influence.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3
     lib.sgo_session_influence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5

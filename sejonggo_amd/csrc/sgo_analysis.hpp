@@ -1,4 +1,4 @@
-// sgo_analysis.hpp -- what the nine position analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race) share on the host: the record
+// sgo_analysis.hpp -- what the ten position analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect) share on the host: the record
 // launchers of their translation units, which sgo_session.hip runs over the context's root records, and the one body of their
 // host entries sgo_X.  Host code only; every kernel stays in its own file.
 #pragma once
@@ -27,14 +27,18 @@ int launch_solve(int S, int n, const uint32_t *d_records, int n_records, const i
 int launch_race(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask, const uint32_t *d_region,
                 int rules, int max_libs, int max_region, int max_nodes, int max_pairs, int32_t *d_n_pairs, int32_t *d_rows, uint32_t *d_regions,
                 hipStream_t st);
+int launch_connect(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask, const uint32_t *d_region,
+                   int rules, int cut_libs, int max_region, int max_nodes, int max_pairs, int32_t *d_n_pairs, int32_t *d_rows, uint32_t *d_regions,
+                   int16_t *d_groups, int32_t *d_group_counts, hipStream_t st);
 
 // The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
 // (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip) and of the solve parameters (csrc/sgo_solve.hip)
-// and the race parameters (csrc/sgo_race.hip).
+// and the race parameters (csrc/sgo_race.hip) and the connect parameters (csrc/sgo_connect.hip).
 int session_shape_table(int S, const sgo_shape *shape, uint32_t *table);
 bool influence_params_ok(int dilate, int erode_moyo, int erode_terr);
 bool solve_params_ok(int rules, int max_region, int max_nodes, int max_targets);
 bool race_params_ok(int rules, int max_libs, int max_region, int max_nodes, int max_pairs);
+bool connect_params_ok(int rules, int cut_libs, int max_region, int max_nodes, int max_pairs);
 
 // One array of a host entry's device block.  `up` (or nullptr) is copied in before the launch, `down` (or nullptr) is filled
 // from it afterwards; an array with neither is only room.

@@ -3,7 +3,8 @@
 // sgo_keys.hip), of sgo_session_tactics ("chains and ladders"; sgo_tactics.hip), of sgo_session_life ("unconditional life";
 // sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip), of
 // sgo_session_influence ("influence"; sgo_influence.hip), of sgo_session_secure ("securing moves"; sgo_secure.hip), of
-// sgo_session_solve ("life and death"; sgo_solve.hip) and of sgo_session_race ("capturing races"; sgo_race.hip).
+// sgo_session_solve ("life and death"; sgo_solve.hip) and of sgo_session_race ("capturing races"; sgo_race.hip) and of sgo_session_connect
+// ("connections"; sgo_connect.hip).
 // Those nine (session_rows below, over the launchers of sgo_analysis.hpp) and sgo_rollout_start_sessions (sgo_rollout.hip) find
 // the root records of the listed slots with launch_session_roots below and run their ordinary record kernels over the context's
 // blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
@@ -107,7 +108,7 @@ struct RowCol {
     std::function<size_t(int)> stored;
 };
 
-// The body of the nine session analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race).  The session buffer is laid out as
+// The body of the ten session analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect).  The session buffer is laid out as
 //     slots | input | record index | status | columns
 // the slots (and `input`, where there is one: a shape table, the dead sets) go up, k_session_roots names the root records,
 // launch(d_index, d_input, d_cols) runs the ordinary record launcher over the context's blocks, and everything behind the index
@@ -452,6 +453,42 @@ int sgo_session_race(sgo_ctx *x, int n, const int32_t *slots, const int32_t *ask
         return launch_race(c.S, n, c.pos, ctx_records(c), d_index, d_in ? reinterpret_cast<const int32_t *>(d_in) : nullptr,
                            (d_in && region) ? reinterpret_cast<const uint32_t *>(d_in + ab) : nullptr, rules, max_libs, max_region, max_nodes,
                            max_pairs, reinterpret_cast<int32_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<uint32_t *>(d[2]), st);
+    });
+}
+
+int sgo_session_connect(sgo_ctx *x, int n, const int32_t *slots, const int32_t *ask, const uint32_t *region, int rules, int cut_libs, int max_region,
+                        int max_nodes, int max_pairs, int32_t *status, int32_t *n_pairs, int32_t *rows, uint32_t *regions, int16_t *groups,
+                        int32_t *group_counts, void *stream) {
+    if (!x || n < 0 || !connect_params_ok(rules, cut_libs, max_region, max_nodes, max_pairs) ||
+        (n && (!slots || !status || !n_pairs || !rows || !regions || !groups || !group_counts))) {
+        set_error("sgo_session_connect: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    const Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t row = sizeof(int32_t) * 12, plane = sizeof(uint32_t) * sgo_plane_words(c.S), ab = al8(sizeof(int32_t) * 2 * (size_t)n);
+    // the optional input block: ask [n][2] (enumerate where the caller gave none), then region [n][NW]
+    std::vector<uint8_t> in;
+    if (ask || region) {
+        in.assign(ab + (region ? plane * n : 0), 0);
+        int32_t *ha = reinterpret_cast<int32_t *>(in.data());
+        for (int i = 0; i < 2 * n; i++) ha[i] = ask ? ask[i] : -1;
+        if (region) memcpy(in.data() + ab, region, plane * n);
+    }
+    // the table rows and region sets behind min(n_pairs, max_pairs) were not written; n_pairs stands before them
+    const auto listed = [=](int i) { return (size_t)(n_pairs[i] < max_pairs ? n_pairs[i] : max_pairs); };
+    const RowCol cols[] = {{n_pairs, sizeof(int32_t), 4},
+                           {rows, row * max_pairs, 4, [=](int i) { return row * listed(i); }},
+                           {regions, plane * max_pairs, 4, [=](int i) { return plane * listed(i); }},
+                           {group_counts, sizeof(int32_t) * 4, 4},
+                           {groups, sizeof(int16_t) * c.S * c.S, 2}};
+    return session_rows(x, "sgo_session_connect", n, slots, in.empty() ? nullptr : in.data(), in.size(), status, cols, st,
+                        [&](const int32_t *d_index, const uint8_t *d_in, uint8_t *const *d) {
+        return launch_connect(c.S, n, c.pos, ctx_records(c), d_index, d_in ? reinterpret_cast<const int32_t *>(d_in) : nullptr,
+                              (d_in && region) ? reinterpret_cast<const uint32_t *>(d_in + ab) : nullptr, rules, cut_libs, max_region, max_nodes,
+                              max_pairs, reinterpret_cast<int32_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<uint32_t *>(d[2]),
+                              reinterpret_cast<int16_t *>(d[4]), reinterpret_cast<int32_t *>(d[3]), st);
     });
 }
 

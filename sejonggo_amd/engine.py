@@ -856,6 +856,22 @@ class SessionEngine(SelfPlayEngine):
                                     out.n_pairs, out.rows, out.regions)
         return out
 
+    def connect(self, slots, ask=None, region=None, rules=1, cut_libs=1, max_region=8, max_nodes=1024, max_pairs=None):
+        """Connections in the root positions of the listed holding sessions (sgo_session_connect; include/sgo.h "connections"): a
+        connect.Connect with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays zero, its
+        group map -1).  ask None: every near pair; else two points per slot ((-1, -1): enumerate), read in row i of `region`
+        (uint32 [n, NW]) when given.  A bounded reader, not a proof about the game.  Boards and trees are only read."""
+        from .connect import MAX_PAIRS, WORDS, Connect, check_args, host_inputs
+        n, NW, mp = len(slots), self.lib.sgo_plane_words(self.S), int(max_pairs or MAX_PAIRS)
+        check_args(rules, cut_libs, max_region, max_nodes, mp)
+        ask, region = host_inputs(self.S, n, ask, region)
+        out = Connect(self.S, np.zeros(n, np.int32), np.zeros((n, mp, WORDS), np.int32), np.zeros((n, mp, NW), np.uint32),
+                      np.full((n, self.S * self.S), -1, np.int16), np.zeros((n, 4), np.int32))
+        out.status = self._analysis(self.lib.sgo_session_connect, slots,
+                                    (_lib.ptr(ask), _lib.ptr(region), int(rules), int(cut_libs), int(max_region), int(max_nodes), mp),
+                                    out.n_pairs, out.rows, out.regions, out.groups, out.group_counts)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

@@ -287,6 +287,14 @@ class DeviceSejongGoEngine(object):
         return self._held(self.engine.race([self.slot], None if ask is None else [ask], None, rules=rules, max_libs=max_libs,
                                            max_region=max_region, max_nodes=max_nodes))
 
+    def connect(self, ask=None, rules=1, cut_libs=1, max_nodes=1024, max_region=8):
+        """Connections in the position on the board (engine.SessionEngine.connect): (a connect.Connect with one row, the stones int8
+        [S * S], +1 black).  ask None: every near pair; else the pair on those two points."""
+        from .rollout import real_board
+        v = self._held(self.engine.connect([self.slot], None if ask is None else [ask], None, rules=rules, cut_libs=cut_libs,
+                                           max_region=max_region, max_nodes=max_nodes))
+        return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -338,7 +346,7 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "quit"])
+                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -632,6 +640,61 @@ class GTPEngine(object):
             raise GTPFailure("no pair on %s %s" % (self._vertex(pts[0]), self._vertex(pts[1])))
         return "\n".join(format_pair(p, self._vertex, N) for p in pairs)
 
+    def _connect_words(self, words, vertices):
+        """(points, keyword arguments) of `sgo-connect` / `sgo-groups` words"""
+        from .connect import MAX_CUT_LIBS, MAX_NODES
+        pts, nodes, libs, rules, words = [], None, None, 1, list(words)
+        while words:
+            w = words.pop(0)
+            if w == "inherited" and rules == 1:
+                rules = 0
+            elif w == "nodes" and nodes is None and words and words[0].isdigit() and 1 <= int(words[0]) <= MAX_NODES:
+                nodes = int(words.pop(0))
+            elif w == "cutlibs" and libs is None and words and words[0].isdigit() and int(words[0]) <= MAX_CUT_LIBS:
+                libs = int(words.pop(0))
+            else:
+                try:
+                    x, y = self.parse_move(w)
+                except Exception:
+                    raise GTPFailure("syntax error")
+                if not (vertices and 0 <= x < self.size and 0 <= y < self.size):
+                    raise GTPFailure("syntax error")
+                pts.append(y * self.size + x)
+        if len(pts) not in (0, 2):
+            raise GTPFailure("syntax error")
+        return pts, dict(rules=rules, cut_libs=1 if libs is None else libs, max_nodes=nodes or 1024)
+
+    def sgo_connect(self, *words):
+        """Private extension `sgo-connect [VERTEX VERTEX] [cutlibs K] [nodes K] [inherited]`: can two chains of one colour be cut
+        apart (include/sgo.h "connections")?  One line per pair `X Y colour shared s links k empty E cutting c verdict cut C join J
+        nodes A D` -- X / Y the lowest points of the two chains, verdict connected / unsettled / cut / unknown / open, cut the other
+        side's first cutting move (`pass`: it cuts by playing elsewhere), join the first joining move.  With two vertices: that pair
+        only; without: every near pair.  `cutlibs K` lets opposing chains with up to K liberties between the two count as
+        capturable cutting chains (default 1); `nodes K` sets the budget per query (default 1024); `inherited` reads under the
+        legal-move rule as inherited (rules = 0).  The verdict of a bounded reader inside the pair's region, not a proof about the
+        game."""
+        from .connect import format_pair
+        pts, kw = self._connect_words(words, True)
+        v, _ = self._engine_method("connect")(tuple(pts) if pts else None, **kw)
+        pairs = v.pairs_of(0)
+        if pts and pairs[0].no_pair:
+            raise GTPFailure("no pair on %s %s" % (self._vertex(pts[0]), self._vertex(pts[1])))
+        return "\n".join(format_pair(p, self._vertex, self.size * self.size) for p in pairs)
+
+    def sgo_groups(self, *words):
+        """Private extension `sgo-groups [cutlibs K] [nodes K] [inherited]`: the board with one letter per GROUP -- the chains that
+        `sgo-connect` reads as connected, tied together -- upper case for black and lower case for white, then `chains C groups G
+        connected P` and, where it applies, `table cut` (more near pairs than the table holds: the partition may be too fine) and
+        `undecided` (some pair is unknown or open and ties nothing)."""
+        from .connect import FLAG_CUT_TABLE, FLAG_UNDECIDED, format_groups
+        _, kw = self._connect_words(words, False)
+        v, stones = self._engine_method("connect")(None, **kw)
+        c = v.group_counts[0]
+        tail = "chains %d groups %d connected %d" % (c[0], c[1], c[2])
+        tail += " table cut" if c[3] & FLAG_CUT_TABLE else ""
+        tail += " undecided" if c[3] & FLAG_UNDECIDED else ""
+        return format_groups(self.size, v.groups[0], set(np.flatnonzero(stones > 0).tolist())) + "\n" + tail
+
     def _influence(self, words):
         from .influence import PRESETS
         preset, dead = None, "life"
@@ -663,7 +726,8 @@ class GTPEngine(object):
 
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
-               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race",
+               "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")

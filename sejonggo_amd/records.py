@@ -468,6 +468,20 @@ class DeviceRecords(object):
                     torch.zeros((0, int(max_pairs), self.NW), dtype=torch.int32, device=self.device))
         return race_dev(self.S, self.records, index, None, None, rules, max_libs, max_region, max_nodes, max_pairs, self.lib)
 
+    def connect(self, index, rules=1, cut_libs=1, max_region=8, max_nodes=1024, max_pairs=64):
+        """(n_pairs int32 [n], rows int32 [n, max_pairs, 12], regions int32 [n, max_pairs, NW] holding the uint32 bit patterns, groups
+        int16 [n, N], group_counts int32 [n, 4]) device tensors of the listed records, every near pair enumerated (sgo_connect_dev,
+        three launches; include/sgo.h "connections").  Rows behind min(n_pairs, max_pairs) are zero; an index outside the object
+        gives n_pairs 0 and a map of -1."""
+        from .connect import WORDS, connect_dev
+        torch = self.torch
+        index = self._index(index)
+        if int(index.shape[0]) == 0:
+            return (torch.zeros(0, dtype=torch.int32, device=self.device), torch.zeros((0, int(max_pairs), WORDS), dtype=torch.int32, device=self.device),
+                    torch.zeros((0, int(max_pairs), self.NW), dtype=torch.int32, device=self.device),
+                    torch.zeros((0, self.N), dtype=torch.int16, device=self.device), torch.zeros((0, 4), dtype=torch.int32, device=self.device))
+        return connect_dev(self.S, self.records, index, None, None, rules, cut_libs, max_region, max_nodes, max_pairs, self.lib)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -694,6 +708,16 @@ class RecordSet(object):
         from .race import Race
         return self._per_record("race", lambda index: self.backend.race(index, rules, max_libs, max_region, max_nodes, max_pairs),
                                 lambda n_pairs, rows, regions: Race(self.S, _host(n_pairs), _host(rows), _host(regions, np.uint32)), stones)
+
+    def connect(self, rules=1, cut_libs=1, max_region=8, max_nodes=1024, max_pairs=64, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `connect`, a connect.Connect with one row per RECORD of the chunk (one
+        backend call per chunk), rows as in `life`: the near pairs of chains of one colour of every position, what a bounded reader
+        says of each, and the group map on top.  Records that were not written give n_pairs 0.  stones=True adds ch.stones as
+        `tactics` does."""
+        from .connect import Connect
+        return self._per_record("connect", lambda index: self.backend.connect(index, rules, cut_libs, max_region, max_nodes, max_pairs),
+                                lambda n_pairs, rows, regions, groups, counts: Connect(self.S, _host(n_pairs), _host(rows), _host(regions, np.uint32),
+                                                                                       _host(groups, np.int16), _host(counts)), stones)
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -1021,6 +1045,28 @@ def race_table(record_set, width=20, **kw):
     return bucket_table(np.array(ply), np.array(action), np.array(colour), np.stack(rows), np.array(n_pairs), record_set.S * record_set.S, width)
 
 
+def connect_table(record_set, width=20, **kw):
+    """The table of `--connect` (connect.bucket_table) from one RecordSet.connect pass: per bucket of `width` moves the near pairs per
+    position, the share of each verdict among them, and the groups per position beside the chains per position.  Set-up stones are
+    left out."""
+    from .connect import bucket_table
+    ply, rows, n_pairs, counts = [], [], [], []
+    for ch in record_set.connect(**kw):
+        v = ch.connect
+        first = {}
+        for e in np.flatnonzero(ch.valid & ~ch.setup):
+            g, r = int(ch.game[e]), int(ch.index[e])
+            number = first.get(g, 0)
+            first[g] = number + 1
+            ply.append(number)
+            rows.append(v.rows[r])
+            n_pairs.append(v.n_pairs[r])
+            counts.append(v.group_counts[r])
+    if not ply:
+        return []
+    return bucket_table(np.array(ply), np.stack(rows), np.array(n_pairs), np.stack(counts), width)
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -1076,6 +1122,10 @@ def main(argv=None, out=sys.stdout):
                     help="capturing races by a bounded reader: per 20-move bucket the pairs of chains in contact per position, the share of "
                          "racers that are safe / unsettled / caught / unknown, and how often the recorded move was a listed catching or "
                          "saving move")
+    ap.add_argument("--connect", action="store_true",
+                    help="connections by a bounded reader: per 20-move bucket the near pairs of chains of one colour per position, the "
+                         "share that is connected / unsettled / cut / unknown / open, and the groups per position beside the chains per "
+                         "position")
     ap.add_argument("--influence", action="store_true",
                     help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
                          "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
@@ -1160,6 +1210,15 @@ def main(argv=None, out=sys.stdout):
             out.write("race: %d pairs in %d positions; %d positions offered the mover a catching or saving move; the recorded move was one %d times; unknown racers %d of %d\n" % (
                 sum(r["pairs"] for r in doc["race"]), sum(r["plies"] for r in doc["race"]), sum(r["chances"] for r in doc["race"]),
                 sum(r["took"] for r in doc["race"]), sum(r["unknown"] for r in doc["race"]), sum(r["racers"] for r in doc["race"])))
+        if a.connect:
+            from .connect import format_bucket_table as format_connect_table
+            doc["connect"] = connect_table(rs, a.bucket)
+            if doc["connect"]:
+                out.write(format_connect_table(doc["connect"]) + "\n")
+            tot = lambda k: sum(r[k] for r in doc["connect"])                            # noqa: E731
+            out.write("connect: %d pairs in %d positions (%d found, %d tables cut); connected %d unsettled %d cut %d unknown %d open %d; %d chains in %d groups\n" % (
+                tot("pairs"), tot("plies"), tot("found"), tot("cut_tables"), tot("connected"), tot("unsettled"), tot("cut"), tot("unknown"),
+                tot("open"), tot("chains"), tot("groups")))
         if a.moves:
             from .moves import format_bucket_table
             doc["moves"] = moves_table(rs, a.bucket)

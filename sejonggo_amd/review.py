@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race]
+                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race] [--connect]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -336,6 +336,27 @@ def add_race(rows, game, record_set=None):
     return rows
 
 
+def connect_rows(game, record_set):
+    """{move number: flags} of the B / W moves of `game` (connect.review_flags) from one RecordSet.connect pass over a set that holds
+    the game as its only record: each played move against the pairs of the position in front of it."""
+    from .connect import review_flags
+    out = {}
+    for ch in record_set.connect():
+        v = ch.connect
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = review_flags(game.size, action, colour, v.pairs_of(r), lambda a: vertex(a, game.size))
+    return out
+
+
+def add_connect(rows, game, record_set=None):
+    """Adds `connect_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = connect_rows(game, rs)
+    for row in rows:
+        row["connect_flags"] = list(found.get(row["move_number"], []))
+    return rows
+
+
 def influence_rows(game, record_set, komi=0.0, dead="life"):
     """{move number: {"estimate", "gain"}} of the B / W moves of `game` (influence.review_fields) from one RecordSet.influence pass
     over a set that holds the game as its only record: the estimate in front of the move, and what the move did to the margin."""
@@ -384,7 +405,7 @@ def format_row(row):
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
         list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or []) + \
-        list(row.get("race_flags") or [])
+        list(row.get("race_flags") or []) + list(row.get("connect_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -460,13 +481,17 @@ def main(argv=None, out=sys.stdout):
                     help="flag each played move against the capturing races a bounded reader decides in the position in front of it: "
                          "wins-race V (the catching or saving move of an unsettled racer V), missed-race V at K (flags from a bounded "
                          "reader, not verdicts).  Like --influence it loads no net when nothing else asks for one")
+    ap.add_argument("--connect", action="store_true",
+                    help="flag each played move against the connections a bounded reader decides in the position in front of it: cuts V "
+                         "(the cut_move of an unsettled pair V of the opponent), joins V, missed-cut V at K, missed-join V at K (flags "
+                         "from a bounded reader, not verdicts).  Like --influence it loads no net when nothing else asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure or a.solve or a.race) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -500,6 +525,8 @@ def main(argv=None, out=sys.stdout):
         add_solve(rows, game)
     if a.race:
         add_race(rows, game)
+    if a.connect:
+        add_connect(rows, game)
     if a.influence:
         add_influence(rows, game)
     for row in rows:
