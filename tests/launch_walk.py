@@ -1,5 +1,6 @@
 """A tiny model of a CAPPED LAUNCH: a kernel whose grid stops at a cap and whose workgroups walk the remaining rows in a stride
-loop (k_keys, k_tactics_read, k_solve_read, k_race_read, k_rollout_start of sejonggo_amd/csrc).  No code of the package takes part.
+loop (k_keys, k_tactics_read, k_solve_read, k_race_read, k_rollout_start, k_secure of sejonggo_amd/csrc).  No code of the package
+takes part.
 
 A launch is (n rows, cap_rows rows per trip of the grid, rows_per_block rows per workgroup).  Trip k of workgroup b covers rows
 k * cap_rows + b * rows_per_block + (0 .. rows_per_block - 1).  rows_of says, per output row, which trip writes it and which INPUT
@@ -39,11 +40,11 @@ def applies(fault, rows_per_block):
     return True
 
 
-def rows_of(n, cap_rows, rows_per_block, fault=None):
+def rows_of(n, cap_rows, rows_per_block, fault=None, first=0):
     """(trip int64 [n], src int64 [n]): the trip that writes output row i and the input row it is computed from; src -1 for a
-    row that is never written"""
+    row that is never written (first > 0: the rows first .. n - 1 only, for a launch too long to lay out whole)"""
     assert n >= 0 and cap_rows >= rows_per_block >= 1 and cap_rows % rows_per_block == 0 and (fault is None or fault in FAULTS)
-    i = np.arange(n, dtype=np.int64)
+    i = np.arange(first, n, dtype=np.int64)
     trip = i // cap_rows
     src = i.copy()
     if fault == "one_trip":
@@ -56,7 +57,7 @@ def rows_of(n, cap_rows, rows_per_block, fault=None):
         src[i >= n // rows_per_block * rows_per_block] = -1
     elif fault == "lone_half":
         if rows_per_block % 2 == 0 and n % 2 == 1:
-            src[n - 1] = -1
+            src[-1] = -1
     return trip, src
 
 
@@ -153,3 +154,40 @@ def start_cells(S, n_src, per_src, fault=None, top_from_words=False):
     if top_from_words:
         done &= np.arange(own_n) < words
     return done
+
+
+# ---- k_secure: one (row, pair of candidates) UNIT per workgroup ------------------------------------------------------------------
+SECURE_CAP = 1 << 24                                                 # SECURE_GRID_CAP of csrc/sgo_secure.hip, in units
+# (ch: the workgroups per row, forced to the pairs (S * S + 1) // 2 of a row through sgo_secure_mode; n: the rows the GPU test gives)
+SECURE = {5: {"ch": 13, "n": 1296001}, 19: {"ch": 181, "n": 97999}}
+
+
+def secure_geometry(S):
+    """(ch, n, astride, first_whole, k0): unit SECURE_CAP is pair k0 of row `astride` -- its pairs below k0 belong to trip 0, the rest
+    to trip 1 -- and `first_whole` = astride + 1 is the first row wholly in the second trip"""
+    ch, n = SECURE[S]["ch"], SECURE[S]["n"]
+    astride, k0 = SECURE_CAP // ch, SECURE_CAP % ch
+    return ch, n, astride, astride + 1, k0
+
+
+def secure_listed(R, first_whole):
+    """how many of the R records of a case set the index list of the secure launch names: wrapped_index(n, first_whole, R) gives the
+    rows from first_whole on the record (i + 1) % R and the units of such a row have their twins one trip earlier in the rows
+    i - first_whole and i - first_whole + 1, those of the row astride the cap in row 0: R, or the largest number below it that
+    divides none of first_whole - 1, first_whole and first_whole + 1 (the 76 securing cases at 5x5: 75)"""
+    while R > 1 and any((first_whole + d) % R == 0 for d in (-1, 0, 1)):
+        R -= 1
+    return R
+
+
+def secure_entries(S, index, R, fault=None, first=0):
+    """k_secure's table as a launch of one UNIT per row of the model: int64 [(n - first) + 2, ch], entry (row i, pair k) -- the
+    table rows of the (2k)-th and (2k + 1)-th empty point -- as record * ch + pair, written by unit i * ch + k % ch (ch = pairs: k);
+    unit u is computed from the record that the index entry of row u // ch names.  The rows first .. n - 1 and two rows behind n."""
+    ch, n = SECURE[S]["ch"], SECURE[S]["n"]
+    trip, src = rows_of(n * ch, SECURE_CAP, 1, fault, first=first * ch)
+    out = np.full((n - first + 2) * ch, FILL, np.int64)
+    rec = record_of(index, R)
+    w = src >= 0
+    out[:(n - first) * ch][w] = rec[src[w] // ch] * ch + src[w] % ch
+    return out.reshape(n - first + 2, ch)

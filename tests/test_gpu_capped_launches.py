@@ -1,6 +1,7 @@
 """GPU: every launch of csrc that caps its grid and walks the remaining rows in a stride loop, run PAST its cap and compared whole
-with the existing models: k_keys (4 096 blocks of 8 rows), k_tactics_read, k_solve_read and k_race_read (gridDim.y = 65 535) and
-k_rollout_start (4 096 blocks of 256 words or ownership cells), then RecordSet.keys / RecordSet.tactics over a collection of more
+with the existing models: k_keys (4 096 blocks of 8 rows), k_tactics_read, k_solve_read and k_race_read (gridDim.y = 65 535),
+k_rollout_start (4 096 blocks of 256 words or ownership cells) and k_secure (1 << 24 workgroups of one pair of candidates each:
+a ROW straddles the cap), then RecordSet.keys / RecordSet.tactics over a collection of more
 than 2 * 65 535 positions in one chunk.  tests/launch_walk.py models such a launch; tests/test_launch_walk_power.py shows that
 these row counts and index lists notice its fault switches.
 
@@ -22,7 +23,10 @@ Measured on MI355X (pytest --durations=0 of this module within the whole suite, 
   0.60s test_race_three_trips[19-enumerated]   0.32s test_race_three_trips[19-asked]     0.35s / 0.18s the same at 5x5
   0.41s test_solve_three_trips[19-asked]       0.37s test_solve_three_trips[19-enumerated]   0.07s / 0.05s the same at 5x5
   0.16s test_keys_three_trips[19]              0.09s / 0.01s / 0.01s test_rollout_start_walk[a / b / c]
-  1.97s test_keys_three_trips[5] when the module runs alone (the first call of the process), 0.01s otherwise"""
+  1.97s test_keys_three_trips[5] when the module runs alone (the first call of the process), 0.01s otherwise
+test_secure_past_the_grid_cap, the two cases alone in a process: 1.98s at 5x5 and 4.37s at 19x19, of which 4.25s are the model's rows of
+the 19x19 case set (computed once per process and shared with tests/test_gpu_secure.py); the two launches of sgo_secure_dev take
+0.012s and 0.055s, the call with its fills and copies 0.1s, listing and comparing the table 0.1s"""
 import ctypes as C
 import functools
 
@@ -33,6 +37,7 @@ from tests import keys_model as K
 from tests import launch_walk as W
 from tests import race_cases as RC
 from tests import race_model as RM
+from tests import secure_cases as SEC
 from tests import solve_cases as SC
 from tests import solve_model as SM
 from tests import tactics_cases as TC
@@ -218,6 +223,55 @@ def test_race_three_trips(S, asked):
     _whole(got["n_pairs"], _listed(n_pairs, index, R, FILL32), ("race", S, asked, "n_pairs"))
     _whole(got["rows"], _listed(rows, index, R, FILL32), ("race", S, asked, "rows"))
     _whole(got["regions"], _listed(regions, index, R, FILL32), ("race", S, asked, "regions"))
+
+
+# ---- secure --------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _secure_tables(S):
+    """(records [R], table int16 [R + 1, N, 4], sets uint32 [R + 1, 4, NW], counts int32 [R + 1, 8]); row R, out of range: zeros"""
+    names, recs = SEC.case_records(S)
+    R = W.secure_listed(len(recs), W.secure_geometry(S)[3])
+    want = SEC.case_model(S, 0)
+    out = []
+    for k in ("table", "sets", "counts"):
+        t = np.zeros((R + 1,) + want[k].shape[1:], want[k].dtype)
+        t[:R] = want[k][:R]
+        out.append(t)
+    return (recs[:R],) + tuple(out)
+
+
+@pytest.mark.parametrize("S", SIZES)
+def test_secure_past_the_grid_cap(S):
+    """k_secure with one workgroup per pair of candidates (sgo_secure_mode forces ch = pairs: 13 and 181), n * ch units behind the
+    cap of 1 << 24: 1 296 001 rows at 5x5 -- unit 2^24 - 1 is pair 0 of row 1 290 555, whose other pairs belong to the second trip,
+    and 5 445 rows lie wholly in it -- and 97 999 rows at 19x19 (row 92 691 astride the cap at pair 145, 5 307 rows behind it).
+    Tables (259 MB and 283 MB), sets and counts whole against the model's rows of the case set, the two rows behind n included.
+    These are the row counts first chosen, nothing was lowered: the launches take 12 ms and 55 ms, and what the 19x19 case spends
+    beyond a second is the model's case set, which the process computes once."""
+    from sejonggo_amd import _lib as L
+    from tests import test_gpu_secure as G
+    lib = L.require_gpu()
+    ch, n, astride, first_whole, k0 = W.secure_geometry(S)
+    recs, table, sets, counts = _secure_tables(S)
+    R = len(recs)
+    assert astride * ch < W.SECURE_CAP < first_whole * ch and n - first_whole >= 5000 and ch == (S * S + 1) // 2
+    index = W.wrapped_index(n, first_whole, R)
+    rec = W.record_of(index, R)
+    # the expected rows themselves tell a row of the second trip from both rows its units have their twins in
+    i = np.arange(astride, n)
+    for back in (first_whole - 1, first_whole):
+        a, b = rec[i], rec[np.maximum(i - back, 0)]
+        assert ((table[a] != table[b]).any(axis=(1, 2)).mean() > 0.8), (S, back)
+    prev = lib.sgo_secure_mode(-1)
+    try:
+        lib.sgo_secure_mode(ch)
+        assert lib.sgo_secure_mode(-1) == ch
+        got = G._run(S, recs, index, 0, pad=2)
+    finally:
+        lib.sgo_secure_mode(prev)
+    _whole(got["counts"], _listed(counts, index, R, FILL32), ("secure", S, "counts"))
+    _whole(got["sets"], _listed(sets, index, R, FILL32), ("secure", S, "sets"))
+    _whole(got["table"], _listed(table, index, R, G.FILL16), ("secure", S, "table"))
 
 
 # ---- rollout start ------------------------------------------------------------------------------------------------------------

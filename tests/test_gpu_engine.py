@@ -131,13 +131,16 @@ def _many_concurrent_games(L, net_kind):
     eng.close()
 
 
-def _compare_with_oracle(eng, games, slots, S, sims, E, stop, nm, uni, noises, net, komi=5.5):
+def _compare_with_oracle(eng, games, slots, S, sims, E, stop, nm, uni, noises, net, komi=5.5, resign=None):
+    """resign: a threshold (or None) per slot, for populations whose games may end before their nm-th move (a resignation, two
+    passes): such a game is as long as the oracle's; without it every game has nm moves"""
     from oracle import oracle as ora
     by_slot = {gd["slot"]: gd for gd in games}
     for s in slots:
-        g = ora.Game(S, sims, E, stop, nm, komi=komi, uniforms=uni[s], noises=noises[s:s + 1]).run(net)
+        r = None if resign is None else resign[s]
+        g = ora.Game(S, sims, E, stop, nm, komi=komi, uniforms=uni[s], noises=noises[s:s + 1], resign=r).run(net)
         gd = by_slot[s]
-        assert g.n_moves == len(gd["moves"]) == nm, s
+        assert g.n_moves == len(gd["moves"]) and (g.n_moves == nm or resign is not None), s
         for i, mv in enumerate(gd["moves"]):
             m = g.move(i)
             assert mv["move"][0] + S * mv["move"][1] == m["action"] or (mv["move"][1] == S and m["action"] == S * S), (s, i)

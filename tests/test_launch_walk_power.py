@@ -58,6 +58,52 @@ def test_row_counts_and_index_lists_notice_every_switch(what):
                 assert np.array_equal(bad, good), (what, S, fault)
 
 
+@pytest.mark.parametrize("S", [5, 19])
+def test_secure_row_counts_notice_every_switch(S):
+    """k_secure with one workgroup per pair of candidates: n * ch units behind a cap of 1 << 24, so a ROW can straddle the cap.
+    The row count puts one row astride it and at least 5 000 rows wholly behind it; every unit of the second trip names another
+    record than its twin one trip earlier (or both are out of range); one_trip, short_stride and stale_trip each change entries
+    of the row astride the cap and of the whole rows behind it, and nothing before the cap.  A launch of one-unit blocks cannot
+    hold a partial block or a lone half-wave."""
+    from tests import secure_cases
+    ch, n, astride, first_whole, k0 = W.secure_geometry(S)
+    cap = W.SECURE_CAP
+    assert ch == (S * S + 1) // 2 and astride * ch < cap < first_whole * ch and 0 < k0 < ch and cap == astride * ch + k0
+    assert (astride, k0) == {5: (1290555, 1), 19: (92691, 145)}[S]
+    assert n - first_whole >= 5000 and n * ch < 2 * cap              # 5 000 whole rows in the second trip, and no third trip
+    assert n * S * S * 8 < 300 << 20                                 # the table: under 300 MB
+    R0 = len(secure_cases.case_records(S)[1])
+    R = W.secure_listed(R0, first_whole)
+    assert R > 4 and R0 - R == (1 if S == 5 else 0) and all((first_whole + d) % R for d in (-1, 0, 1))
+    index = W.wrapped_index(n, first_whole, R)
+    rec = W.record_of(index, R)
+    oor = rec == R
+    assert oor[n - 1] and oor[:astride].any() and oor[first_whole:].any() and not oor[astride]
+    # every unit behind the cap and its twin one trip earlier
+    u = np.arange(cap, n * ch, dtype=np.int64)
+    a, b = rec[u // ch], rec[(u - cap) // ch]
+    assert ((a != b) | ((a == R) & (b == R))).all()
+    first = astride - 2                                              # two rows of the first trip, the row astride, everything behind
+    good = W.secure_entries(S, index, R, first=first)
+    assert (good[:n - first] != W.FILL).all() and (good[n - first:] == W.FILL).all() and good.shape == (n - first + 2, ch)
+    assert np.array_equal(good[:n - first], rec[first:n, None] * ch + np.arange(ch)[None, :])
+    for fault in W.FAULTS:
+        bad = W.secure_entries(S, index, R, fault, first=first)
+        assert (bad[n - first:] == W.FILL).all()
+        rows = np.flatnonzero((bad != good).any(axis=1)) + first
+        if not W.applies(fault, 1):
+            assert len(rows) == 0, (S, fault)
+            continue
+        assert len(rows) > 0 and rows[0] == astride, (S, fault, rows[:4])
+        # the row astride the cap: its pairs below k0 are right, the rest wrong
+        assert np.array_equal(bad[2, :k0], good[2, :k0]) and (bad[2, k0:] != good[2, k0:]).all(), (S, fault)
+        whole = np.setdiff1d(np.arange(first_whole, n), rows)
+        if fault == "short_stride":                                  # the unit before: the neighbouring pair, of the row before for pair 0
+            assert len(whole) == 0
+        else:                                                        # one_trip / stale_trip: all but the rows out of range themselves
+            assert len(whole) <= n // W.EVERY + 1 and (oor[whole] | (fault == "stale_trip")).all(), (S, fault, len(whole))
+
+
 def test_rollout_start_cases_notice_every_switch():
     """k_rollout_start walks one word or one ownership cell per thread.  Case (b) copies three trips of words, (a) and (c) end in a
     partial block, (a) is the only one whose walk is longer than its record words; a cell only ever receives a zero, so a cell
