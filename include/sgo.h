@@ -54,7 +54,8 @@ extern "C" {
  *   (sgo_life*, sgo_session_life), the "shape search" section (sgo_shape_compile, sgo_shapes*, sgo_session_shapes), the "move
  *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
  *   section (sgo_secure*, sgo_session_secure), the "life and death" section (sgo_solve*, sgo_session_solve), the "capturing races"
- *   section (sgo_race*, sgo_session_race), the "connections" section (sgo_connect*, sgo_session_connect). */
+ *   section (sgo_race*, sgo_session_race), the "connections" section (sgo_connect*, sgo_session_connect), the "superko" section
+ *   (sgo_superko*; no session form). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -1206,6 +1207,60 @@ int sgo_influence(int S, int n, const uint32_t *records, const uint32_t *dead, i
  * a NULL argument other than dead. */
 int sgo_session_influence(sgo_ctx *ctx, int n, const int32_t *slots, const uint32_t *dead, int dilate, int erode_moyo, int erode_terr,
                           int32_t *status, int16_t *values, uint32_t *sets, int32_t *counts, void *stream);
+
+/* ---- superko: which moves would repeat an earlier position of the game? ------------------------------------------------------------ */
+/* The one analysis that needs a record AND the game behind it (csrc/sgo_superko.hip).  Everything is integer.  N = S * S,
+ * W = sgo_plane_words(S).
+ * Row i names a record r = d_index[i] (d_index NULL: r = i) of d_records [n_records][sgo_packed_words(S)] and the first record
+ * f = d_first[i] of its game.  The HISTORY of the row is the records f .. r in order, the current one included: what
+ * sgo_records_replay writes for one game (f = base_g).  Nothing asks that the history come from a real game: it is a list of
+ * positions.
+ * A POSITION is the set of stones of planes 0 / 1, bits a < N, exactly as the "position keys" section reads them (the flag is not a
+ * stone; padding bits and planes 2..15 are no part of it); its side to move is the to-play flag.
+ * `rule` selects the comparison: 0 POSITIONAL, two positions are equal when their stones are equal; 1 SITUATIONAL, their stones are
+ * equal and the same side is to move.
+ * For every EMPTY point a of record r the side to move plays a by one ply of sgo_make_play (captures removed, then suicide
+ * executed); the result is P' with the OTHER side to move.  The ply is played whether or not it is legal.
+ *   a REPEATS when some h in [f, r] holds a position equal to P' under `rule`;
+ *   back[a] = r - h for the LARGEST such h.  A simple ko gives 1; a single-stone suicide gives 0 under rule 0 (P' is the current
+ *   position) and can never match h = r under rule 1.
+ * d_sets uint32 [n][3][W], padding bits zero:
+ *   0 repeat          the empty points that repeat
+ *   1 extra           repeat AND the record's own legal set (sgo_legal_moves with `prev` from plane 2 / 3, what sgo_moves_dev calls
+ *                     ALLOWED at side 0): the points superko forbids and the inherited rule (play.py:78-80) allows
+ *   2 legal_superko   the legal set without repeat, with the pass bit N always set: a drop-in legal bitset
+ * A pass is never in set 0 or 1.
+ * d_back int16 [n][N]: back[a] for the points of repeat, -1 everywhere else (stones included).
+ * d_counts int32 [n][8]:
+ *   0 |repeat|     1 |extra|
+ *   2 the largest back over extra, 0 when it is empty     3 the lowest point that has it, -1 when extra is empty
+ *   4 seen = r - h for the largest h in [f, r - 1] whose position equals the CURRENT position of r under `rule`, 0 when there is
+ *     none: the game has already cycled when it reaches this record
+ *   5 the number of history records looked at
+ *   6 key matches that the exact comparison refuted (below)
+ *   7 1 when the history was longer than SGO_SUPERKO_MAX_HISTORY(S) and only its most recent part was read, else 0
+ * A row with r outside [0, n_records), f < 0 or f > r gives the ZERO ROW: sets 0, back all -1, counts 0.
+ * KEYS.  Stage 1 writes key_0 of the "position keys" section (with the flag term under rule 1, without it under rule 0) of every
+ * record [0, n_records) into the work array d_keys; stage 2 compares the key of P' with the keys of the history.  A verdict NEVER
+ * rests on a key alone: every key match is confirmed by comparing the stones of P' with planes 0 / 1 of record h (and the flag under
+ * rule 1); a match the comparison refutes is counted in counts[6] and the search goes on with the next smaller h.
+ *
+ * sgo_superko_dev: TWO launches on `stream` (the keys; one half-wavefront per row), no allocation, no synchronisation, capturable;
+ * n == 0 is a no-op; rows >= n are not written.  d_keys is uint64 [n_records], overwritten.  SGO_ERR_ARG: an unsupported S, n < 0,
+ * n_records < 0, rule outside {0, 1}, a NULL d_records, d_first, d_keys or output.
+ * LEFT OUT: superko inside the search, self-play and rollouts (the engine keeps the reference's one-ply rule); natural situational
+ * superko; colour-swapped and symmetric repetition; histories longer than SGO_SUPERKO_MAX_HISTORY(S), beyond the flag.
+ * There is NO session form: a session slot holds its root record and seven positions of history, not the game.  A caller that
+ * holds a game replays its move list (sgo_records_replay) and asks for the last record with f = 0. */
+#define SGO_SUPERKO_MAX_HISTORY(size) (SGO_SETUP_MAX_MOVES(size) + 1)   /* the longest game a replay can write */
+int sgo_superko_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_first,
+                    int rule, uint64_t *d_keys, uint32_t *d_sets, int16_t *d_back, int32_t *d_counts, void *stream);
+/* The same for HOST buffers: records [n_records][sgo_packed_words(S)], index [n] or NULL, first [n] (copy in, run, copy back). */
+int sgo_superko(int S, int n_records, const uint32_t *records, int n, const int32_t *index, const int32_t *first, int rule,
+                uint32_t *sets, int16_t *back, int32_t *counts);
+/* 1: stage 2 compares only the low 6 bits of the keys, so that the confirmation path is taken often (for tests); every output
+ * but counts[6] stays the same.  0: all 64 bits (default).  Returns the previous mode; other values only query. */
+int sgo_superko_mode(int mode);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

@@ -46,6 +46,7 @@ SYMBOLS = [
     "sgo_solve_dev", "sgo_solve", "sgo_session_solve",
     "sgo_race_dev", "sgo_race", "sgo_session_race",
     "sgo_connect_dev", "sgo_connect", "sgo_session_connect",
+    "sgo_superko_dev", "sgo_superko", "sgo_superko_mode",
 ]
 
 
@@ -221,6 +222,9 @@ def load():
     lib.sgo_influence_dev.argtypes =[C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4
     lib.sgo_influence.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3
     lib.sgo_session_influence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5
+    lib.sgo_superko_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_superko.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_superko_mode.argtypes = [C.c_int]
     _lib = lib
     return lib
 

@@ -30,6 +30,9 @@ int launch_race(int S, int n, const uint32_t *d_records, int n_records, const in
 int launch_connect(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_ask, const uint32_t *d_region,
                    int rules, int cut_libs, int max_region, int max_nodes, int max_pairs, int32_t *d_n_pairs, int32_t *d_rows, uint32_t *d_regions,
                    int16_t *d_groups, int32_t *d_group_counts, hipStream_t st);
+// superko reads a record and the records of its game before it (d_first), through the work array d_keys [n_records]: two launches
+int launch_superko(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_first, int rule,
+                   uint64_t *d_keys, uint32_t *d_sets, int16_t *d_back, int32_t *d_counts, hipStream_t st);
 
 // The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
 // (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip) and of the solve parameters (csrc/sgo_solve.hip)

@@ -17,6 +17,8 @@
 // records (INLINE = false, the product), or is computed where it is needed (INLINE = true: eight splitmix rounds per stone;
 // sgo_keys_mode selects it for A/B timing).  Same bits either way.
 //
+// z and the row walk stone_keys are in sgo_zkeys.hpp, which sgo_superko.hip shares.
+//
 // Nothing branches around a shuffle on a per-record condition: a half whose row is out of range or does not exist reads no
 // stones and only its final stores differ.
 #include <string.h>
@@ -24,19 +26,9 @@
 #include "sgo_analysis.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_rows.hpp"
+#include "sgo_zkeys.hpp"
 
 namespace sgo {
-
-__host__ __device__ __forceinline__ uint64_t sm64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// c: 0 black, 1 white, 2 = "white to play" (a = 0)
-__host__ __device__ __forceinline__ uint64_t zkey(int S, int c, int a) {
-    return sm64(((uint64_t)S << 24) | ((uint64_t)c << 16) | (uint64_t)a);
-}
 
 // L_k[y * S + x], the table sgo_sym_lut(S, k) writes (build_sym_lut's rotations and reflections, in integers)
 template <int S>
@@ -51,39 +43,6 @@ SGO_DEV int sym_point(int k, int x, int y) {
     case 5: return (m - y) * S + (m - x);      // rotation 180
     case 6: return (m - x) * S + y;            // rotation 270
     default: return (m - x) * S + (m - y);     // right diagonal
-    }
-}
-
-// The eight keys of one record WITHOUT the to-play word, XOR-reduced over the half: every lane of the half returns them all.
-// rec == nullptr (uniform over the half): no stones.
-template <int S, bool INLINE>
-SGO_DEV void stone_keys(const uint32_t *rec, const uint64_t *zt, int y, uint64_t (&key)[8]) {
-    using G = Geo<S>;
-    constexpr int m = S - 1;
-    uint32_t row[2] = {0u, 0u};
-    if (rec) { row[0] = rows::load_row<S>(rec, y); row[1] = rows::load_row<S>(rec + G::NW, y); }
-    // L_k[y * S + x] = base[k] + x * step[k]
-    const int base[8] = {y * S, y, y * S + m, (m - y) * S, m - y, (m - y) * S + m, m * S + y, m * S + (m - y)};
-    constexpr int step[8] = {1, S, -1, 1, S, -1, -S, -S};
-#pragma unroll
-    for (int k = 0; k < 8; k++) key[k] = 0ull;
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        uint32_t bits = row[c];
-        while (bits) {
-            const int x = __builtin_ctz(bits);
-            bits &= bits - 1u;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int a = base[k] + x * step[k];
-                key[k] ^= INLINE ? zkey(S, c, a) : zt[c * G::N + a];
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) key[k] ^= (uint64_t)__shfl_xor((unsigned long long)key[k], o, 32);
     }
 }
 

@@ -159,6 +159,9 @@ class DeviceSejongGoEngine(object):
             raise ValueError("the device tree is dropped by clear_board only")
 
     def close(self):
+        if getattr(self, "_game_records", None) is not None:
+            self._game_records.close()
+            self._game_records = None
         if self._own and self.engine is not None:
             self.engine.close()
             if self._workers:
@@ -295,6 +298,23 @@ class DeviceSejongGoEngine(object):
                                            max_region=max_region, max_nodes=max_nodes))
         return v, np.asarray(real_board(self.board), dtype=np.int8).reshape(-1)
 
+    def superko(self, rule=0):
+        """Which moves of the side to move would repeat an earlier position of THIS game (include/sgo.h "superko"): a
+        superko.Superko with one row.  A session slot holds seven positions of history, not the game, so the move list is replayed
+        into a records object of one game (created at the first call, sgo_records_replay) and the analysis runs on its last record
+        with the whole game as history.  rule 0 / "positional", 1 / "situational"."""
+        from .records import DeviceRecords, max_entries_of
+        from .superko import Superko, rule_of
+        rule = rule_of(rule)
+        if getattr(self, "_game_records", None) is None:
+            self._game_records = DeviceRecords(self.size, 1, max_entries_of(self.size), self.engine.device.index or 0)
+        rec, n = self._game_records, len(self.moves)
+        status, fail_at = rec.replay([n], [0], [a for a, _ in self.moves], [c for _, c in self.moves])
+        if int(status[0]):
+            raise ValueError("the move list does not replay: entry %d refused (%d)" % (int(fail_at[0]), int(status[0])))
+        sets, back, counts = rec.superko([n], [0], rule, n + 1)
+        return Superko(self.size, sets.cpu().numpy().view(np.uint32), back.cpu().numpy(), counts.cpu().numpy())
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -317,10 +337,18 @@ class GTPFailure(Exception):
 
 
 class GTPEngine(object):
-    def __init__(self, engine=None, book=None, book_min=1):
+    def __init__(self, engine=None, book=None, book_min=1, superko=None):
         """book: a records.Book (or the path of its .npz) genmove answers from while it holds a legal move played at least
-        book_min times; it needs the device engine (position keys come from the session slot)."""
+        book_min times; it needs the device engine (position keys come from the session slot).
+        superko: None, or "positional" / "situational" (0 / 1): `play` refuses a move that repeats an earlier position of the game
+        and genmove never makes one; it needs the device engine too (the move list is replayed on the device)."""
         self._komi = 0
+        self.superko_rule = None
+        if superko is not None:
+            from .superko import rule_of
+            if engine is None or not hasattr(engine, "superko"):
+                raise ValueError("superko needs the device engine (gtp --device)")
+            self.superko_rule = rule_of(superko)
         self.book, self.book_min = None, int(book_min)
         if book is not None:
             if engine is None or not hasattr(engine, "keys"):
@@ -346,7 +374,7 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "quit"])
+                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "sgo-superko", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -379,10 +407,32 @@ class GTPEngine(object):
             x += 1
         return string.ascii_uppercase[x] + str(row + 1)
 
+    def _to_move(self):
+        return int(np.asarray(self.sejong_engine.board)[0, 0, 0, -1])
+
     def play(self, color, move):
         x, y = self.parse_move(move)
+        if self.superko_rule is not None and y < self.size and COLOR_TO_PLAYER[color] == self._to_move():
+            # the table is the side to move's; a stone placed out of turn is set-up, as everywhere else
+            if self.sejong_engine.superko(self.superko_rule).played(0, y * self.size + x)[0]:
+                raise GTPFailure("illegal move")
         self.board, self.player = self.sejong_engine.play(COLOR_TO_PLAYER[color], x, y)
         return ""
+
+    def _superko_move(self, player, extra):
+        """genmove while superko forbids what the inherited rule allows: the search runs without moving, and the child with the
+        largest (visits, mean, higher index) that is not forbidden is played as an external move; a pass when there is none"""
+        self.sejong_engine.analyze()
+        r = self.sejong_engine.report(top=1, depth=1)
+        N, Q = np.asarray(r["N"][0]), np.asarray(r["Q"][0])
+        best = None
+        for a in range(len(N)):
+            if N[a] >= 0 and a not in extra and (best is None or (int(N[a]), float(Q[a]), a) > (int(N[best]), float(Q[best]), best)):
+                best = a
+        points = self.size * self.size
+        x, y = (best % self.size, best // self.size) if best is not None and best < points else (0, self.size)
+        self.board, self.player = self.sejong_engine.play(player, x, y)
+        return self.print_move(x, y)
 
     def _book_moves(self):
         """[(action, count, wins, losses)] of the book for the position on the board, most played first; [] without a book"""
@@ -392,15 +442,20 @@ class GTPEngine(object):
 
     def genmove(self, color):
         player = COLOR_TO_PLAYER[color]
-        if self.book is not None and player == int(np.asarray(self.sejong_engine.board)[0, 0, 0, -1]):
+        extra = set()
+        if self.superko_rule is not None and player == self._to_move():
+            extra = {a for a, _ in self.sejong_engine.superko(self.superko_rule).extra(0)}
+        if self.book is not None and player == self._to_move():
             rows = [r for r in self._book_moves() if r[1] >= self.book_min]
             legal = self.sejong_engine.legal() if rows else None
             for a, _, _, _ in rows:
-                if legal[a]:
+                if legal[a] and a not in extra:
                     # an external move as far as the session is concerned: its tree follows as for any play
                     x, y = (a % self.size, a // self.size) if a < self.size * self.size else (0, self.size)
                     self.board, self.player = self.sejong_engine.play(player, x, y)
                     return self.print_move(x, y)
+        if extra:
+            return self._superko_move(player, extra)
         x, y, _, _, self.board, self.player = self.sejong_engine.genmove(player)
         return self.print_move(x, y)
 
@@ -549,6 +604,16 @@ class GTPEngine(object):
             else:
                 raise GTPFailure("syntax error")
         return format_kind(self._engine_method("move_outcomes")(side), 0, kind, self._vertex)
+
+    def sgo_superko(self, *words):
+        """Private extension `sgo-superko [situational]`: the moves of the side to move that would repeat an earlier position of
+        the game (include/sgo.h "superko") -- one line `V K` per point in ascending point order, K plies back (1: a ko
+        recapture), with `forbidden` appended where the inherited ko rule would allow the move.  Positional (equal stones) by
+        default; `situational` asks for the same side to move as well.  Empty when nothing repeats."""
+        from .superko import format_repeat
+        if len(words) > 1 or (words and words[0] not in ("positional", "situational")):
+            raise GTPFailure("syntax error")
+        return format_repeat(self._engine_method("superko")(words[0] if words else "positional"), 0, self._vertex)
 
     def sgo_secure(self, *words):
         """Private extension `sgo-secure [opponent] [min K]`: what one more stone makes pass-alive (include/sgo.h "securing moves")
@@ -727,7 +792,7 @@ class GTPEngine(object):
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
                "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race",
-               "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups", "sgo-superko": "sgo_superko"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")
@@ -744,14 +809,19 @@ class GTPEngine(object):
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 
-def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1):
+def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, superko=None):
     """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine).
-    book (`--book FILE [--book-min N]`, device only): genmove plays from the opening book records.py wrote while it has a move."""
+    book (`--book FILE [--book-min N]`, device only): genmove plays from the opening book records.py wrote while it has a move.
+    superko (`--superko positional|situational`, device only): `play` refuses and genmove avoids a move that repeats an earlier
+    position of the game."""
     if book is not None and not device:
         sys.stderr.write("--book needs the device engine: run with --device\n")
         return 2
+    if superko is not None and not device:
+        sys.stderr.write("--superko needs the device engine: run with --device\n")
+        return 2
     engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None, book=book,
-                       book_min=book_min)
+                       book_min=book_min, superko=superko)
     for line in inp:
         for cmd in line.split("\n"):
             res = engine.parse_command(cmd)
@@ -769,8 +839,10 @@ def _cli(argv):
     ap.add_argument("--device", action="store_true", help="the game lives on the device engine")
     ap.add_argument("--book", default=None, help="an opening book (.npz of `python -m sejonggo_amd.records --book`); needs --device")
     ap.add_argument("--book-min", type=int, default=1, help="play a book move only when it was played at least N times (default 1)")
+    ap.add_argument("--superko", default=None, choices=("positional", "situational"),
+                    help="refuse and avoid moves that repeat an earlier position of the game; needs --device")
     a = ap.parse_args(argv)
-    return main(device=a.device, book=a.book, book_min=a.book_min)
+    return main(device=a.device, book=a.book, book_min=a.book_min, superko=a.superko)
 
 
 if __name__ == "__main__":

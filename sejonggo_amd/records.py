@@ -4,7 +4,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
                                         [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt] [--moves]
-                                        [--influence]
+                                        [--influence] [--superko [positional|situational]]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -50,6 +50,12 @@ INFLUENCE (include/sgo.h "influence", csrc/sgo_influence.hip).  --influence read
 (the classical territory triple; the stones unconditional life proves dead lifted first) and prints per bucket of --bucket plies the
 mean |margin|, the mean number of neutral points and the mean moyo beyond territory per colour, and per game the estimate at the
 last position (before komi: a Record keeps none).  An estimate, not a proof.
+
+SUPERKO (include/sgo.h "superko", csrc/sgo_superko.hip).  --superko compares what every move of every position would give with
+every earlier position of the SAME game (positional: equal stones; situational: and the same side to move) and prints per game the
+first move that reached a position seen before (passes apart), every played move that repeats although the inherited one-ply ko
+rule allowed it, the number of ko recaptures played through (a recorded move is played, not filtered), and per bucket of --bucket
+plies the share of positions in which superko forbids a move that rule allows.
 
 A file that does not parse, whose board is not the requested size or whose list is longer than the replay takes is counted and
 skipped; a record that holds a move onto a stone or off the board is cut short there and reported.  PyTorch is plumbing here
@@ -482,6 +488,22 @@ class DeviceRecords(object):
                     torch.zeros((0, self.N), dtype=torch.int16, device=self.device), torch.zeros((0, 4), dtype=torch.int32, device=self.device))
         return connect_dev(self.S, self.records, index, None, None, rules, cut_libs, max_region, max_nodes, max_pairs, self.lib)
 
+    def superko(self, index, first, rule=0, n_records=None):
+        """(sets int32 [n, 3, NW] holding the uint32 bit patterns, back int16 [n, N], counts int32 [n, 8]) device tensors of the listed
+        records, each with the history first[i] .. index[i] (sgo_superko_dev, two launches; include/sgo.h "superko").  An index
+        outside the object, a negative first or one behind the record gives the zero row (back all -1).  n_records: how many
+        records of the object are in use (the first stage keys them all; None: the whole object)."""
+        from .superko import superko_dev
+        torch = self.torch
+        index, first = self._index(index), self._index(first)
+        n = int(index.shape[0])
+        assert int(first.shape[0]) == n
+        if n == 0:
+            return (torch.zeros((0, 3, self.NW), dtype=torch.int32, device=self.device), torch.zeros((0, self.N), dtype=torch.int16, device=self.device),
+                    torch.zeros((0, 8), dtype=torch.int32, device=self.device))
+        used = self.cap if n_records is None else max(0, min(self.cap, int(n_records)))
+        return superko_dev(self.S, self.records, index, first, rule, self.lib, n_records=used)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -631,12 +653,13 @@ class RecordSet(object):
             yield ch
 
     # ------------------------------------------------------------------ one row per record: tactics, life, influence, shapes
-    def _per_record(self, attr, call, wrap, stones=False):
+    def _per_record(self, attr, call, wrap, stones=False, games=False):
         """Generator of Chunks as `replay` gives them, each with `attr` = wrap(*call(index)) over the records of the chunk (one
-        backend call per chunk) and, with stones=True, ch.stones int8 [records, N] (+1 black, -1 white) of the same rows."""
+        backend call per chunk) and, with stones=True, ch.stones int8 [records, N] (+1 black, -1 white) of the same rows.
+        games=True: call(index, first) with the first record of each record's game (-1 where index is)."""
         for ch in self.replay():
             index = self._record_index(ch)
-            setattr(ch, attr, wrap(*call(index)))
+            setattr(ch, attr, wrap(*(call(index, self._record_first(ch)) if games else call(index))))
             if stones:
                 ch.stones = np.asarray(self.backend.stones(index), dtype=np.int8)
             yield ch
@@ -647,6 +670,13 @@ class RecordSet(object):
         for _, _, base, _, _, played in ch.walk():
             index[base:base + played + 1] = np.arange(base, base + played + 1)
         return index
+
+    def _record_first(self, ch):
+        """int32 [records of the chunk]: the first record of the record's game (Chunk.walk's base), -1 behind a refused entry"""
+        first = np.full(len(ch.action) + len(ch.games), -1, np.int32)
+        for _, _, base, _, _, played in ch.walk():
+            first[base:base + played + 1] = base
+        return first
 
     def tactics(self, max_chains=128, stones=False):
         """Generator of Chunks as `replay` gives them, each with `tactics`, a tactics.Tactics with one row per RECORD of the
@@ -718,6 +748,16 @@ class RecordSet(object):
         return self._per_record("connect", lambda index: self.backend.connect(index, rules, cut_libs, max_region, max_nodes, max_pairs),
                                 lambda n_pairs, rows, regions, groups, counts: Connect(self.S, _host(n_pairs), _host(rows), _host(regions, np.uint32),
                                                                                        _host(groups, np.int16), _host(counts)), stones)
+
+    def superko(self, rule=0):
+        """Generator of Chunks as `replay` gives them, each with `superko`, a superko.Superko with one row per RECORD of the chunk (one
+        backend call per chunk), rows as in `life`: which moves of every position would repeat an earlier position of ITS game --
+        the history of a record is its game's records from the first (Chunk.walk's base) to itself.  Records that were not written
+        give the zero row."""
+        from .superko import Superko, rule_of
+        rule = rule_of(rule)
+        return self._per_record("superko", lambda index, first: self.backend.superko(index, first, rule, len(index)),
+                                lambda sets, back, counts: Superko(self.S, _host(sets, np.uint32), _host(back, np.int16), _host(counts)), games=True)
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -1067,6 +1107,23 @@ def connect_table(record_set, width=20, **kw):
     return bucket_table(np.array(ply), np.stack(rows), np.array(n_pairs), np.stack(counts), width)
 
 
+def superko_report(record_set, rule=0, width=20):
+    """What `--superko` prints, from one RecordSet.superko pass: {"rule", "games": [superko.game_report per game], "buckets":
+    superko.bucket_table over every written record (ply = the number of entries before it), "positions_with_extra", "max_back"}."""
+    from .superko import bucket_table, game_report, rule_of
+    rule = rule_of(rule)
+    games, ply, extra, max_back = [], [], [], 0
+    for ch in record_set.superko(rule):
+        v = ch.superko
+        for _, g, base, off, _, played in ch.walk():
+            games.append(game_report(record_set.records[g].name, v, base, played, ch.action[off:off + played]))
+            ply += list(range(played + 1))
+            extra += [int(c) for c in v.counts[base:base + played + 1, 1]]
+            max_back = max([max_back] + [int(c) for c in v.counts[base:base + played + 1, 2]])
+    return {"rule": ("positional", "situational")[rule], "games": games, "buckets": bucket_table(ply, extra, width) if ply else [],
+            "positions_with_extra": int(sum(1 for c in extra if c > 0)), "max_back": max_back}
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -1130,6 +1187,11 @@ def main(argv=None, out=sys.stdout):
                     help="Bouzy's influence map of every position (an estimate; proved-dead stones lifted): per 20-move bucket the "
                          "mean |margin|, mean neutral points and mean moyo beyond territory per colour; per game the estimate at "
                          "the last position")
+    ap.add_argument("--superko", nargs="?", const="positional", default=None, choices=("positional", "situational"),
+                    help="which moves would repeat an earlier position of their game: per game the first move that reached a position "
+                         "seen before (passes apart) and every played move that the ko approximation let through although it repeats; "
+                         "the ko recaptures played through; per 20-move bucket the share of positions where superko forbids a move "
+                         "the inherited rule allows")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -1235,6 +1297,12 @@ def main(argv=None, out=sys.stdout):
                     d["moyo_beyond_white"]))
             for d in doc["influence"]["games"]:
                 out.write("influence %s plies %d estimate %s\n" % (d["name"], d["plies"], score_text(d["margin"])))
+        if a.superko:
+            from .superko import format_report
+            from .review import vertex
+            doc["superko"] = superko_report(rs, a.superko, a.bucket)
+            out.write("superko (%s)\n" % doc["superko"]["rule"])
+            out.write(format_report(doc["superko"]["games"], doc["superko"]["buckets"], lambda p: vertex(p, size)) + "\n")
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

@@ -4,7 +4,7 @@ all positions) and read back in one launch (report).
 
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
-                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race] [--connect]
+                                           [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race] [--connect] [--superko [RULE]]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -29,7 +29,11 @@ looked at and nothing is read out.  --influence reads Bouzy's influence map of e
 `estimate` (live stones + territory of black minus white's, minus the record's komi, in front of the move) and `gain` (the change of
 that margin across the move in the mover's favour), and a last line names the three moves with the highest and the three with the
 lowest gain.  An estimate, and numbers, not verdicts.  Given without --sims, --net and --rollouts it searches nothing and loads no
-net: the lines then hold the move and the two figures only.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+net: the lines then hold the move and the two figures only.  --superko [positional|situational] compares what every move of every
+position would give with every earlier position of the game (records.RecordSet.superko; include/sgo.h "superko") and flags a played
+move `repeats K` when it recreated the position K records before the one it was played from (1: a ko recapture), and a position
+`superko-forbidden V ...` with the moves superko forbids although the inherited ko rule allows them; like --influence it loads no
+net when nothing else asks for one.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import contextlib
 import json
@@ -293,6 +297,29 @@ def add_secure(rows, game, record_set=None):
     return rows
 
 
+def superko_rows(game, record_set, rule=0):
+    """{move number: flags} of the B / W moves of `game` (superko.review_flags) from one RecordSet.superko pass over a set that holds
+    the game as its only record: `repeats K` for a played move that recreated an earlier position of the game, `superko-forbidden V
+    ...` for a position in which superko forbids moves the inherited rule allows.  The table is the side to move's: a stone placed
+    out of turn is read as that side's."""
+    from .superko import review_flags
+    out = {}
+    for ch in record_set.superko(rule):
+        v = ch.superko
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = review_flags(v, r, action, lambda a: vertex(a, game.size))
+    return out
+
+
+def add_superko(rows, game, record_set=None, rule=0):
+    """Adds `superko_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = superko_rows(game, rs, rule)
+    for row in rows:
+        row["superko_flags"] = list(found.get(row["move_number"], []))
+    return rows
+
+
 def solve_rows(game, record_set):
     """{move number: flags} of the B / W moves of `game` (solve.review_flags) from one RecordSet.solve pass over a set that holds
     the game as its only record: the verdicts of the same chain in the position before and after the move."""
@@ -405,7 +432,7 @@ def format_row(row):
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
         list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or []) + \
-        list(row.get("race_flags") or []) + list(row.get("connect_flags") or [])
+        list(row.get("race_flags") or []) + list(row.get("connect_flags") or []) + list(row.get("superko_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -485,13 +512,17 @@ def main(argv=None, out=sys.stdout):
                     help="flag each played move against the connections a bounded reader decides in the position in front of it: cuts V "
                          "(the cut_move of an unsettled pair V of the opponent), joins V, missed-cut V at K, missed-join V at K (flags "
                          "from a bounded reader, not verdicts).  Like --influence it loads no net when nothing else asks for one")
+    ap.add_argument("--superko", nargs="?", const="positional", default=None, choices=("positional", "situational"),
+                    help="flag every played move that recreated an earlier position of the game (repeats K: K records back from the "
+                         "position it was played in) and every position in which superko forbids moves the inherited ko rule allows "
+                         "(superko-forbidden V ...).  Like --influence it loads no net when nothing else asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect or a.superko) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -527,6 +558,8 @@ def main(argv=None, out=sys.stdout):
         add_race(rows, game)
     if a.connect:
         add_connect(rows, game)
+    if a.superko:
+        add_superko(rows, game, rule=a.superko)
     if a.influence:
         add_influence(rows, game)
     for row in rows:
