@@ -55,7 +55,7 @@ extern "C" {
  *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
  *   section (sgo_secure*, sgo_session_secure), the "life and death" section (sgo_solve*, sgo_session_solve), the "capturing races"
  *   section (sgo_race*, sgo_session_race), the "connections" section (sgo_connect*, sgo_session_connect), the "superko" section
- *   (sgo_superko*; no session form). */
+ *   (sgo_superko*; no session form), the "light playouts" section (sgo_playout*, sgo_session_playout). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -1261,6 +1261,60 @@ int sgo_superko(int S, int n_records, const uint32_t *records, int n, const int3
 /* 1: stage 2 compares only the low 6 bits of the keys, so that the confirmation path is taken often (for tests); every output
  * but counts[6] stays the same.  0: all 64 bits (default).  Returns the previous mode; other values only query. */
 int sgo_superko_mode(int mode);
+
+/* ---- light playouts: ownership, score and move values from uniformly random games, no net -------------------------------------------- */
+/* Per listed record `per_row` random games that refuse to fill their own eyes, each played to its end inside one kernel
+ * (csrc/sgo_playout.hip): who ends up holding each point, the score distribution and an all-moves-as-first table.  An ESTIMATE of how
+ * the position ends, not a proof; no net, no host loop.  Everything is integer.  N = S * S.
+ * Row i names a record r = d_index[i] (d_index NULL: r = i) of d_records [n_records][sgo_packed_words(S)], read in place.  Per row
+ * per_row PLAYOUTS j run, each with the global id g = i * per_row + j as uint32: the position in the CALL, not the record index, as
+ * sgo_rollout_* numbers its sources.
+ * START of a playout = the start of a rollout: black / white = the bits a < N of planes 0 / 1; the side to move is the to-play flag
+ * (the top bit of the last word of plane 0; NOT a stone); `prev` of the first ply = plane 2 (black to move) or 3 (white), bits a < N,
+ * as sgo_rollout_step reads it; from the second ply on `prev` = the mover's stones one ply ago in the playout itself (so after a pass
+ * nothing is forbidden).  Passes in the record's history do not count: ply = 0, passes = 0.  touched = the points that hold a stone at
+ * the start; first = the empty set.  Padding bits and planes 4..15 are never read.
+ * EACH PLY, mover X, other colour O:
+ *   ALLOWED is exactly the set of the "life and death" section for the given `rules`: 0 = sgo_legal_moves, 1 = sound; the ko test is
+ *     word for word that section's (prev & ~own is exactly one point, and it is that point).
+ *   EYE = the EMPTY points whose every on-board 4-neighbour holds an X stone and of whose on-board diagonal neighbours fewer than T
+ *     hold an O stone; T = 2 when all four diagonals are on the board, else T = 1.  Empty diagonals do not count.
+ *   cand = ALLOWED minus EYE, k = |cand|.  k = 0: the playout passes, passes += 1.  Otherwise t = (uint64(draw(seed, g, ply)) * k) >> 32
+ *     with draw and mix exactly those of the "policy rollouts" section; the move is the (t + 1)-th lowest point of cand, played with one
+ *     ply of sgo_make_play; passes returns to 0; a point not in touched enters touched and, when X is also the side that was to move
+ *     at the start, first.
+ *   ply += 1.
+ * END: passes == 2 or ply == max_plies.  One that ends with fewer than two passes in a row is CAPPED.  max_plies <= 0 means 3 * N; a
+ * value above 4 * N is refused.  (Under rules = 0 random playouts need not end on their own: a ko can never be connected, because the
+ * connecting point has no empty neighbour and captures nothing; the cap ends them.  Under rules = 1 the cap is rarely reached.)
+ * SCORING is that of the "policy rollouts" section (play.py:244-292): a point is black's if it holds a black stone or is empty and
+ * reached by black only, the same for white; diff = black - white, komi-free.
+ * OUTPUTS per row, written and not added to:
+ *   own  int32 [2][N]   the number of playouts that end with the point black's, and with it white's
+ *   amaf int32 [2][N]   for the side to move at the start: [0][a] = the playouts with a in first, [1][a] = the sum over those of diff
+ *                       seen from that side (-diff for white).  Points occupied at the start have 0 in both.
+ *   sums int64 [8]      {black_wins, white_wins, draws, score_sum, score_sq_sum, plies_sum, capped, playouts}, the order of
+ *                       sgo_rollout_result
+ * Results do not depend on how playouts are dealt to the machine or in which order they finish: accumulation is integer adds only.
+ * A row whose record index is outside [0, n_records) gets all-zero outputs.  Illegal records go through the same definitions.
+ *
+ * sgo_playout_dev: d_own [n][2][N], d_amaf [n][2][N] or NULL, d_sums [n][8].  TWO launches on `stream` (the outputs are zeroed, then the
+ * playouts add into them), no allocation, no synchronisation, capturable; n == 0 is a no-op; rows >= n are not written.
+ * SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, rules outside {0, 1}, per_row outside [1, SGO_PLAYOUT_MAX_PER_ROW] (so that
+ * amaf [1][a] fits int32 at 19x19), n * per_row beyond int32, max_plies above 4 * N, a NULL d_records, d_own or d_sums. */
+#define SGO_PLAYOUT_MAX_PER_ROW 65536
+int sgo_playout_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int per_row, uint32_t seed, int rules,
+                    int max_plies, int32_t *d_own, int32_t *d_amaf, int64_t *d_sums, void *stream);
+/* The same for HOST buffers: records [n_records][sgo_packed_words(S)], index [n] or NULL, amaf or NULL (copy in, run, copy back). */
+int sgo_playout(int S, int n_records, const uint32_t *records, int n, const int32_t *index, int per_row, uint32_t seed, int rules,
+                int max_plies, int32_t *own, int32_t *amaf, int64_t *sums);
+/* The root positions of the listed HOLDING session slots of `ctx` (what sgo_game_board shows), read in place; waits for `stream`.
+ * HOST arrays: status [n], own [n][2][N], amaf [n][2][N] or NULL, sums [n][8].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is
+ * not a holding session: that row's outputs are left as the caller filled them.  g counts the listed slots, not the slot ids.  The
+ * context is only read; a slot may be listed repeatedly.  SGO_ERR_ARG: the bounds of sgo_playout_dev, a slot outside the context, a
+ * NULL slot list, status, own or sums. */
+int sgo_session_playout(sgo_ctx *ctx, int n, const int32_t *slots, int per_row, uint32_t seed, int rules, int max_plies, int32_t *status,
+                        int32_t *own, int32_t *amaf, int64_t *sums, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

@@ -47,6 +47,7 @@ SYMBOLS = [
     "sgo_race_dev", "sgo_race", "sgo_session_race",
     "sgo_connect_dev", "sgo_connect", "sgo_session_connect",
     "sgo_superko_dev", "sgo_superko", "sgo_superko_mode",
+    "sgo_playout_dev", "sgo_playout", "sgo_session_playout",
 ]
 
 
@@ -225,6 +226,9 @@ def load():
     lib.sgo_superko_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     lib.sgo_superko.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
     lib.sgo_superko_mode.argtypes = [C.c_int]
+    lib.sgo_playout_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.sgo_playout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.sgo_session_playout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 5
     _lib = lib
     return lib
 

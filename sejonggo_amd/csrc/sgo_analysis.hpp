@@ -1,4 +1,4 @@
-// sgo_analysis.hpp -- what the ten position analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect) share on the host: the record
+// sgo_analysis.hpp -- what the position analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect, playout) share on the host: the record
 // launchers of their translation units, which sgo_session.hip runs over the context's root records, and the one body of their
 // host entries sgo_X.  Host code only; every kernel stays in its own file.
 #pragma once
@@ -33,6 +33,9 @@ int launch_connect(int S, int n, const uint32_t *d_records, int n_records, const
 // superko reads a record and the records of its game before it (d_first), through the work array d_keys [n_records]: two launches
 int launch_superko(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, const int32_t *d_first, int rule,
                    uint64_t *d_keys, uint32_t *d_sets, int16_t *d_back, int32_t *d_counts, hipStream_t st);
+// light playouts: per row per_row random games played to their end; d_amaf may be nullptr; two launches (zero, play)
+int launch_playout(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int per_row, uint32_t seed, int rules,
+                   int max_plies, int32_t *d_own, int32_t *d_amaf, int64_t *d_sums, hipStream_t st);
 
 // The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
 // (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip) and of the solve parameters (csrc/sgo_solve.hip)
@@ -42,6 +45,7 @@ bool influence_params_ok(int dilate, int erode_moyo, int erode_terr);
 bool solve_params_ok(int rules, int max_region, int max_nodes, int max_targets);
 bool race_params_ok(int rules, int max_libs, int max_region, int max_nodes, int max_pairs);
 bool connect_params_ok(int rules, int cut_libs, int max_region, int max_nodes, int max_pairs);
+bool playout_params_ok(int S, int n, int per_row, int rules, int max_plies);   // csrc/sgo_playout.hip
 
 // One array of a host entry's device block.  `up` (or nullptr) is copied in before the launch, `down` (or nullptr) is filled
 // from it afterwards; an array with neither is only room.

@@ -23,6 +23,7 @@
 // on the order of the list, which the survivors' appends (one atomicAdd each) leave unspecified.
 #include <string.h>
 
+#include "sgo_draw.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_rows.hpp"
 
@@ -41,25 +42,12 @@ struct Roll {          // passed by value to the kernels
     int32_t *slots, *sroot;       // sgo_rollout_start_sessions: slot ids in [max_src]; status and root record index out [2][max_src]
 };
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t draw32(uint32_t seed, uint32_t g, uint32_t ply) {
-    return mix32(mix32(seed ^ (g * 0x9E3779B9u)) + ply * 0x85EBCA6Bu);
-}
 // floor(clamp(p) * 2^20) + 1: the scaling is exact in float32, the conversion truncates a non-negative value
 __device__ __forceinline__ uint32_t weight_of(float p) {
     if (!(p > 0.f)) return 1u;                 // NaN, negatives, +-0
     if (p >= 1.f) return (1u << 20) + 1u;      // 1, above, +inf
     return (uint32_t)(p * 1048576.f) + 1u;
 }
-__device__ __forceinline__ int half_sum(int v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
-
 template <int S>
 __global__ __launch_bounds__(256) void k_rollout_start(Roll d, int n_src, const uint32_t *srcrec, const int32_t *index, int per_src) {
     using G = Geo<S>;
@@ -150,9 +138,8 @@ __global__ __launch_bounds__(64) void k_rollout_step(Roll d, int n, int cur, con
     const int ply1 = ply + 1, passes1 = (a == G::N) ? passes + 1 : 0;
     const bool ended = passes1 >= 2 || ply1 >= max_plies;
     if (__any(ended)) {                                             // uniform over the wave: the fills below vote over it
-        const uint32_t emp = ~(nb | nw) & bd.M;
-        const uint32_t rb = bd.flood(bd.nbr4(nb) & emp, emp), rw = bd.flood(bd.nbr4(nw) & emp, emp);
-        const uint32_t bo = nb | (rb & ~rw), wo = nw | (rw & ~rb);  // play.py:244-292: reached by one colour only
+        uint32_t bo, wo;
+        area_owners<S>(bd, nb, nw, bo, wo);                         // play.py:244-292: reached by one colour only
         const int bp = half_sum(__popc(bo)), wp = half_sum(__popc(wo));
         if (ended && valid) {
             const int s = rid / per_src;

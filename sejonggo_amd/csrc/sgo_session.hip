@@ -4,7 +4,7 @@
 // sgo_life.hip), of sgo_session_shapes ("shape search"; sgo_shapes.hip), of sgo_session_moves ("move outcomes"; sgo_moves.hip), of
 // sgo_session_influence ("influence"; sgo_influence.hip), of sgo_session_secure ("securing moves"; sgo_secure.hip), of
 // sgo_session_solve ("life and death"; sgo_solve.hip) and of sgo_session_race ("capturing races"; sgo_race.hip) and of sgo_session_connect
-// ("connections"; sgo_connect.hip).
+// ("connections"; sgo_connect.hip) and of sgo_session_playout ("light playouts"; sgo_playout.hip).
 // Those nine (session_rows below, over the launchers of sgo_analysis.hpp) and sgo_rollout_start_sessions (sgo_rollout.hip) find
 // the root records of the listed slots with launch_session_roots below and run their ordinary record kernels over the context's
 // blocks.  sgo_session_open is a restart and lives beside sgo_start_games in sgo_engine.hip; the
@@ -108,7 +108,7 @@ struct RowCol {
     std::function<size_t(int)> stored;
 };
 
-// The body of the ten session analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect).  The session buffer is laid out as
+// The body of the eleven session analyses (keys, tactics, life, shapes, moves, influence, secure, solve, race, connect, playout).  The session buffer is laid out as
 //     slots | input | record index | status | columns
 // the slots (and `input`, where there is one: a shape table, the dead sets) go up, k_session_roots names the root records,
 // launch(d_index, d_input, d_cols) runs the ordinary record launcher over the context's blocks, and everything behind the index
@@ -489,6 +489,24 @@ int sgo_session_connect(sgo_ctx *x, int n, const int32_t *slots, const int32_t *
                               (d_in && region) ? reinterpret_cast<const uint32_t *>(d_in + ab) : nullptr, rules, cut_libs, max_region, max_nodes,
                               max_pairs, reinterpret_cast<int32_t *>(d[0]), reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<uint32_t *>(d[2]),
                               reinterpret_cast<int16_t *>(d[4]), reinterpret_cast<int32_t *>(d[3]), st);
+    });
+}
+
+int sgo_session_playout(sgo_ctx *x, int n, const int32_t *slots, int per_row, uint32_t seed, int rules, int max_plies, int32_t *status,
+                        int32_t *own, int32_t *amaf, int64_t *sums, void *stream) {
+    if (!x || !playout_params_ok(x->c.S, n, per_row, rules, max_plies) || (n && (!slots || !status || !own || !sums))) {
+        set_error("sgo_session_playout: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    const Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t tb = sizeof(int32_t) * 2 * c.S * c.S;
+    // without amaf the third column has no bytes and the kernel gets no table
+    const RowCol cols[] = {{sums, sizeof(int64_t) * 8, 8}, {own, tb, 4}, {amaf ? amaf : own, amaf ? tb : 0, 4}};
+    return session_rows(x, "sgo_session_playout", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_playout(c.S, n, c.pos, ctx_records(c), d_index, per_row, seed, rules, max_plies, reinterpret_cast<int32_t *>(d[1]),
+                              amaf ? reinterpret_cast<int32_t *>(d[2]) : nullptr, reinterpret_cast<int64_t *>(d[0]), st);
     });
 }
 

@@ -872,6 +872,18 @@ class SessionEngine(SelfPlayEngine):
                                     out.n_pairs, out.rows, out.regions, out.groups, out.group_counts)
         return out
 
+    def playouts(self, slots, per_row=256, seed=0, rules=1, max_plies=0):
+        """Light playouts from the root positions of the listed holding sessions (sgo_session_playout; include/sgo.h "light
+        playouts"): a playout.Playouts with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays
+        zero).  No net is asked; an ESTIMATE of how the position ends, not a proof.  Boards and trees are only read."""
+        from .playout import Playouts, check_args
+        check_args(self.S, per_row, rules, max_plies)
+        n, N = len(slots), self.S * self.S
+        out = Playouts(self.S, np.zeros((n, 2, N), np.int32), np.zeros((n, 2, N), np.int32), np.zeros((n, 8), np.int64))
+        out.status = self._analysis(self.lib.sgo_session_playout, slots, (int(per_row), int(seed) & 0xFFFFFFFF, int(rules), int(max_plies)),
+                                    out.own, out.amaf, out.sums)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

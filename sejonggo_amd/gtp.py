@@ -315,6 +315,21 @@ class DeviceSejongGoEngine(object):
         sets, back, counts = rec.superko([n], [0], rule, n + 1)
         return Superko(self.size, sets.cpu().numpy().view(np.uint32), back.cpu().numpy(), counts.cpu().numpy())
 
+    def playouts(self, per_row=None, rules=1, seed=0):
+        """How the game ends from here by light playouts (engine.SessionEngine.playouts; include/sgo.h "light playouts"): the
+        position played out per_row times (None: playout.DEFAULT_PER_ROW) with uniformly random moves that spare the mover's eyes
+        -- no net is asked.  Returns (a playout.Playouts with one row, the stones int8 [S, S], +1 black); board, tree and move
+        number stay.  The answer is kept until the position changes.  An ESTIMATE, not a proof."""
+        from .playout import DEFAULT_PER_ROW
+        from .rollout import real_board
+        key = (tuple(self.moves), per_row, rules, seed)
+        if getattr(self, "_playout_cache", (None,))[0] != key:
+            board = self.board
+            v = self._held(self.engine.playouts([self.slot], per_row=int(per_row or DEFAULT_PER_ROW), seed=seed, rules=rules))
+            v.white_to_play = np.array([int(board[0, 0, 0, -1]) == -1])
+            self._playout_cache = (key, v, real_board(board))
+        return self._playout_cache[1], self._playout_cache[2]
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -337,12 +352,19 @@ class GTPFailure(Exception):
 
 
 class GTPEngine(object):
-    def __init__(self, engine=None, book=None, book_min=1, superko=None):
-        """book: a records.Book (or the path of its .npz) genmove answers from while it holds a legal move played at least
+    def __init__(self, engine=None, book=None, book_min=1, superko=None, score="rollouts"):
+        """score: "rollouts" (default: final_score, final_status_list and sgo-ownership stand on policy rollouts, as ever) or
+        "playouts" (they stand on light playouts, which ask no net); device engine only.
+        book: a records.Book (or the path of its .npz) genmove answers from while it holds a legal move played at least
         book_min times; it needs the device engine (position keys come from the session slot).
         superko: None, or "positional" / "situational" (0 / 1): `play` refuses a move that repeats an earlier position of the game
         and genmove never makes one; it needs the device engine too (the move list is replayed on the device)."""
         self._komi = 0
+        if score not in ("rollouts", "playouts"):
+            raise ValueError("score is 'rollouts' or 'playouts'")
+        if score == "playouts" and (engine is None or not hasattr(engine, "playouts")):
+            raise ValueError("--score playouts needs the device engine (gtp --device)")
+        self.score = score
         self.superko_rule = None
         if superko is not None:
             from .superko import rule_of
@@ -374,7 +396,8 @@ class GTPEngine(object):
         return "\n".join(["name", "version", "protocol_version", "list_commands", "known_command", "boardsize", "komi", "play",
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
-                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "sgo-superko", "quit"])
+                          "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "sgo-superko", "sgo-playouts",
+                          "sgo-playout-moves", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -532,17 +555,29 @@ class GTPEngine(object):
                                                                       float(r["P"][0][a]), pv))
         return "\n".join(lines)
 
+    def _score_source(self):
+        """the callable behind final_score, final_status_list and sgo-ownership: () -> (a row shaped like rollout.result_row, the
+        stones); policy rollouts unless the engine was started with score = playouts"""
+        if self.score == "playouts":
+            playouts = self._engine_method("playouts")
+
+            def source():
+                v, stones = playouts()
+                return v.row(0), stones
+            return source
+        return self._engine_method("rollouts")
+
     def final_score(self):
         """GTP final_score from policy rollouts: the points two thirds of the rollouts give one colour, minus komi."""
         from .rollout import final_score
-        row, _ = self._engine_method("rollouts")()
+        row, _ = self._score_source()()
         return final_score(row, float(self._komi))
 
     def final_status_list(self, status=""):
         """GTP final_status_list alive|dead|seki: the stones whose point the rollouts give to their own colour / to the
         opponent / to neither."""
         from .rollout import stone_status
-        rollouts = self._engine_method("rollouts")
+        rollouts = self._score_source()
         if status not in ("alive", "dead", "seki"):
             raise GTPFailure("syntax error")
         row, stones = rollouts()
@@ -551,7 +586,7 @@ class GTPEngine(object):
     def sgo_ownership(self):
         """Private extension `sgo-ownership`: S lines of S signed per-mille values from the top row down, black positive:
         (black_own - white_own) * 1000 / rollouts, rounded towards zero."""
-        row, _ = self._engine_method("rollouts")()
+        row, _ = self._score_source()()
         R = max(1, int(row["rollouts"]))
         d = (np.asarray(row["black_own"], dtype=np.int64) - np.asarray(row["white_own"], dtype=np.int64)).reshape(self.size, self.size)
         return "\n".join(" ".join("%d" % (int(np.sign(v)) * (1000 * abs(int(v)) // R)) for v in line) for line in d)
@@ -614,6 +649,41 @@ class GTPEngine(object):
         if len(words) > 1 or (words and words[0] not in ("positional", "situational")):
             raise GTPFailure("syntax error")
         return format_repeat(self._engine_method("superko")(words[0] if words else "positional"), 0, self._vertex)
+
+    def _playout_words(self, words, default):
+        """(the number, rules) of `[N] [inherited]`"""
+        n, rules = default, 1
+        for w in words:
+            if w == "inherited" and rules == 1:
+                rules = 0
+            elif w.isdigit() and n == default and int(w) >= 1:
+                n = int(w)
+            else:
+                raise GTPFailure("syntax error")
+        return n, rules
+
+    def sgo_playouts(self, *words):
+        """Private extension `sgo-playouts [N] [inherited]`: N light playouts from the position (include/sgo.h "light playouts";
+        default playout.DEFAULT_PER_ROW) -- one line `score M +- SD  capped C%  playouts N` (black - white, komi-free), then S lines
+        of S signed per-mille values from the top row down, black positive: who holds the point at the end.  Uniformly random moves
+        that spare the mover's eyes; no net is asked.  `inherited` plays under the inherited legal set, where a ko can never be
+        connected and the ply cap ends what does not end.  An ESTIMATE, not a proof."""
+        from .playout import DEFAULT_PER_ROW, MAX_PER_ROW, format_summary
+        n, rules = self._playout_words(words, DEFAULT_PER_ROW)
+        if n > MAX_PER_ROW:
+            raise GTPFailure("at most %d playouts" % MAX_PER_ROW)
+        v, _ = self._engine_method("playouts")(n, rules)
+        return format_summary(v, 0) + "\n" + v.format_board(0)
+
+    def sgo_playout_moves(self, *words):
+        """Private extension `sgo-playout-moves [K] [inherited]`: the K (default 10) best first moves of the side to move by the
+        all-moves-as-first table of the light playouts -- one line `V count mean` per move: in how many playouts the side to move
+        was the first to play V, and the mean final score of those from its view.  Moves seen in fewer than 1 % of the playouts are
+        left out.  An ESTIMATE, not a proof."""
+        from .playout import format_moves
+        k, rules = self._playout_words(words, 10)
+        v, _ = self._engine_method("playouts")(None, rules)
+        return format_moves(v, 0, k, self._vertex, min_count=max(1, v.count(0, "playouts") // 100))
 
     def sgo_secure(self, *words):
         """Private extension `sgo-secure [opponent] [min K]`: what one more stone makes pass-alive (include/sgo.h "securing moves")
@@ -792,7 +862,8 @@ class GTPEngine(object):
     ALIASES = {"sgo-analyze": "sgo_analyze", "sgo-ownership": "sgo_ownership", "sgo-book": "sgo_book", "sgo-ladders": "sgo_ladders",
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
                "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race",
-               "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups", "sgo-superko": "sgo_superko"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups", "sgo-superko": "sgo_superko",
+               "sgo-playouts": "sgo_playouts", "sgo-playout-moves": "sgo_playout_moves"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")
@@ -809,7 +880,7 @@ class GTPEngine(object):
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 
-def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, superko=None):
+def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, superko=None, score="rollouts"):
     """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine).
     book (`--book FILE [--book-min N]`, device only): genmove plays from the opening book records.py wrote while it has a move.
     superko (`--superko positional|situational`, device only): `play` refuses and genmove avoids a move that repeats an earlier
@@ -820,8 +891,11 @@ def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, sup
     if superko is not None and not device:
         sys.stderr.write("--superko needs the device engine: run with --device\n")
         return 2
+    if score != "rollouts" and not device:
+        sys.stderr.write("--score playouts needs the device engine: run with --device\n")
+        return 2
     engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None, book=book,
-                       book_min=book_min, superko=superko)
+                       book_min=book_min, superko=superko, score=score)
     for line in inp:
         for cmd in line.split("\n"):
             res = engine.parse_command(cmd)
@@ -841,8 +915,11 @@ def _cli(argv):
     ap.add_argument("--book-min", type=int, default=1, help="play a book move only when it was played at least N times (default 1)")
     ap.add_argument("--superko", default=None, choices=("positional", "situational"),
                     help="refuse and avoid moves that repeat an earlier position of the game; needs --device")
+    ap.add_argument("--score", default="rollouts", choices=("rollouts", "playouts"),
+                    help="what final_score, final_status_list and sgo-ownership stand on: policy rollouts (default) or light playouts, "
+                         "which ask no net; needs --device")
     a = ap.parse_args(argv)
-    return main(device=a.device, book=a.book, book_min=a.book_min, superko=a.superko)
+    return main(device=a.device, book=a.book, book_min=a.book_min, superko=a.superko, score=a.score)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ packed record per ply, written out as supervised samples, and a net scored on th
     python -m sejonggo_amd.records PATH [--size S] [--samples OUT] [--score] [--net best|hash|uniform|table]
                                         [--symmetry identity|random1|0..7] [--bucket N] [--json FILE] [--compat-unknown-result]
                                         [--book OUT.npz] [--book-plies N] [--duplicates] [--find SHAPE.txt] [--moves]
-                                        [--influence] [--superko [positional|situational]]
+                                        [--influence] [--superko [positional|situational]] [--playouts R]
 
 PATH is one .sgf file or a directory of them (default conf['KGS_DATA_DIR']).  The counterpart of the reference's
 kgs_game_parser/KGSSelfPlayWorker.py: every record is replayed with make_play's rules, and every B / W move gives the board before
@@ -504,6 +504,19 @@ class DeviceRecords(object):
         used = self.cap if n_records is None else max(0, min(self.cap, int(n_records)))
         return superko_dev(self.S, self.records, index, first, rule, self.lib, n_records=used)
 
+    def playouts(self, index, per_row=16, seed=0, rules=1, max_plies=0, amaf=True):
+        """(own int32 [n, 2, N], amaf int32 [n, 2, N] or None, sums int64 [n, 8]) device tensors of the listed records: per_row light
+        playouts each (sgo_playout_dev, two launches; include/sgo.h "light playouts").  Playout j of row i draws with the id
+        i * per_row + j.  An index outside the object gives the zero row."""
+        from .playout import playout_dev
+        torch = self.torch
+        index = self._index(index)
+        n = int(index.shape[0])
+        if n == 0:
+            z = torch.zeros((0, 2, self.N), dtype=torch.int32, device=self.device)
+            return z, (z.clone() if amaf else None), torch.zeros((0, 8), dtype=torch.int64, device=self.device)
+        return playout_dev(self.S, self.records, index, n, per_row, seed, rules, max_plies, self.lib, amaf=amaf)
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -758,6 +771,20 @@ class RecordSet(object):
         rule = rule_of(rule)
         return self._per_record("superko", lambda index, first: self.backend.superko(index, first, rule, len(index)),
                                 lambda sets, back, counts: Superko(self.S, _host(sets, np.uint32), _host(back, np.int16), _host(counts)), games=True)
+
+    def playouts(self, per_row=16, seed=0, rules=1, max_plies=0, stones=False):
+        """Generator of Chunks as `replay` gives them, each with `playouts`, a playout.Playouts with one row per RECORD of the chunk
+        (one backend call per chunk), rows as in `life`: per_row light playouts from every position -- ownership, score
+        distribution and the all-moves-as-first table of the side to move.  An ESTIMATE, not a proof.  The draws of a row depend
+        on its place in the chunk.  Records that were not written give the zero row.  ch.to_play int8 [records] is the side to move
+        of each record (+1 black, -1 white; 0 for a record that was not written)."""
+        from .playout import Playouts, check_args
+        check_args(self.S, per_row, rules, max_plies)
+        for ch in self._per_record("playouts", lambda index: self.backend.playouts(index, per_row, seed, rules, max_plies),
+                                   lambda own, amaf, sums: Playouts(self.S, _host(own), _host(amaf), _host(sums, np.int64)), stones):
+            ch.to_play = _host(self.backend.to_play(self._record_index(ch)), np.int8)
+            ch.playouts.white_to_play = ch.to_play < 0
+            yield ch
 
     # ------------------------------------------------------------------ move outcomes
     def moves(self, side=0):
@@ -1124,6 +1151,28 @@ def superko_report(record_set, rule=0, width=20):
             "positions_with_extra": int(sum(1 for c in extra if c > 0)), "max_back": max_back}
 
 
+def playout_report(record_set, per_row=16, width=20, seed=0):
+    """What `--playouts R` prints, from one RecordSet.playouts pass (rules 1, the default cap): {"per_row", "games": [{"name", "plies",
+    "lead", "sd", "capped", "result"}] with the playout score (black - white, komi-free) of each game's LAST position beside the
+    recorded result, "buckets": playout.bucket_table over every written record (ply = the number of entries before it)}.  An
+    estimate from uniformly random playouts, not a verdict."""
+    from .playout import bucket_table
+    games, ply, mean, sd, capped = [], [], [], [], []
+    for ch in record_set.playouts(per_row=per_row, seed=seed):
+        v = ch.playouts
+        for _, g, base, off, _, played in ch.walk():
+            last = base + played
+            w = record_set.records[g].winner
+            games.append({"name": record_set.records[g].name, "plies": played, "lead": v.score_mean(last), "sd": v.score_sd(last),
+                          "capped": v.capped_share(last), "result": "B" if w == 1 else "W" if w == -1 else "?"})
+            for r in range(base, last + 1):
+                ply.append(r - base)
+                mean.append(v.score_mean(r))
+                sd.append(v.score_sd(r))
+                capped.append(v.capped_share(r))
+    return {"per_row": int(per_row), "games": games, "buckets": bucket_table(ply, mean, sd, capped, width) if ply else []}
+
+
 def format_bucket(d, label):
     def pct(a, b):
         return "%5.1f%%" % (100.0 * a / b) if b else "    - "
@@ -1192,6 +1241,10 @@ def main(argv=None, out=sys.stdout):
                          "seen before (passes apart) and every played move that the ko approximation let through although it repeats; "
                          "the ko recaptures played through; per 20-move bucket the share of positions where superko forbids a move "
                          "the inherited rule allows")
+    ap.add_argument("--playouts", type=int, default=None, metavar="R",
+                    help="R light playouts from every position (uniformly random moves that spare the mover's eyes, no net): per "
+                         "20-move bucket the mean |score|, its standard deviation and the share of playouts the ply cap ended; per game "
+                         "the estimate at the last position beside the recorded result.  An estimate, not a verdict")
     a = ap.parse_args(argv)
     size = a.size or conf['SIZE']
     symmetry = a.symmetry if a.symmetry in ("identity", "random1") else int(a.symmetry)
@@ -1303,6 +1356,11 @@ def main(argv=None, out=sys.stdout):
             doc["superko"] = superko_report(rs, a.superko, a.bucket)
             out.write("superko (%s)\n" % doc["superko"]["rule"])
             out.write(format_report(doc["superko"]["games"], doc["superko"]["buckets"], lambda p: vertex(p, size)) + "\n")
+        if a.playouts:
+            from .playout import format_report as format_playouts
+            doc["playouts"] = playout_report(rs, a.playouts, a.bucket)
+            out.write("playouts (%d per position; an estimate)\n" % a.playouts)
+            out.write(format_playouts(doc["playouts"]["games"], doc["playouts"]["buckets"]) + "\n")
         doc["refused"] = [list(t) for t in rs.refused]
         for name, status, at in rs.refused:
             out.write("record %s cut short at entry %d (status %d)\n" % (name, at, status))

@@ -5,6 +5,7 @@ all positions) and read back in one launch (report).
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
                                            [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race] [--connect] [--superko [RULE]]
+                                           [--playouts R]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -33,7 +34,10 @@ net: the lines then hold the move and the two figures only.  --superko [position
 position would give with every earlier position of the game (records.RecordSet.superko; include/sgo.h "superko") and flags a played
 move `repeats K` when it recreated the position K records before the one it was played from (1: a ko recapture), and a position
 `superko-forbidden V ...` with the moves superko forbids although the inherited ko rule allows them; like --influence it loads no
-net when nothing else asks for one.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+net when nothing else asks for one.  --playouts R puts the mean score of R light playouts (records.RecordSet.playouts; include/sgo.h
+"light playouts": uniformly random moves that spare the mover's eyes, no net; black - white, komi-free) in front of every move with
+its change across the move in the mover's favour, and a last line names the three largest drops: an estimate, not a verdict, and
+again no net is loaded for it.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import contextlib
 import json
@@ -410,6 +414,38 @@ def add_influence(rows, game, record_set=None, komi=None):
     return rows
 
 
+def playout_rows(game, record_set, per_row, seed=0):
+    """{move number: (lead, sd, change, capped share)} of the B / W moves of `game` from one RecordSet.playouts pass over a set that
+    holds the game as its only record: the mean playout score (black - white, komi-free) of the position in front of the move, its
+    standard deviation, and the change of the mean across the move in the mover's favour.  An estimate from uniformly random
+    playouts (include/sgo.h "light playouts"), not a verdict."""
+    out = {}
+    for ch in record_set.playouts(per_row=per_row, seed=seed):
+        v = ch.playouts
+        for m, _, r, action, colour in played_moves(game, ch):
+            out[m] = (v.score_mean(r), v.score_sd(r), (v.score_mean(r + 1) - v.score_mean(r)) * (1 if colour > 0 else -1), v.capped_share(r))
+    return out
+
+
+def add_playouts(rows, game, per_row, record_set=None, seed=0):
+    """Adds `playout_lead`, `playout_sd`, `playout_change` and `playout_capped` to every row of a review.  record_set None: a device
+    RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = playout_rows(game, rs, per_row, seed)
+    for row in rows:
+        lead, sd, change, capped = found.get(row["move_number"], (None, None, None, None))
+        row["playout_lead"], row["playout_sd"], row["playout_change"], row["playout_capped"] = lead, sd, change, capped
+    return rows
+
+
+def playout_summary(rows, top=3):
+    """`playouts (estimate): largest drops M C V (-d) ...` of the rows add_playouts filled: the moves after which the mean playout
+    score fell most for the mover"""
+    drops = sorted((row["playout_change"], row["move_number"], row["colour"], row["played"]) for row in rows
+                   if row.get("playout_change") is not None and row["playout_change"] < 0)[:top]
+    return "playouts (estimate): largest drops " + (" ".join("%d %s %s (%+.1f)" % (m, c, v, d) for d, m, c, v in drops) or "-")
+
+
 def influence_summary(rows, top=3):
     """`influence: highest gain M (+g) ...; lowest gain M (-g) ...` of the rows add_influence filled"""
     from .influence import review_summary
@@ -430,6 +466,8 @@ def format_row(row):
     if row.get("estimate") is not None:
         from .influence import score_text
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
+    if row.get("playout_lead") is not None:
+        text += "  | playouts %+.1f +- %.1f change %+.1f" % (row["playout_lead"], row["playout_sd"], row["playout_change"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
         list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or []) + \
         list(row.get("race_flags") or []) + list(row.get("connect_flags") or []) + list(row.get("superko_flags") or [])
@@ -516,13 +554,17 @@ def main(argv=None, out=sys.stdout):
                     help="flag every played move that recreated an earlier position of the game (repeats K: K records back from the "
                          "position it was played in) and every position in which superko forbids moves the inherited ko rule allows "
                          "(superko-forbidden V ...).  Like --influence it loads no net when nothing else asks for one")
+    ap.add_argument("--playouts", type=int, default=None, metavar="R",
+                    help="put the mean score of R light playouts (uniformly random moves that spare the mover's eyes, no net; black - "
+                         "white, komi-free) in front of every move, with its change across the move in the mover's favour, and name the "
+                         "three largest drops.  An estimate, not a verdict.  Like --influence it loads no net when nothing else asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect or a.superko) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect or a.superko or a.playouts) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -562,10 +604,14 @@ def main(argv=None, out=sys.stdout):
         add_superko(rows, game, rule=a.superko)
     if a.influence:
         add_influence(rows, game)
+    if a.playouts:
+        add_playouts(rows, game, a.playouts)
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.influence:
         out.write(influence_summary(rows) + "\n")
+    if a.playouts:
+        out.write(playout_summary(rows) + "\n")
     if a.json:
         with open(a.json, "w") as f:
             json.dump(document(game, rows, sims, energy, getattr(net, "name", a.net) if searched else None, a.rollouts), f, indent=1,
