@@ -55,7 +55,8 @@ extern "C" {
  *   outcomes" section (sgo_moves*, sgo_session_moves), the "influence" section (sgo_influence*, sgo_session_influence), the "securing moves"
  *   section (sgo_secure*, sgo_session_secure), the "life and death" section (sgo_solve*, sgo_session_solve), the "capturing races"
  *   section (sgo_race*, sgo_session_race), the "connections" section (sgo_connect*, sgo_session_connect), the "superko" section
- *   (sgo_superko*; no session form), the "light playouts" section (sgo_playout*, sgo_session_playout). */
+ *   (sgo_superko*; no session form), the "light playouts" section (sgo_playout*, sgo_session_playout),
+ *   the "playout tree search" section (sgo_uct*, sgo_session_uct). */
 #define SGO_ABI_VERSION 4
 
 const char *sgo_last_error(void);
@@ -1315,6 +1316,86 @@ int sgo_playout(int S, int n_records, const uint32_t *records, int n, const int3
  * NULL slot list, status, own or sums. */
 int sgo_session_playout(sgo_ctx *ctx, int n, const int32_t *slots, int per_row, uint32_t seed, int rules, int max_plies, int32_t *status,
                         int32_t *own, int32_t *amaf, int64_t *sums, void *stream);
+
+/* ---- playout tree search: which move?  Monte-Carlo tree search with RAVE on the light playouts, no net ------------------------------- */
+/* Per listed record `trees` independent tree searches of `sims` simulations each, every search run from first to last inside one
+ * kernel (csrc/sgo_uct.hip): selection by a RAVE-blended value, expansion, a light playout below the tree, back-propagation.  What
+ * comes out is the root's move table summed over the trees and the move it favours.  An ESTIMATE, not a proof; no net, no host
+ * loop.  Everything is integer.  N = S * S; the pass is the move N.
+ * ROWS, TREES, SIMULATIONS.  Rows, records, d_index, `rules` and the START of a game (stones, side to move, `prev` of the first ply)
+ * are exactly those of the "light playouts" section.  Per row `trees` searches run (root parallelisation); tree t of row i has the id
+ * g = i * trees + t.  A tree runs its simulations s = 0 .. sims - 1 one after another; simulation s of tree g draws with the playout id
+ * gs = g * sims + s as uint32, that is draw(seed, gs, ply) of the "policy rollouts" section with ply counted from the root.  A tree
+ * never sees another tree, and what a row reports is the integer sum over its trees: results do not depend on scheduling.
+ * CANDIDATES.  At every ply, in the tree and below it, cand = ALLOWED minus EYE of the "light playouts" section for the given `rules`;
+ * cand empty means the only move is the pass.  A simulation ENDS at two passes in a row or at ply == max_plies; max_plies <= 0 means
+ * 3 * N, a value above 4 * N is refused, and a simulation that ends with fewer than two passes in a row is CAPPED, as there.
+ * NODES.  A node is a position reached by a move sequence from the root (no transpositions).  When it is created it takes cand of its
+ * position as its child set ({N} when cand is empty) and keeps per child a the counters n[a], w[a], rn[a], rw[a], all zero, and a link
+ * to the child's node, none at first.  w counts 2 per win and 1 per draw from the view of the node's mover.  The root is node 0 and
+ * is created before simulation 0.  A position in which the game has ended gets no node.
+ * SELECTION at a node with mover X, ply `ply`, with P = prior and E = rave_equiv; all values unsigned, all divisions floor divisions:
+ *   rn' = rn + P, rw' = rw + P
+ *   rq = (E != 0 and rn' != 0) ? (rw' << 16) / rn' : 65536
+ *   q = n ? (w << 16) / n : rq
+ *   beta = n == 0 ? 65536 : (E != 0 and rn' != 0) ? (rn' << 16) / (rn' + n + rn' * n / E) : 0
+ *   v = (beta * rq + (65536 - beta) * q) >> 16                       (the products in 64 bits; everything else fits 32)
+ * The child chosen has the largest v; among equals the largest h(a) = mix(draw(seed, gs, ply) + a) (mod 2^32); among equals the lowest
+ * a.  There is no exploration term: the prior and the hash tie-break do that work.
+ * DESCENT.  The chosen child is played with one ply of sgo_make_play.  If the child has a node the simulation goes on there.
+ * Otherwise the tree part ends with D = the number of tree plies taken, and a node for the new position is created and linked when
+ * all of these hold: the child's n before this simulation was at least expand_at; D < SGO_UCT_MAX_DEPTH; the game has not ended; the
+ * tree has fewer than max_nodes nodes.  (When only the last fails the tree was REFUSED a node.)  From ply D on the moves are the
+ * playouts' uniform picks with draw(seed, gs, ply).
+ * RESULT.  Scoring is that of the "policy rollouts" section; diff = black - white.  result2 = 2, 1 or 0 for 2 * diff greater than,
+ * equal to or less than komi2, seen from black; from white's view it is 2 - result2.
+ * During the plies >= D two sets are kept: a point played at such a ply enters Fb (black moved) or Fw (white moved) unless it is
+ * already in one of them.
+ * BACK-PROPAGATION walks the path from d = D - 1 down to 0.  With c the mover of ply d, a_d its move, its node, and r = result2 from
+ * c's view:  (1) if a_d is a point it enters F_c and leaves the other set;  (2) n[a_d] += 1, w[a_d] += r;  (3) for every a in F_c
+ * that is a child of the node: rn[a] += 1, rw[a] += r.
+ * OUTPUTS per row, written and not added to:
+ *   visits int32 [N + 1]      the root's n, summed over the trees; index N is the pass
+ *   wins2  int32 [N + 1]      the root's w, summed over the trees (seen from the side to move)
+ *   rave   int32 [2][N + 1]   the root's rn and rw, summed over the trees; may be NULL
+ *   own    int32 [2][N]       the number of simulations that end with the point black's, and with it white's; may be NULL
+ *   sums   int64 [8]          the eight sums of the "light playouts" section over all simulations (komi-free; plies from the root)
+ *   info   int32 [4]          {nodes created, roots included; the largest D; the trees that were refused a node at least once; best}
+ *   trace  int32 [n * trees][sims], indexed [g][s]; may be NULL: a_0 | D << 9 | result2 << 16 | capped << 18 of every simulation,
+ *                             a_0 the move of ply 0
+ * best = the child of the largest visits; among equals the larger wins2; among equals the lower point.  A row whose record index is
+ * outside [0, n_records) gets all-zero outputs (its trace words included) and best = -1.
+ *
+ * sgo_uct_dev: THREE launches on `stream` (the outputs are zeroed, the trees add into them, best is written), no allocation, no
+ * synchronisation, capturable; n == 0 is a no-op; rows >= n are not written.  d_work is device memory of at least
+ * sgo_uct_workspace bytes (S, n, trees, max_nodes), 4-byte aligned, whose content means nothing before or after the call.
+ * SGO_ERR_ARG: an unsupported S, n < 0, n_records < 0, trees outside [1, SGO_UCT_MAX_TREES], sims outside [1, SGO_UCT_MAX_SIMS],
+ * n * trees * sims beyond int32, rules outside {0, 1}, max_plies above 4 * N, |komi2| above 4 * N, expand_at outside [0, sims],
+ * rave_equiv outside [0, 1 << 20], prior outside [0, 1024], max_nodes outside [1, sims + 1], a NULL d_records, d_visits, d_wins2,
+ * d_sums or d_info, and for n > 0 a NULL d_work or a work_bytes below the workspace size.  Nothing is written then.
+ * sgo_uct_workspace returns the bytes, or SGO_ERR_ARG (negative) for an unsupported S, n < 0, trees or max_nodes out of range. */
+#define SGO_UCT_MAX_TREES 4096
+#define SGO_UCT_MAX_SIMS 4096
+#define SGO_UCT_MAX_DEPTH 64
+int64_t sgo_uct_workspace(int S, int n, int trees, int max_nodes);
+int sgo_uct_dev(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int trees, int sims, uint32_t seed, int rules,
+                int max_plies, int komi2, int expand_at, int rave_equiv, int prior, int max_nodes, int32_t *d_visits, int32_t *d_wins2,
+                int32_t *d_rave, int32_t *d_own, int64_t *d_sums, int32_t *d_info, int32_t *d_trace, void *d_work, int64_t work_bytes,
+                void *stream);
+/* The same for HOST buffers: records [n_records][sgo_packed_words(S)], index [n] or NULL; rave, own and trace or NULL (copy in,
+ * allocate the workspace, run, copy back). */
+int sgo_uct(int S, int n_records, const uint32_t *records, int n, const int32_t *index, int trees, int sims, uint32_t seed, int rules, int max_plies,
+            int komi2, int expand_at, int rave_equiv, int prior, int max_nodes, int32_t *visits, int32_t *wins2, int32_t *rave, int32_t *own,
+            int64_t *sums, int32_t *info, int32_t *trace);
+/* The root positions of the listed HOLDING session slots of `ctx`, read in place; waits for `stream`; allocates and frees its
+ * workspace for the call.  HOST arrays: status [n], visits [n][N + 1], wins2 [n][N + 1], rave [n][2][N + 1] or NULL, own [n][2][N] or
+ * NULL, sums [n][8], info [n][4].  status[i] = SGO_OK, or SGO_ERR_STATE for a slot that is not a holding session: that row's outputs
+ * are left as the caller filled them.  g counts the listed slots, not the slot ids.  The context is only read; a slot may be listed
+ * repeatedly.  SGO_ERR_ARG: the bounds of sgo_uct_dev, a slot outside the context, a NULL slot list, status, visits, wins2, sums or
+ * info. */
+int sgo_session_uct(sgo_ctx *ctx, int n, const int32_t *slots, int trees, int sims, uint32_t seed, int rules, int max_plies, int komi2,
+                    int expand_at, int rave_equiv, int prior, int max_nodes, int32_t *status, int32_t *visits, int32_t *wins2, int32_t *rave,
+                    int32_t *own, int64_t *sums, int32_t *info, void *stream);
 
 /* Introspection for parity tests: root child table of a slot's current tree and the canonical
  * serialisation of the whole tree (32-byte records, see oracle/sgo_oracle.c ora_game_tree_serialize). */

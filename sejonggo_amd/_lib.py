@@ -48,6 +48,7 @@ SYMBOLS = [
     "sgo_connect_dev", "sgo_connect", "sgo_session_connect",
     "sgo_superko_dev", "sgo_superko", "sgo_superko_mode",
     "sgo_playout_dev", "sgo_playout", "sgo_session_playout",
+    "sgo_uct_workspace", "sgo_uct_dev", "sgo_uct", "sgo_session_uct",
 ]
 
 
@@ -229,6 +230,12 @@ def load():
     lib.sgo_playout_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.sgo_playout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.sgo_session_playout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.sgo_uct_workspace.argtypes = [C.c_int] * 4
+    lib.sgo_uct_workspace.restype = C.c_int64
+    uct = [C.c_int, C.c_int, C.c_uint32] + [C.c_int] * 7                 # trees, sims, seed, rules .. max_nodes
+    lib.sgo_uct_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + uct + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p]
+    lib.sgo_uct.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + uct + [C.c_void_p] * 7
+    lib.sgo_session_uct.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + uct + [C.c_void_p] * 8
     _lib = lib
     return lib
 

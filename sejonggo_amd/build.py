@@ -18,7 +18,7 @@ INCLUDE = os.path.join(HERE, "..", "include")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsgo_hip.so")
 MANIFEST = LIB + ".manifest.json"
-SOURCES = ["sgo_rules.hip", "sgo_engine.hip", "sgo_session.hip", "sgo_rollout.hip", "sgo_records.hip", "sgo_keys.hip", "sgo_tactics.hip", "sgo_life.hip", "sgo_shapes.hip", "sgo_moves.hip", "sgo_influence.hip", "sgo_secure.hip", "sgo_solve.hip", "sgo_race.hip", "sgo_connect.hip", "sgo_superko.hip", "sgo_playout.hip", "sgo_conv.hip", "sgo_net.hip"]
+SOURCES = ["sgo_rules.hip", "sgo_engine.hip", "sgo_session.hip", "sgo_rollout.hip", "sgo_records.hip", "sgo_keys.hip", "sgo_tactics.hip", "sgo_life.hip", "sgo_shapes.hip", "sgo_moves.hip", "sgo_influence.hip", "sgo_secure.hip", "sgo_solve.hip", "sgo_race.hip", "sgo_connect.hip", "sgo_superko.hip", "sgo_playout.hip", "sgo_uct.hip", "sgo_conv.hip", "sgo_net.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"] + os.environ.get("SGO_EXTRA_CFLAGS", "").split()
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]

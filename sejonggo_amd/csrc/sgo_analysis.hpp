@@ -36,6 +36,11 @@ int launch_superko(int S, int n, const uint32_t *d_records, int n_records, const
 // light playouts: per row per_row random games played to their end; d_amaf may be nullptr; two launches (zero, play)
 int launch_playout(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int per_row, uint32_t seed, int rules,
                    int max_plies, int32_t *d_own, int32_t *d_amaf, int64_t *d_sums, hipStream_t st);
+// playout tree search: per row `trees` searches of `sims` simulations; d_rave, d_own, d_trace may be nullptr; d_work holds
+// uct_work_bytes; three launches (zero, search, best)
+int launch_uct(int S, int n, const uint32_t *d_records, int n_records, const int32_t *d_index, int trees, int sims, uint32_t seed, int rules,
+               int max_plies, int komi2, int expand_at, int rave_equiv, int prior, int max_nodes, int32_t *d_visits, int32_t *d_wins2, int32_t *d_rave,
+               int32_t *d_own, int64_t *d_sums, int32_t *d_info, int32_t *d_trace, void *d_work, hipStream_t st);
 
 // The host-side checks sgo_session.hip needs: the table of `shape` at the context's size, checked, into HOST memory
 // (csrc/sgo_shapes.hip), and the bounds of the influence parameters (csrc/sgo_influence.hip) and of the solve parameters (csrc/sgo_solve.hip)
@@ -46,6 +51,9 @@ bool solve_params_ok(int rules, int max_region, int max_nodes, int max_targets);
 bool race_params_ok(int rules, int max_libs, int max_region, int max_nodes, int max_pairs);
 bool connect_params_ok(int rules, int cut_libs, int max_region, int max_nodes, int max_pairs);
 bool playout_params_ok(int S, int n, int per_row, int rules, int max_plies);   // csrc/sgo_playout.hip
+bool uct_params_ok(int S, int n, int trees, int sims, int rules, int max_plies, int komi2, int expand_at, int rave_equiv, int prior,
+                   int max_nodes);                                             // csrc/sgo_uct.hip
+size_t uct_work_bytes(int S, int n, int trees, int max_nodes);
 
 // One array of a host entry's device block.  `up` (or nullptr) is copied in before the launch, `down` (or nullptr) is filled
 // from it afterwards; an array with neither is only room.

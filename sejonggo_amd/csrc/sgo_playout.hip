@@ -13,15 +13,11 @@
 // two floods of k_rollout_step), the draw draw32 of the rollouts.
 //   `prev` of the next ply is the next mover's row as it was before this ply (what advance_record_rows hands to legal): after a pass
 //     it equals that colour's stones, so the ko test forbids nothing.
-//   SOUND (rules = 1): the points Board::legal leaves out and on which the stone would stand.  Such a point has no empty neighbour
-//     and captures nothing (else it were legal, or it is the ko point, which stays out), so its stone stands exactly when an adjacent
-//     own chain keeps a liberty elsewhere.  Own chains with a liberty that HAS an empty neighbour are found with one flood for all
-//     points at once; what is left (a point next to own chains whose liberties are all single holes) is decided one point at a time
-//     with one flood each.  Only points outside EYE are looked at: the others are no candidates anyway.  An illegal record may hold
-//     opponent chains without a liberty, which any neighbouring stone captures and Board::legal does not count: a unit that starts
-//     from such a record (found once per unit; a legal position never turns into one) pays one more flood per ply for them.
-//   EYE: two neighbour-row shifts of the opponent row give the four diagonals, the rest is bit operations per lane.
-//   PICK: popcount per row, inclusive scan over the half, the owning row resolves the bit: as k_rollout_step finds its weighted point.
+//   SOUND (rules = 1), EYE and PICK -- the candidate set of a ply and the uniform pick -- are in sgo_playout_core.hpp, which the
+//     playout tree search (sgo_uct.hip) inlines as well: the points Board::legal leaves out and on which the stone would stand, found
+//     with floods; two neighbour-row shifts of the opponent row for the four diagonals; popcount per row, inclusive scan over the
+//     half, the owning row resolves the bit.  A unit that starts from a record with a chain without a liberty (found once per unit)
+//     pays one more flood per ply.
 // UNITS: a unit is SGO_PLAYOUT_UNIT consecutive playouts j of one row, played by one half from first to last; a half whose playout
 // has ended takes the next one of its unit in the same trip.  Ownership, AMAF and sums accumulate in registers across the unit (at
 // 19x19 four tables of 19 VGPRs per lane) and leave with one round of integer atomics at its end.  The grid is capped and walks
@@ -38,6 +34,7 @@
 #include "sgo_draw.hpp"
 #include "sgo_engine_state.hpp"
 #include "sgo_half.hpp"
+#include "sgo_playout_core.hpp"
 #include "sgo_rows.hpp"
 
 namespace sgo {
@@ -62,9 +59,7 @@ __global__ __launch_bounds__(64) void k_playout(int n, const uint32_t *records, 
     const int half = threadIdx.x >> 5, y = threadIdx.x & 31;
     const rows::Board<S> bd(half, y);
     const long n_units = (long)n * upr;
-    // the masks of the eye test: a neighbour beyond the edge counts as the mover's; T = 1 on the edge, 2 inside
-    const uint32_t off_u = (y == 0) ? G::ROWMASK : 0u, off_d = (y == S - 1) ? G::ROWMASK : 0u;
-    const uint32_t edge = (y == 0 || y == S - 1) ? G::ROWMASK : (1u | (1u << (S - 1)));
+    const PlayoutCore<S> core(bd);
 
     for (long u0 = (long)blockIdx.x * 2; u0 < n_units; u0 += (long)gridDim.x * 2) {    // the trip count is the workgroup's
         const long u = u0 + half;
@@ -79,12 +74,7 @@ __global__ __launch_bounds__(64) void k_playout(int n, const uint32_t *records, 
         const bool start_white = rec ? ((rec[G::META_WORD] & G::META_BIT) != 0) : false;
         const uint32_t sprev = rec ? rows::load_row<S>(rec + (start_white ? 3 : 2) * G::NW, y) : 0u;
         const uint32_t g0 = (uint32_t)i * (uint32_t)per_row + (uint32_t)j0;
-        bool weird;                                                  // the record holds a chain without a liberty
-        {
-            const uint32_t e0 = ~(sb | sw) & bd.M, l0 = bd.nbr4(e0);
-            const uint32_t ab = bd.flood(sb & l0, sb), aw = bd.flood(sw & l0, sw);
-            weird = rows::half_any((sb & ~ab) | (sw & ~aw), half);
-        }
+        const bool weird = playout_weird<S>(bd, sb, sw);             // the record holds a chain without a liberty
 
         int bacc[S], wacc[S], acnt[S], asum[S];
 #pragma unroll
@@ -98,66 +88,9 @@ __global__ __launch_bounds__(64) void k_playout(int n, const uint32_t *records, 
 
         for (int trip = 0; trip < PLAYOUT_UNIT * max_plies; trip++) {
             if (!__any(active)) break;
-            const uint32_t emp = ~(own | opp) & bd.M;
-            // EYE: every on-board neighbour is the mover's, and fewer than T diagonals are the other colour's
-            uint32_t eye;
-            {
-                const uint32_t a4 = (rows::row_above(own) | off_u) & (rows::row_below(own) | off_d) & ((own << 1) | 1u) &
-                                    ((own >> 1) | (1u << (S - 1)));
-                const uint32_t oa = rows::row_above(opp), ob = rows::row_below(opp);
-                const uint32_t d1 = (oa << 1) & bd.M, d2 = oa >> 1, d3 = (ob << 1) & bd.M, d4 = ob >> 1;
-                const uint32_t ge1 = d1 | d2 | d3 | d4, ge2 = ((d1 | d2) & (d3 | d4)) | (d1 & d2) | (d3 & d4);
-                eye = emp & a4 & ~((edge & ge1) | ge2);
-            }
-            uint32_t allowed = bd.legal(own, opp, prev);
-            if (rules) {                                             // uniform over the launch
-                const uint32_t t0 = bd.nbr4(emp), e1 = emp & t0;
-                const uint32_t gone = prev & ~own;
-                const uint32_t ko = rows::half_one_bit(gone, half) ? gone : 0u;
-                const uint32_t cx = emp & ~t0 & ~allowed & ~ko & ~eye;
-                if (__any(cx != 0)) {
-                    const uint32_t safe = bd.flood(own & bd.nbr4(e1), own);
-                    uint32_t ex = cx & bd.nbr4(safe);
-                    if (__any(weird)) {
-                        const uint32_t live = bd.flood(opp & t0, opp);
-                        ex |= weird ? (cx & bd.nbr4(opp & ~live)) : 0u;
-                    }
-                    uint32_t rem = cx & ~ex;
-                    for (int q = 0; q < G::N; q++) {
-                        if (!__any(rem != 0)) break;
-                        const int a = lowest_point<S>(rem, half);    // -1: this half has none left
-                        const uint32_t pb = (a >= 0 && y == a / S) ? (1u << (a % S)) : 0u;
-                        rem &= ~pb;
-                        const uint32_t g = bd.flood(bd.nbr4(pb) & own, own);
-                        if (rows::half_any(bd.nbr4(g) & emp & ~pb, half)) ex |= pb;
-                    }
-                    allowed |= ex;
-                }
-            }
-            const uint32_t cand = allowed & ~eye;
-
-            // the (t + 1)-th lowest candidate
-            const int rc = __popc(cand);
-            int incl = rc;
-#pragma unroll
-            for (int s = 1; s < 32; s <<= 1) {
-                const int t = __shfl_up(incl, s, 32);
-                if (y >= s) incl += t;
-            }
-            const uint32_t k = (uint32_t)__shfl(incl, 31, 32);
-            const uint32_t t = (uint32_t)(((unsigned long long)draw32(seed, g0 + (uint32_t)j, (uint32_t)ply) * k) >> 32);
-            const uint32_t excl = (uint32_t)(incl - rc);
-            const bool mine = k != 0 && excl <= t && t < (uint32_t)incl;   // exactly one row when a candidate exists
-            int a_loc = 0;
-            {
-                uint32_t v = cand;
-                const uint32_t rank = t - excl;
-#pragma unroll
-                for (int x = 0; x < S - 1; x++) v &= ((uint32_t)x < rank && mine) ? (v - 1u) : ~0u;
-                a_loc = y * S + (v ? __builtin_ctz(v) : 0);
-            }
-            const uint32_t who = rows::half_ballot(mine, half);
-            const int a_pick = __shfl(a_loc, who ? (__ffs((int)who) - 1) : 0, 32);
+            const uint32_t cand = core.cand(own, opp, prev, rules, weird);
+            uint32_t k;                                              // the (t + 1)-th lowest candidate
+            const int a_pick = core.pick(cand, draw32(seed, g0 + (uint32_t)j, (uint32_t)ply), k);
             const int a = (active && k != 0) ? a_pick : G::N;        // no candidate: a pass
 
             const uint32_t before_opp = opp;

@@ -510,4 +510,32 @@ int sgo_session_playout(sgo_ctx *x, int n, const int32_t *slots, int per_row, ui
     });
 }
 
+int sgo_session_uct(sgo_ctx *x, int n, const int32_t *slots, int trees, int sims, uint32_t seed, int rules, int max_plies, int komi2, int expand_at,
+                    int rave_equiv, int prior, int max_nodes, int32_t *status, int32_t *visits, int32_t *wins2, int32_t *rave, int32_t *own,
+                    int64_t *sums, int32_t *info, void *stream) {
+    if (!x || !uct_params_ok(x->c.S, n, trees, sims, rules, max_plies, komi2, expand_at, rave_equiv, prior, max_nodes) ||
+        (n && (!slots || !status || !visits || !wins2 || !sums || !info))) {
+        set_error("sgo_session_uct: bad argument");
+        return SGO_ERR_ARG;
+    }
+    if (n == 0) return SGO_OK;
+    const Ctx &c = x->c;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)c.S * c.S, tb = sizeof(int32_t) * (N + 1);
+    // the workspace is this call's own; an optional table that was not asked for is a column without bytes
+    void *work = nullptr;
+    SGO_HIP(hipMalloc(&work, uct_work_bytes(c.S, n, trees, max_nodes)));
+    const RowCol cols[] = {{sums, sizeof(int64_t) * 8, 8}, {visits, tb, 4}, {wins2, tb, 4}, {info, sizeof(int32_t) * 4, 4},
+                           {rave ? rave : visits, rave ? 2 * tb : 0, 4}, {own ? own : visits, own ? sizeof(int32_t) * 2 * N : 0, 4}};
+    const int rc = session_rows(x, "sgo_session_uct", n, slots, nullptr, 0, status, cols, st, [&](const int32_t *d_index, const uint8_t *, uint8_t *const *d) {
+        return launch_uct(c.S, n, c.pos, ctx_records(c), d_index, trees, sims, seed, rules, max_plies, komi2, expand_at, rave_equiv, prior, max_nodes,
+                          reinterpret_cast<int32_t *>(d[1]), reinterpret_cast<int32_t *>(d[2]), rave ? reinterpret_cast<int32_t *>(d[4]) : nullptr,
+                          own ? reinterpret_cast<int32_t *>(d[5]) : nullptr, reinterpret_cast<int64_t *>(d[0]), reinterpret_cast<int32_t *>(d[3]),
+                          nullptr, work, st);
+    });
+    if (rc != SGO_OK) (void)hipStreamSynchronize(st);                // session_rows synchronised when it succeeded
+    (void)hipFree(work);
+    return rc;
+}
+
 }  // extern "C"

@@ -884,6 +884,27 @@ class SessionEngine(SelfPlayEngine):
                                     out.own, out.amaf, out.sums)
         return out
 
+    def uct(self, slots, trees=None, sims=None, seed=0, rules=1, komi=None, max_plies=0, expand_at=None, rave_equiv=None, prior=None,
+            max_nodes=None):
+        """Playout tree search from the root positions of the listed holding sessions (sgo_session_uct; include/sgo.h "playout tree
+        search"): a uct.Search with status int32 [n] beside its arrays (SGO_ERR_STATE: not a holding session; that row stays zero).
+        None takes the defaults of uct.py (untuned) and the context's komi.  No net is asked; an ESTIMATE of the best move, not a
+        proof.  Boards and trees are only read."""
+        from . import uct as U
+        trees, sims = U.TREES if trees is None else int(trees), U.SIMS if sims is None else int(sims)
+        expand_at = min(U.EXPAND_AT, sims) if expand_at is None else int(expand_at)
+        rave_equiv, prior = U.RAVE_EQUIV if rave_equiv is None else int(rave_equiv), U.PRIOR if prior is None else int(prior)
+        max_nodes = sims + 1 if max_nodes is None else int(max_nodes)
+        komi2 = U.komi2_of(self.komi if komi is None else komi)
+        U.check_args(self.S, trees, sims, rules, max_plies, komi2, expand_at, rave_equiv, prior, max_nodes)
+        n, N = len(slots), self.S * self.S
+        out = U.Search(self.S, np.zeros((n, N + 1), np.int32), np.zeros((n, N + 1), np.int32), np.zeros((n, 2, N + 1), np.int32),
+                       np.zeros((n, 2, N), np.int32), np.zeros((n, 8), np.int64), np.zeros((n, 4), np.int32))
+        out.info[:, 3] = -1
+        head = (trees, sims, int(seed) & 0xFFFFFFFF, int(rules), int(max_plies), komi2, expand_at, rave_equiv, prior, max_nodes)
+        out.status = self._analysis(self.lib.sgo_session_uct, slots, head, out.visits, out.wins2, out.rave, out.own, out.sums, out.info)
+        return out
+
     # ------------------------------------------------------------------ policy rollouts: how the games ended
     def rollouts(self, slots, per_src=None, seed=0, max_plies=None, symmetry="identity"):
         """Plays the positions of the listed holding sessions out `per_src` times each (None: conf['ROLLOUTS']) with the net's

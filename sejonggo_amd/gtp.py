@@ -330,6 +330,14 @@ class DeviceSejongGoEngine(object):
             self._playout_cache = (key, v, real_board(board))
         return self._playout_cache[1], self._playout_cache[2]
 
+    def uct(self, trees=None, sims=None, komi=0.0, seed=0, rules=1):
+        """Which move, by playout tree search (engine.SessionEngine.uct; include/sgo.h "playout tree search"): `trees` searches of
+        `sims` simulations each from the position on the board (None: the untuned defaults of uct.py) -- no net is asked.  Returns a
+        uct.Search with one row; board, tree and move number stay.  An ESTIMATE, not a proof."""
+        v = self._held(self.engine.uct([self.slot], trees=trees, sims=sims, seed=seed, rules=rules, komi=komi))
+        v.white_to_play = np.array([int(self.board[0, 0, 0, -1]) == -1])
+        return v
+
     def legal(self):
         """bool [S * S + 1]: the legal set of the position on the board (play.legal_moves flags the illegal ones)."""
         from .play import legal_moves
@@ -352,14 +360,25 @@ class GTPFailure(Exception):
 
 
 class GTPEngine(object):
-    def __init__(self, engine=None, book=None, book_min=1, superko=None, score="rollouts"):
-        """score: "rollouts" (default: final_score, final_status_list and sgo-ownership stand on policy rollouts, as ever) or
+    def __init__(self, engine=None, book=None, book_min=1, superko=None, score=None, player="net", uct_trees=None, uct_sims=None):
+        """player: "net" (default: genmove is the net's tree search, as ever) or "uct": genmove plays the best move of the playout
+        tree search (include/sgo.h "playout tree search"; uct_trees / uct_sims, None: the untuned defaults of uct.py), which asks
+        no net -- the device engine may stand on a stub net then, `score` defaults to "playouts", and every command that would call
+        the net answers a failure that says so; device engine only.
+        score: "rollouts" (default: final_score, final_status_list and sgo-ownership stand on policy rollouts, as ever) or
         "playouts" (they stand on light playouts, which ask no net); device engine only.
         book: a records.Book (or the path of its .npz) genmove answers from while it holds a legal move played at least
         book_min times; it needs the device engine (position keys come from the session slot).
         superko: None, or "positional" / "situational" (0 / 1): `play` refuses a move that repeats an earlier position of the game
         and genmove never makes one; it needs the device engine too (the move list is replayed on the device)."""
         self._komi = 0
+        if player not in ("net", "uct"):
+            raise ValueError("player is 'net' or 'uct'")
+        if player == "uct" and (engine is None or not hasattr(engine, "uct")):
+            raise ValueError("--player uct needs the device engine (gtp --device)")
+        self.player_kind, self.uct_trees, self.uct_sims = player, uct_trees, uct_sims
+        if score is None:
+            score = "playouts" if player == "uct" else "rollouts"
         if score not in ("rollouts", "playouts"):
             raise ValueError("score is 'rollouts' or 'playouts'")
         if score == "playouts" and (engine is None or not hasattr(engine, "playouts")):
@@ -397,7 +416,7 @@ class GTPEngine(object):
                           "genmove", "undo", "loadsgf", "clear_board", "final_score", "final_status_list", "sgo-analyze",
                           "sgo-ownership", "sgo-book", "sgo-ladders", "sgo-life", "sgo-find", "sgo-moves", "sgo-influence",
                           "sgo-estimate", "sgo-secure", "sgo-solve", "sgo-race", "sgo-connect", "sgo-groups", "sgo-superko", "sgo-playouts",
-                          "sgo-playout-moves", "quit"])
+                          "sgo-playout-moves", "sgo-uct", "quit"])
 
     def known_command(self, name=""):
         # the method name behind a hyphenated private command is accepted by parse_command too, so it is known as well
@@ -463,6 +482,24 @@ class GTPEngine(object):
             return []
         return self.book.moves(*self.sejong_engine.keys())
 
+    def _no_net(self, what):
+        """a command that would call the net, on an engine that was started without one"""
+        if self.player_kind == "uct":
+            raise GTPFailure("%s asks the net, and this engine was started with --player uct, without a model" % what)
+
+    def _uct_move(self, player, extra):
+        """genmove of --player uct: the most visited child of the playout tree search (ties: the larger wins2, the lower point) that
+        superko does not forbid, played as an external move through the slot's play; a pass when there is none"""
+        if player != self._to_move():
+            raise GTPFailure("genmove for the side that is not to move: play the missing move (or a pass) first")
+        v = self.sejong_engine.uct(self.uct_trees, self.uct_sims, float(self._komi))
+        points = self.size * self.size
+        ranked = v.ranked(0, lambda a: a not in extra)
+        best = ranked[0] if ranked else points
+        x, y = (best % self.size, best // self.size) if best < points else (0, self.size)
+        self.board, self.player = self.sejong_engine.play(player, x, y)
+        return self.print_move(x, y)
+
     def genmove(self, color):
         player = COLOR_TO_PLAYER[color]
         extra = set()
@@ -477,6 +514,8 @@ class GTPEngine(object):
                     x, y = (a % self.size, a // self.size) if a < self.size * self.size else (0, self.size)
                     self.board, self.player = self.sejong_engine.play(player, x, y)
                     return self.print_move(x, y)
+        if self.player_kind == "uct":
+            return self._uct_move(player, extra)
         if extra:
             return self._superko_move(player, extra)
         x, y, _, _, self.board, self.player = self.sejong_engine.genmove(player)
@@ -540,6 +579,7 @@ class GTPEngine(object):
     def sgo_analyze(self, sims=None, top=5, depth=8):
         """Private extension `sgo-analyze [sims]`: searches the position without moving and replies one line per top child --
         vertex, visits, mean, prior, pv vertices."""
+        self._no_net("sgo-analyze")
         analyze, report = self._engine_method("analyze"), self._engine_method("report")
         try:
             analyze(int(sims) if sims is not None else None)
@@ -565,6 +605,7 @@ class GTPEngine(object):
                 v, stones = playouts()
                 return v.row(0), stones
             return source
+        self._no_net("scoring by policy rollouts (--score rollouts)")
         return self._engine_method("rollouts")
 
     def final_score(self):
@@ -674,6 +715,22 @@ class GTPEngine(object):
             raise GTPFailure("at most %d playouts" % MAX_PER_ROW)
         v, _ = self._engine_method("playouts")(n, rules)
         return format_summary(v, 0) + "\n" + v.format_board(0)
+
+    def sgo_uct(self, *words):
+        """Private extension `sgo-uct [trees T] [sims K]`: the playout tree search from the position (include/sgo.h "playout tree
+        search"; default: the engine's --uct-trees / --uct-sims, else the untuned defaults of uct.py) at the GTP komi -- a head line
+        `best V winrate W simulations N nodes M depth D`, then one line `V visits winrate rave-visits rave-winrate` per move, the
+        ten most visited first; win rates are the side to move's.  No net is asked.  An ESTIMATE, not a proof."""
+        from .uct import MAX_SIMS, MAX_TREES, format_moves
+        opt = {"trees": self.uct_trees, "sims": self.uct_sims}
+        if len(words) % 2:
+            raise GTPFailure("syntax error")
+        for key, val in zip(words[::2], words[1::2]):
+            if key not in opt or not val.isdigit() or not 1 <= int(val) <= (MAX_TREES if key == "trees" else MAX_SIMS):
+                raise GTPFailure("syntax error")
+            opt[key] = int(val)
+        v = self._engine_method("uct")(opt["trees"], opt["sims"], float(self._komi))
+        return format_moves(v, 0, 10, self._vertex)
 
     def sgo_playout_moves(self, *words):
         """Private extension `sgo-playout-moves [K] [inherited]`: the K (default 10) best first moves of the side to move by the
@@ -863,7 +920,7 @@ class GTPEngine(object):
                "sgo-life": "sgo_life", "sgo-find": "sgo_find", "sgo-moves": "sgo_moves", "sgo-influence": "sgo_influence",
                "sgo-estimate": "sgo_estimate", "sgo-secure": "sgo_secure", "sgo-solve": "sgo_solve", "sgo-race": "sgo_race",
                "sgo-connect": "sgo_connect", "sgo-groups": "sgo_groups", "sgo-superko": "sgo_superko",
-               "sgo-playouts": "sgo_playouts", "sgo-playout-moves": "sgo_playout_moves"}      # GTP private extensions carry a hyphen; methods cannot
+               "sgo-playouts": "sgo_playouts", "sgo-playout-moves": "sgo_playout_moves", "sgo-uct": "sgo_uct"}      # GTP private extensions carry a hyphen; methods cannot
 
     def parse_command(self, line):
         tokens = line.strip().split(" ")
@@ -880,22 +937,32 @@ class GTPEngine(object):
         return "=\n\n" if not result.strip() else "= " + result + "\n\n"
 
 
-def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, superko=None, score="rollouts"):
+def main(inp=sys.stdin, out=sys.stdout, device=False, book=None, book_min=1, superko=None, score=None, player="net", uct_trees=None,
+         uct_sims=None):
     """device=True (`python -m sejonggo_amd.gtp --device`): the game lives on the device engine (DeviceSejongGoEngine).
     book (`--book FILE [--book-min N]`, device only): genmove plays from the opening book records.py wrote while it has a move.
     superko (`--superko positional|situational`, device only): `play` refuses and genmove avoids a move that repeats an earlier
-    position of the game."""
+    position of the game.
+    player "uct" (`--player uct [--uct-trees T --uct-sims K]`, device only): genmove plays the playout tree search's best move and the
+    engine starts WITHOUT loading a model: the session stands on the uniform stub net, which nothing asks."""
+    if player != "net" and not device:
+        sys.stderr.write("--player uct needs the device engine: run with --device\n")
+        return 2
     if book is not None and not device:
         sys.stderr.write("--book needs the device engine: run with --device\n")
         return 2
     if superko is not None and not device:
         sys.stderr.write("--superko needs the device engine: run with --device\n")
         return 2
-    if score != "rollouts" and not device:
+    if score not in (None, "rollouts") and not device:
         sys.stderr.write("--score playouts needs the device engine: run with --device\n")
         return 2
-    engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE']) if device else None, book=book,
-                       book_min=book_min, superko=superko, score=score)
+    net = None
+    if player == "uct":
+        from .stub_nets import make_stub
+        net = make_stub("uniform", conf['SIZE'])                     # a given net: no predicting worker starts, no model file is read
+    engine = GTPEngine(engine=DeviceSejongGoEngine(conf['MCTS_SIMULATIONS'], size=conf['SIZE'], net=net) if device else None, book=book,
+                       book_min=book_min, superko=superko, score=score, player=player, uct_trees=uct_trees, uct_sims=uct_sims)
     for line in inp:
         for cmd in line.split("\n"):
             res = engine.parse_command(cmd)
@@ -915,11 +982,17 @@ def _cli(argv):
     ap.add_argument("--book-min", type=int, default=1, help="play a book move only when it was played at least N times (default 1)")
     ap.add_argument("--superko", default=None, choices=("positional", "situational"),
                     help="refuse and avoid moves that repeat an earlier position of the game; needs --device")
-    ap.add_argument("--score", default="rollouts", choices=("rollouts", "playouts"),
+    ap.add_argument("--score", default=None, choices=("rollouts", "playouts"),
                     help="what final_score, final_status_list and sgo-ownership stand on: policy rollouts (default) or light playouts, "
-                         "which ask no net; needs --device")
+                         "which ask no net (the default with --player uct); needs --device")
+    ap.add_argument("--player", default="net", choices=("net", "uct"),
+                    help="who answers genmove: the net's tree search (default) or the playout tree search, which asks no net -- the "
+                         "engine then starts without loading a model; needs --device")
+    ap.add_argument("--uct-trees", type=int, default=None, help="independent searches per genmove of --player uct (default: uct.TREES)")
+    ap.add_argument("--uct-sims", type=int, default=None, help="simulations per search of --player uct (default: uct.SIMS)")
     a = ap.parse_args(argv)
-    return main(device=a.device, book=a.book, book_min=a.book_min, superko=a.superko, score=a.score)
+    return main(device=a.device, book=a.book, book_min=a.book_min, superko=a.superko, score=a.score, player=a.player, uct_trees=a.uct_trees,
+                uct_sims=a.uct_sims)
 
 
 if __name__ == "__main__":

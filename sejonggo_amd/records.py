@@ -517,6 +517,20 @@ class DeviceRecords(object):
             return z, (z.clone() if amaf else None), torch.zeros((0, 8), dtype=torch.int64, device=self.device)
         return playout_dev(self.S, self.records, index, n, per_row, seed, rules, max_plies, self.lib, amaf=amaf)
 
+    def uct(self, index, trees, sims, seed=0, rules=1, max_plies=0, komi2=0, expand_at=2, rave_equiv=256, prior=4, max_nodes=None):
+        """(visits, wins2 int32 [n, N + 1], rave int32 [n, 2, N + 1], own int32 [n, 2, N], sums int64 [n, 8], info int32 [n, 4]) device
+        tensors of the listed records: `trees` playout tree searches of `sims` simulations each (sgo_uct_dev, three launches;
+        include/sgo.h "playout tree search").  An index outside the object gives the zero row with best -1."""
+        from .uct import uct_dev
+        torch = self.torch
+        index = self._index(index)
+        n = int(index.shape[0])
+        if n == 0:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=self.device)      # noqa: E731
+            return z(0, self.N + 1), z(0, self.N + 1), z(0, 2, self.N + 1), z(0, 2, self.N), torch.zeros((0, 8), dtype=torch.int64, device=self.device), z(0, 4)
+        max_nodes = int(sims) + 1 if max_nodes is None else max_nodes
+        return uct_dev(self.S, self.records, index, n, trees, sims, seed, rules, max_plies, komi2, expand_at, rave_equiv, prior, max_nodes, self.lib)[:6]
+
     def moves(self, index, side=0, action=None, colour=None, rows_per_call=16384):
         """Move outcomes of the listed records (sgo_moves_dev, one launch per rows_per_call rows; include/sgo.h "move outcomes"); an
         index outside the object gives the zero row.  action None: (rows int16 [n, N, 8], counts int32 [n, 8]) device tensors, in
@@ -784,6 +798,23 @@ class RecordSet(object):
                                    lambda own, amaf, sums: Playouts(self.S, _host(own), _host(amaf), _host(sums, np.int64)), stones):
             ch.to_play = _host(self.backend.to_play(self._record_index(ch)), np.int8)
             ch.playouts.white_to_play = ch.to_play < 0
+            yield ch
+
+    def uct(self, trees=None, sims=None, seed=0, rules=1, komi=0.0, max_plies=0):
+        """Generator of Chunks as `replay` gives them, each with `uct`, a uct.Search with one row per RECORD of the chunk (one backend
+        call per chunk), rows as in `life`: the playout tree search from every position -- the root's move table and the move it
+        favours.  None: the untuned defaults of uct.py.  An ESTIMATE, not a proof.  The draws of a row depend on its place in the
+        chunk.  Records that were not written give the zero row with best None.  ch.to_play as in `playouts`."""
+        from . import uct as U
+        trees, sims = U.TREES if trees is None else int(trees), U.SIMS if sims is None else int(sims)
+        komi2, expand_at = U.komi2_of(komi), min(U.EXPAND_AT, sims)
+        U.check_args(self.S, trees, sims, rules, max_plies, komi2, expand_at, U.RAVE_EQUIV, U.PRIOR, sims + 1)
+        for ch in self._per_record("uct", lambda index: self.backend.uct(index, trees, sims, seed, rules, max_plies, komi2, expand_at, U.RAVE_EQUIV,
+                                                                         U.PRIOR, sims + 1),
+                                   lambda visits, wins2, rave, own, sums, info: U.Search(self.S, _host(visits), _host(wins2), _host(rave), _host(own),
+                                                                                         _host(sums, np.int64), _host(info))):
+            ch.to_play = _host(self.backend.to_play(self._record_index(ch)), np.int8)
+            ch.uct.white_to_play = ch.to_play < 0
             yield ch
 
     # ------------------------------------------------------------------ move outcomes

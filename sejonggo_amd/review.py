@@ -5,7 +5,7 @@ all positions) and read back in one launch (report).
     python -m sejonggo_amd.review game.sgf [--sims N] [--every k] [--top K] [--depth D] [--net best|hash|uniform]
                                            [--energy E] [--games n] [--json FILE] [--rollouts R] [--tactics] [--life]
                                            [--find SHAPE.txt] [--moves] [--influence] [--secure] [--solve] [--race] [--connect] [--superko [RULE]]
-                                           [--playouts R]
+                                           [--playouts R] [--uct [TREES SIMS]]
 
 One line per reviewed position: the move number, the move played there, its share of the root's visits and its mean value, the
 engine's best move with its mean, and the principal variation.  Position m is the board BEFORE move m of the record (set-up
@@ -37,7 +37,9 @@ move `repeats K` when it recreated the position K records before the one it was 
 net when nothing else asks for one.  --playouts R puts the mean score of R light playouts (records.RecordSet.playouts; include/sgo.h
 "light playouts": uniformly random moves that spare the mover's eyes, no net; black - white, komi-free) in front of every move with
 its change across the move in the mover's favour, and a last line names the three largest drops: an estimate, not a verdict, and
-again no net is loaded for it.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
+again no net is loaded for it.  --uct [TREES SIMS] puts `uct V W` in front of every move -- the move the playout tree search favours
+there (records.RecordSet.uct; include/sgo.h "playout tree search") and the win rate W of the side to move at the game's komi -- and
+flags the move `uct-agrees` or `uct-prefers V`: flags from an estimate, not verdicts, and no net is loaded.  More positions than --games slots run in chunks: one setup, one analyze, one report per chunk."""
 import argparse
 import contextlib
 import json
@@ -438,6 +440,32 @@ def add_playouts(rows, game, per_row, record_set=None, seed=0):
     return rows
 
 
+def uct_rows(game, record_set, trees=None, sims=None, seed=0):
+    """{move number: (best move text, win rate of the side to move, flag)} of the B / W moves of `game` from one RecordSet.uct pass
+    over a set that holds the game as its only record: what the playout tree search (include/sgo.h "playout tree search") favours
+    in the position in front of the move at the game's komi, and `uct-agrees` or `uct-prefers V`.  A flag from an estimate, not a
+    verdict."""
+    out = {}
+    for ch in record_set.uct(trees=trees, sims=sims, seed=seed, komi=game.komi if game.komi is not None else conf['KOMI']):
+        v = ch.uct
+        for m, _, r, action, colour in played_moves(game, ch):
+            best = v.best(r)
+            if best is not None:
+                text = vertex(best, game.size)
+                out[m] = (text, v.winrate(r), "uct-agrees" if best == action else "uct-prefers " + text)
+    return out
+
+
+def add_uct(rows, game, trees=None, sims=None, record_set=None, seed=0):
+    """Adds `uct_best`, `uct_winrate` and `uct_flags` to every row of a review.  record_set None: a device RecordSet of the game."""
+    with _record_set_of(game, record_set) as rs:
+        found = uct_rows(game, rs, trees, sims, seed)
+    for row in rows:
+        best, winrate, flag = found.get(row["move_number"], (None, None, None))
+        row["uct_best"], row["uct_winrate"], row["uct_flags"] = best, winrate, [flag] if flag else []
+    return rows
+
+
 def playout_summary(rows, top=3):
     """`playouts (estimate): largest drops M C V (-d) ...` of the rows add_playouts filled: the moves after which the mean playout
     score fell most for the mover"""
@@ -468,9 +496,11 @@ def format_row(row):
         text += "  | estimate %s gain %s" % (score_text(row["estimate"]), "-" if row.get("gain") is None else "%+d" % row["gain"])
     if row.get("playout_lead") is not None:
         text += "  | playouts %+.1f +- %.1f change %+.1f" % (row["playout_lead"], row["playout_sd"], row["playout_change"])
+    if row.get("uct_best") is not None:
+        text += "  | uct %s %.3f" % (row["uct_best"], row["uct_winrate"])
     flags = list(row.get("tactics") or []) + list(row.get("life_flags") or []) + list(row.get("find_flags") or []) + \
         list(row.get("moves_flags") or []) + list(row.get("secure_flags") or []) + list(row.get("solve_flags") or []) + \
-        list(row.get("race_flags") or []) + list(row.get("connect_flags") or []) + list(row.get("superko_flags") or [])
+        list(row.get("race_flags") or []) + list(row.get("connect_flags") or []) + list(row.get("superko_flags") or []) + list(row.get("uct_flags") or [])
     if flags:
         text += "  | " + " ".join(flags)
     return text
@@ -558,13 +588,20 @@ def main(argv=None, out=sys.stdout):
                     help="put the mean score of R light playouts (uniformly random moves that spare the mover's eyes, no net; black - "
                          "white, komi-free) in front of every move, with its change across the move in the mover's favour, and name the "
                          "three largest drops.  An estimate, not a verdict.  Like --influence it loads no net when nothing else asks for one")
+    ap.add_argument("--uct", nargs="*", type=int, default=None, metavar="N",
+                    help="--uct [TREES SIMS]: put the best move and the win rate (of the side to move, at the game's komi) of the playout "
+                         "tree search in front of every move, and flag it uct-agrees or uct-prefers V (flags from an estimate, not "
+                         "verdicts; default: the untuned trees and sims of uct.py).  Like --influence it loads no net when nothing else "
+                         "asks for one")
     ap.add_argument("--json", default=None, help="write the review as one JSON document to this file")
     a = ap.parse_args(argv)
+    if a.uct is not None and len(a.uct) not in (0, 2):
+        ap.error("--uct takes no values or TREES SIMS")
     from .engine import SessionEngine
     from .sgfload import load_file
     game = load_file(a.sgf)
     # --influence with nothing that asks for a search or a net: the record kernels alone
-    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect or a.superko or a.playouts) and a.sims is None and a.net is None and not a.rollouts)
+    searched = not ((a.influence or a.secure or a.solve or a.race or a.connect or a.superko or a.playouts or a.uct is not None) and a.sims is None and a.net is None and not a.rollouts)
     a.net = a.net or "best"
     sims = a.sims or conf['MCTS_SIMULATIONS']
     energy = a.energy or min(conf['ENERGY'], sims)
@@ -606,6 +643,8 @@ def main(argv=None, out=sys.stdout):
         add_influence(rows, game)
     if a.playouts:
         add_playouts(rows, game, a.playouts)
+    if a.uct is not None:
+        add_uct(rows, game, *(a.uct or (None, None)))
     for row in rows:
         out.write(format_row(row) + "\n")
     if a.influence:
